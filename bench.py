@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MSCKF-update benchmark (BASELINE.json metric: MSCKF features/sec per EKF update at a 30-clone state; ms/update at 1/2/4/8 GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one complete UpdaterMSCKF::update (triangulate + refine -> Jacobians -> nullspace projection -> chi2 gate ->
 measurement compression -> EKF update, UpdaterMSCKF.cpp:58-295) of a synthetic BASELINE.json snapshot with every input
@@ -17,7 +17,10 @@ record order, column-block lists: one launch), rebuilt on every step as a filter
 
 When WORLD_SIZE is not set and N > 1 the script launches its own N ranks (torch.distributed.run, 127.0.0.1).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times ONE loop of exactly K steps (ms_per_step = its time / K), writes the outputs of the last
+timed step when --dump-outputs is given, and prints ONE JSON line with the contract fields.  With --full, rank 0's line also
+carries what takes measurements of its own (below), and the headline loop of K steps is repeated (at least 3 times, until
+--min-timed-seconds have been timed) with the median reported:
   roofline           the per-feature stage (k_feat_rows, k_feat_qr, k_feat, k_feat_out of csrc/k_feat.h): algorithmic FLOPs of
                      SURVEY.md 8(d) of the features that reach the gate / its HIP-event time on the context's stream, against
                      the FP64 peak; `compression` = the same for the Gram accumulation on the matrix cores
@@ -25,6 +28,12 @@ Rank 0 prints ONE JSON line with the contract fields plus
   mode_a             ovgpu_msckf_compress host to host (the shims' unpatched mode): default route and Householder TSQR
   cpu_baseline       the oracle (float64 restatement of the reference's serial Eigen path) on this host: 1 thread, and all cores
                      for the per-feature loops; bounded sample, 5 repetitions after a warm-up, median.
+  ...                the secondary workloads (tight window, every gate factored, resident tables, configs[3] and the scaling
+                     model at N = 1; weak scaling, the prediction and the preflight at N > 1), box_probe, shim timings.
+
+--dump-outputs DIR writes the posterior the last timed step left resident (what a caller of the timed path reads back with
+ovgpu_get_state: P, clone_q_p, calib_q_p, intrinsics) as DIR/<name>.npy in float64.  The inputs are seeded: the same
+arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -50,9 +59,9 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--cfg", type=int, default=None, help="BASELINE.json config index + 1 (default: 3 at one GPU, 4 beyond)")
     ap.add_argument("--features", type=int, default=None, help="override the TOTAL number of features of the update")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive and the secondary (weak / single-GPU reference) measurements")
-    ap.add_argument("--shim-in-filter", action="store_true", help="also time the drop-in libraries (the shim compiled into the reference's own tree, when "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the PCIe-inclusive and the secondary (weak / single-GPU reference) measurements")
+    ap.add_argument("--shim-in-filter", action="store_true", help="--full: also time the drop-in libraries (the shim compiled into the reference's own tree, when "
                     "they were built: __graft_entry__.build) inside the reference's running filter: UpdaterMSCKF::update per frame, modes B and resident covariance")
     ap.add_argument("--route", choices=["gram", "tsqr"], default="gram")
     ap.add_argument("--stage-events-every", type=int, default=4, help="the library's per-stage HIP events (roofline durations) on every n-th update of the timed region")
@@ -62,8 +71,13 @@ def parse_args(argv=None):
                     help="headline batch on the N = 224 state of SURVEY 8(d) (camera calibration only) instead of BASELINE configs[2] as written "
                          "(\"online cam/IMU calib\": N = 248, the default at one GPU)")
     ap.add_argument("--min-timed-seconds", type=float, default=1.0,
-                    help="timed loops of exactly --steps updates are repeated (at least 3) until this much time has been timed: a utilisation sampler "
-                         "sees the run whatever --steps is")
+                    help="--full: timed loops of exactly --steps updates are repeated (at least 3) until this much time has been timed: a utilisation "
+                         "sampler sees the run whatever --steps is")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (roofline, secondary workloads, PCIe-inclusive, mode A, shim, box probe, CPU "
+                         "baseline, multi-rank preflight) and repeat the headline loop; a plain run times ONE loop of --steps updates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the posterior of the last timed step (P, clone_q_p, calib_q_p, intrinsics) as DIR/<name>.npy, float64")
     ap.add_argument("--debug-option", action="append", default=[], metavar="NAME=VALUE",
                     help="ovgpu_debug_option(NAME, VALUE) on every context before the batch is uploaded (developer A/Bs, e.g. featy_shape=1)")
     ap.add_argument("--resident-tables", action="store_true",
@@ -248,7 +262,7 @@ def main(argv=None):
     prob = synth.make_problem(cfg, F=args.features, imu_intrinsics=imu_intr)
     mine = parallel.shard_features(prob.meas_offsets, rank, world)
     preflight = None
-    if world > 1:
+    if world > 1 and args.full:
         # PREFLIGHT of a multi-rank run, on stderr before anything is timed (the first line a failed SCALE run leaves behind): every rank's
         # device, shard and the time of its shard as a stand-alone update, and the scaling model's prediction from them
         pre = {"rank": rank, "device": (torch.cuda.get_device_name(local_rank) if hook is None else "cpu (test hook)"), "features_this_rank": int(len(mine))}
@@ -268,10 +282,12 @@ def main(argv=None):
         if rank == 0:
             sys.stderr.write("[bench preflight] " + json.dumps(preflight) + "\n")  # (ONE write: the ranks share this pipe, print() writes the newline separately)
             sys.stderr.flush()
-    # the MEDIAN of the timed loops of K steps is the line's value (three loops, more until --min-timed-seconds have been timed)
+    # a plain run: ONE timed loop of K steps is the line's value; --full: the MEDIAN of the timed loops of K steps (three loops, more
+    # until --min-timed-seconds have been timed)
     err = None
     try:
-        dt, up, shard = run(prob, mine, args.steps, args.warmup, repeats=3, min_seconds=args.min_timed_seconds if hook is None else 0.0)
+        dt, up, shard = run(prob, mine, args.steps, args.warmup, repeats=3 if args.full else 1,
+                            min_seconds=args.min_timed_seconds if (args.full and hook is None) else 0.0)
     except Exception as e:  # noqa: BLE001
         if world == 1:
             raise
@@ -294,15 +310,17 @@ def main(argv=None):
                "rccl_rank": int(info["rccl_rank"]), "rccl_ranks": int(info["rccl_ranks"])}
         rank_records = [None] * world
         dist.all_gather_object(rank_records, rec)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(up, args.dump_outputs)
     headline_loops = [1e3 * x / args.steps for x in timed_loops]
     headline_rank_ms = [1e3 * x / args.steps for x in rank_loops]
-    kt = up.kernel_times(reset=True)
+    kt = up.kernel_times(reset=True) if args.full else None
     ms_per_step = 1e3 * dt / args.steps
     value = prob.F / (dt / args.steps)
 
     out = None
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world > 1:  # weak figure: the same per-GPU load whatever N
             wprob = synth.make_problem(cfg, F=(WEAK_FEATURES_PER_GPU if hook is None else hook.WEAK_FEATURES_PER_GPU) * world)
             wdt, wup, _ = run(wprob, parallel.shard_features(wprob.meas_offsets, rank, world), max(5, args.steps // 2), 2)
@@ -400,24 +418,6 @@ def main(argv=None):
                                        "model": "measured stand-alone update of rank 0's share (F / N features, this GPU) + modelled ring all-reduce of the "
                                                 f"{gram_bytes / 1e6:.2f} MB Gram matrix (2 (N - 1) steps x 8 us + bytes at 40 GB/s); not a measurement of N GPUs"}
     if rank == 0:
-        up.reset_state()   # (the timed loop left the posterior of its last update resident)
-        res = up.update()  # one synchronous update of the prior for the accept set (outside the timed region)
-        up.reset_state()
-        flops_system, flops_compress = gated_flops(shard, res["feat_status"], capi, synth)
-        ms_c, ms_s = kt["ms_compress"], kt["ms_system"]
-        achieved_c = flops_compress / (ms_c * 1e-3) / 1e12 if ms_c > 0 else 0.0
-        achieved = flops_system / (ms_s * 1e-3) / 1e12 if ms_s > 0 else 0.0
-        traffic = pmc_traffic_bytes(cfg if world == 1 and args.features is None else None)
-        gram = args.route == "gram"
-        # the Gram route executes r D^2 multiply-adds for what SURVEY.md 8(d) counts as 2 r D^2 (Householder-equivalent):
-        # its roofline fraction is quoted on the EXECUTED flops, the algorithmic rate beside it
-        exec_c = 0.5 * achieved_c if gram else achieved_c
-        # Round 6: with the unprojected stack (k_gram_regions) the products EXECUTED are the regions' own triangles — 512 flop per row and tile —, well under
-        # r D^2: the fraction is quoted on those, the dense and the Householder-equivalent counts beside it
-        stack_raw = bool(gram and not args.gram_fp32 and up.debug_option("last_stack_raw"))
-        exec_flops_c = 512.0 * up.debug_option("raw_gram_tile_rows") if stack_raw else (0.5 * flops_compress if gram else flops_compress)
-        if stack_raw:
-            exec_c = exec_flops_c / (ms_c * 1e-3) / 1e12 if ms_c > 0 else 0.0
         out = {
             "metric": "MSCKF features/sec per EKF update (30-clone state)",
             "value": value,
@@ -441,10 +441,31 @@ def main(argv=None):
                 "workload": (f"BASELINE.json configs[{cfg - 1}]: {prob.K}-camera radtan rig, {prob.C}-clone window, {prob.F} MSCKF features/update"
                              f"{' dealt over ' + str(world) + ' GPUs' if world > 1 else ''}, N={prob.N}, D={prob.Dmax}, online cam extrinsic+intrinsic calib{' + IMU intrinsics in the state' if imu_intr else ''}, FEJ"),
                 "features_total": prob.F, "features_this_rank": shard.F, "clones": prob.C, "cameras": prob.K, "state_dim": prob.N,
-                "measurements_total": prob.M, "features_used_rank0": int(res["stats"]["n_used"]),
+                "measurements_total": prob.M,
                 "parallelism": f"feature-shard x{world}, one all-reduce of the Gram matrix: {exchange['kind']}" if world > 1 else "single GPU",
             },
-            "roofline": {
+        }
+        if args.full:
+            up.reset_state()   # (the timed loop left the posterior of its last update resident)
+            res = up.update()  # one synchronous update of the prior for the accept set (outside the timed region)
+            up.reset_state()
+            flops_system, flops_compress = gated_flops(shard, res["feat_status"], capi, synth)
+            ms_c, ms_s = kt["ms_compress"], kt["ms_system"]
+            achieved_c = flops_compress / (ms_c * 1e-3) / 1e12 if ms_c > 0 else 0.0
+            achieved = flops_system / (ms_s * 1e-3) / 1e12 if ms_s > 0 else 0.0
+            traffic = pmc_traffic_bytes(cfg if world == 1 and args.features is None else None)
+            gram = args.route == "gram"
+            # the Gram route executes r D^2 multiply-adds for what SURVEY.md 8(d) counts as 2 r D^2 (Householder-equivalent):
+            # its roofline fraction is quoted on the EXECUTED flops, the algorithmic rate beside it
+            exec_c = 0.5 * achieved_c if gram else achieved_c
+            # Round 6: with the unprojected stack (k_gram_regions) the products EXECUTED are the regions' own triangles — 512 flop per row and tile —, well under
+            # r D^2: the fraction is quoted on those, the dense and the Householder-equivalent counts beside it
+            stack_raw = bool(gram and not args.gram_fp32 and up.debug_option("last_stack_raw"))
+            exec_flops_c = 512.0 * up.debug_option("raw_gram_tile_rows") if stack_raw else (0.5 * flops_compress if gram else flops_compress)
+            if stack_raw:
+                exec_c = exec_flops_c / (ms_c * 1e-3) / 1e12 if ms_c > 0 else 0.0
+            out["config"]["features_used_rank0"] = int(res["stats"]["n_used"])
+            out["roofline"] = {
                 "kernel": ("per-feature stage = k_feat_rows_sorted + k_feat_vt + k_feat_y (csrc/k_featy.h: Jacobian records, reflectors, then ONE kernel per "
                            "feature: whitened rows Y = H L as block products on the f64 matrix cores, projection and stacking, gate matrix Y Y^T + s^2 I as a "
                            "SYRK in accumulator registers, blocked Cholesky, chi2; gate matrices beyond 136 tiles (configs[4]): k_feat_y_big, csrc/k_featy_big.h, block row "
@@ -486,9 +507,8 @@ def main(argv=None):
                                  "achieved": (flops_system + flops_compress + ekf_flops(prob)) / (ms_per_step * 1e-3) / 1e12,
                                  "frac": (flops_system + flops_compress + ekf_flops(prob)) / (ms_per_step * 1e-3) / 1e12 / PEAK_FP64_TFLOPS},
                 "stage_events": f"HIP events around the stages on every {args.stage_events_every}th update of the timed region ({kt['launches']} updates sampled)",
-            },
-        }
-        if hook is None and not args.no_extras:
+            }
+        if hook is None and args.full and not args.no_extras:
             # What kind of box this is (ovgpu_debug_box_probe: shader clock idle and under matrix load, dependent-load latencies, launch
             # and dispatch rates).  Boxes of one pool run this binary 20 % apart (0.85 and 1.02 ms per update within minutes of each
             # other); the one slow box these probes were taken on showed the SAME values as the fast ones -- so the spread is not clock,
@@ -512,7 +532,7 @@ def main(argv=None):
         if hook is not None:
             out["test_hook"] = os.environ["OVGPU_BENCH_TEST_HOOK"] + ": host stand-in for the updater over gloo -- control flow only, NOT a measurement"
         out.update(extras)
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             out["pcie_inclusive_ms"] = pcie_inclusive_ms(prob, opts, local_rank)
             out["mode_a"] = mode_a_ms(prob, opts, local_rank, capi)
             out["shim"] = shim_dropin_ms(prob.F)
@@ -522,7 +542,7 @@ def main(argv=None):
             out["shim_resident_ms"] = (out["shim"] or {}).get("shim_resident_cov_ms")
             if args.shim_in_filter:
                 out["shim_in_filter"] = shim_in_filter_ms()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prob, opts)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -531,6 +551,15 @@ def main(argv=None):
     if world > 1:
         dist.destroy_process_group()
     return out
+
+
+def dump_outputs(up, directory):
+    """--dump-outputs: the posterior the timed path left resident after its last step, read back as a caller of
+    ovgpu_msckf_update_async does (ovgpu_get_state), one float64 DIR/<name>.npy per array (< 2 MB at every config)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in up.get_state(P=True).items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def pcie_inclusive_ms(prob, opts, device):

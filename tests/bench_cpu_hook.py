@@ -13,6 +13,8 @@ WEAK_FEATURES_PER_GPU = 6
 
 
 class Updater:
+    steps = 0  # update_async calls of every instance (tests/test_bench_launcher.py counts a plain run's steps)
+
     def __init__(self, opts, device=0):
         self.opts = opts
         self.prob = None
@@ -30,7 +32,11 @@ class Updater:
         pass
 
     def update_async(self):
+        Updater.steps += 1
         self.last = pyoracle.msckf_update(self.opts, self.v)
+
+    def get_state(self, P=True):
+        return {k: self.last[k] for k in ("clone_q_p", "calib_q_p", "intrinsics") + (("P",) if P else ())}
 
     def update_sharded_async(self):
         raise RuntimeError("the native sharded update needs the library")

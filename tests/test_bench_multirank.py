@@ -16,7 +16,8 @@ def test_two_rank_bench_runs_end_to_end_over_gloo():
     env["OVGPU_BENCH_TEST_HOOK"] = "tests.bench_cpu_hook"
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cfg", "4", "--features", "14"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cfg", "4", "--features", "14",
+                        "--full"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

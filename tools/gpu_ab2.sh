@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd /root/repo
 CUR=open_vins_amd/csrc/libovgpu.so
 cp $CUR /tmp/cur.so
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 run() { # name, args
   timeout 300 $B $2 > $OUT/$1.json 2>> $OUT/err
   python - $OUT/$1.json <<'PY'

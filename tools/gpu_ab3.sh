@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd /root/repo
 CUR=open_vins_amd/csrc/libovgpu.so
 cp $CUR /tmp/cur.so
-B="python bench.py --no-cpu-baseline --no-extras --steps ${STEPS:-300} --warmup 10"
+B="python bench.py --full --no-cpu-baseline --no-extras --steps ${STEPS:-300} --warmup 10"
 run() { # name
   timeout 60 $B > $OUT/$1.json 2>> $OUT/err
   python - $OUT/$1.json <<'PY'

@@ -29,7 +29,7 @@ timeout 60 python tools/dev_bitcompare.py dump /tmp/new.npz $P > $OUT/dump_new.t
 tail -2 $OUT/dump_new.txt
 echo "== new build against base" | tee -a $OUT/compare.txt
 python tools/dev_bitcompare.py compare /tmp/base_a.npz /tmp/new.npz 2>&1 | tee -a $OUT/compare.txt
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 run() { # name, args
   timeout 60 $B $2 > $OUT/$1.json 2>> $OUT/err
   python - $OUT/$1.json <<'PY'

@@ -6,8 +6,8 @@ TAG=${1:-final_light}
 OUT=/root/repo/gpurun_out/$TAG
 mkdir -p $OUT
 cd /root/repo
-timeout 200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 60 python bench.py --cfg 2 --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_cfg2.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 60 python bench.py --full --cfg 2 --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_cfg2.json 2>> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout 120 rocprofv3 --kernel-trace --stats -d $OUT/prof -o s -- python /root/repo/bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 --stage-events-every 1000 > /dev/null 2>&1
 cd /root/repo

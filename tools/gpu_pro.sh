@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_known_answer.py
 cat $OUT/pytest.txt
 CUR=open_vins_amd/csrc/libovgpu.so
 cp $CUR /tmp/cur.so
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 run() { # name, args
   timeout 300 $B $2 > $OUT/$1.json 2>> $OUT/err
   python - $OUT/$1.json <<'PY'

@@ -9,7 +9,7 @@ cd /root/repo
 timeout 170 python -m pytest tests/test_gpu_track_store.py tests/test_gpu_parity.py tests/test_ref_fixtures.py -q -m gpu -x -p no:cacheprovider \
   -k "track_store or long_lived or imu_intrinsics_state" 2>&1 | tail -15 > $OUT/pytest.txt
 cat $OUT/pytest.txt
-timeout 110 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 110 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.err
 python - $OUT/bench.json <<'PY'
 import json,sys

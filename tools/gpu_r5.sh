@@ -14,7 +14,7 @@ if [ -n "$KEXPR" ]; then
 fi
 CUR=open_vins_amd/csrc/libovgpu.so
 cp $CUR /tmp/cur.so
-B="python bench.py --no-cpu-baseline --no-extras --steps ${STEPS:-300} --warmup 10 ${BARGS:-}"
+B="python bench.py --full --no-cpu-baseline --no-extras --steps ${STEPS:-300} --warmup 10 ${BARGS:-}"
 run() { # name, extra args
   timeout 120 $B $2 > $OUT/$1.json 2>> $OUT/err
   python - $OUT/$1.json <<'PY'

@@ -15,7 +15,7 @@ for w in "$@"; do
     timeout 100 python tools/dev_featy_phases.py $n 2>&1 | grep -v amdgpu.ids | tee $OUT/phases_${which}_$w.txt
   done
 done
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 run() {
   timeout 90 $B $2 > $OUT/$1.json 2>> $OUT/err
   python - $OUT/$1.json <<'PY'

@@ -14,13 +14,13 @@ timeout 300 python -m pytest tests/test_rpng_sim_loop.py -m gpu -q -s -p no:cach
 timeout 120 open_vins_amd/shim/selftest --time 2000 9 > $OUT/shim_time.json 2>/dev/null
 timeout 120 open_vins_amd/shim/selftest --time 800 9 >> $OUT/shim_time.json 2>/dev/null
 timeout 300 python -m pytest tests/test_gpu_fullsize.py -q -s -p no:cacheprovider -k "conditioning_sweep or round1_route" 2>&1 | grep "cond(P_DD)\|gram then\|passed\|failed" > $OUT/conditioning_sweep.txt
-timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 120 python bench.py --cfg 2 --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_cfg2.json 2>> $OUT/bench.err
-timeout 120 python bench.py --cfg 2 --features 10000 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $OUT/bench_stereo_10k.json 2>> $OUT/bench.err
-timeout 120 python bench.py --cfg 4 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $OUT/bench_cfg4_one_gpu.json 2>> $OUT/bench.err
-timeout 120 python bench.py --route tsqr --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_tsqr.json 2>> $OUT/bench.err
-timeout 200 python bench.py --cfg 5 --features 2500 --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_cfg5_share_f64.json 2>> $OUT/bench.err
-timeout 200 python bench.py --cfg 5 --features 2500 --gram-fp32 --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_cfg5_share_fp32_gram.json 2>> $OUT/bench.err
+timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 120 python bench.py --full --cfg 2 --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_cfg2.json 2>> $OUT/bench.err
+timeout 120 python bench.py --full --cfg 2 --features 10000 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $OUT/bench_stereo_10k.json 2>> $OUT/bench.err
+timeout 120 python bench.py --full --cfg 4 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $OUT/bench_cfg4_one_gpu.json 2>> $OUT/bench.err
+timeout 120 python bench.py --full --route tsqr --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_tsqr.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --cfg 5 --features 2500 --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_cfg5_share_f64.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --cfg 5 --features 2500 --gram-fp32 --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_cfg5_share_fp32_gram.json 2>> $OUT/bench.err
 timeout 120 python tools/dev_mode_a_time.py 3 2>/dev/null > $OUT/mode_a_times.txt
 timeout 120 python tools/dev_mode_a_time.py 2 2>/dev/null >> $OUT/mode_a_times.txt
 timeout 120 python tools/dev_mode_a_time.py 4 1250 2>/dev/null >> $OUT/mode_a_times.txt
