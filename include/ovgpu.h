@@ -518,6 +518,65 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_stat
                             double *dx_seq, int32_t *N_out, double *P_out,
                             ovgpu_update_stats *stats);
 
+/* Mode A of UpdaterSLAM::delayed_init (UpdaterSLAM.cpp:61-251): the chain of ovgpu_slam_delayed_init run
+ * SPECULATIVELY, every feature's system exported in the form the stock StateHelper::initialize
+ * (StateHelper.cpp:393-481) takes, so that an unpatched reference applies them itself.  Inputs as
+ * ovgpu_slam_delayed_init (resident state and landmarks, the uploaded batch, feat_rep,
+ * ovgpu_set_feature_reps / _options, ovgpu_set_triangulation).  The triangulation runs once at entry
+ * (:121-144); feature f is linearised at the state the chain reached when it got there (:147-239:
+ * UpdaterHelper::get_feature_jacobian_full after the previous features' initialize), as the reference
+ * linearises it — provided the host's gate decisions agree with the device's (`status`).
+ *
+ * first_feature = k restarts the chain at feature k from the state resident NOW: features before k
+ * produce nothing (status -1).  After the host decided feature f differently, it uploads its own state
+ * (ovgpu_set_state / _landmarks / _features, the options, and ovgpu_set_triangulation with the entry
+ * triangulation and its anchors) and calls with first_feature = f + 1.
+ *
+ * No side effect on the resident state: P, clones, calibration, intrinsics, landmarks and the feature
+ * batch are what they were before the call (the chain works on copies); the triangulation of the call
+ * stays readable through ovgpu_get_triangulation.
+ *
+ * Per feature f, sys[f] (all F entries are written):
+ *   status        the device's decision: OVGPU_FEAT_USED (passed the gate, initialised in the chain),
+ *                 OVGPU_FEAT_CHI2_REJECTED, or the triangulation's failure; -1 for f < first_feature
+ *   feat_rep      the representation the feature is initialised in
+ *   rows, cols_f  rows of H_x / H_f / res and columns of H_f: 2m x 3, or (2m - 2) x 1 for
+ *                 ANCHORED_INVERSE_DEPTH_SINGLE after the bearing projection (:181-196); rows = 0: no
+ *                 system (status neither USED nor CHI2_REJECTED)
+ *   n_vars, h     Hx_order = var_id / var_size [var_off .. var_off + n_vars): (covariance id, size) of
+ *                 the clones, extrinsics and intrinsics the Jacobian touches, by covariance id; h = the
+ *                 sum of the sizes
+ *   H_x [hx_off .. + rows * h], H_f [hf_off .. + rows * cols_f], res [res_off .. + rows]: row-major.  An
+ *                 orthogonal transform of the reference's rows: [R1; 0] as H_f with Q^T [H_x | res]
+ *                 (initialize is invariant under it up to rounding); R = sigma_pix_f^2 I
+ *   chi2, chi2_thresh   the device's gate (NaN without a system)
+ *   anchor_cam, anchor_clone   the triangulation's anchor (Feature::anchor_cam_id, the clone of
+ *                 anchor_clone_timestamp)
+ *   p_seed[3]     what Landmark::set_from_xyz receives (:213-221): p_FinA for an anchored
+ *                 representation, p_FinG otherwise
+ * The ragged arrays are sized by ovgpu_slam_init_systems_len (same batch, feat_rep, first_feature);
+ * OVGPU_ERR_CAPACITY when `cap` is smaller.  stats->n_used = features the device accepted.          */
+typedef struct {
+  int64_t n_vars; /* entries of var_id / var_size */
+  int64_t n_hx;   /* doubles of H_x                */
+  int64_t n_hf;   /* doubles of H_f                */
+  int64_t n_res;  /* doubles of res                */
+} ovgpu_init_sizes;
+
+typedef struct {
+  int32_t status, feat_rep, rows, cols_f, n_vars, h, anchor_cam, anchor_clone;
+  int64_t var_off, hx_off, hf_off, res_off;
+  double chi2, chi2_thresh;
+  double p_seed[3];
+} ovgpu_init_system;
+
+int ovgpu_slam_init_systems_len(ovgpu_ctx *ctx, int32_t feat_rep, int32_t first_feature,
+                                ovgpu_init_sizes *sizes);
+int ovgpu_slam_init_systems(ovgpu_ctx *ctx, int32_t feat_rep, int32_t first_feature,
+                            const ovgpu_init_sizes *cap, ovgpu_init_system *sys, int32_t *var_id,
+                            int32_t *var_size, double *H_x, double *H_f, double *res,
+                            ovgpu_update_stats *stats);
+
 /* Landmarks resident after ovgpu_slam_update / ovgpu_slam_delayed_init: L_out = count,
  * value / fej [3*L] (representation coordinates), cov_id / anchor_cam / anchor_clone [L]. */
 int ovgpu_get_landmarks(ovgpu_ctx *ctx, int32_t *L_out, double *value, double *fej,

@@ -100,6 +100,18 @@ class UpdateStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
 
 
+class InitSizes(C.Structure):
+    """ovgpu_init_sizes: lengths of the ragged outputs of ovgpu_slam_init_systems."""
+    _fields_ = [("n_vars", C.c_int64), ("n_hx", C.c_int64), ("n_hf", C.c_int64), ("n_res", C.c_int64)]
+
+
+class InitSystem(C.Structure):
+    """ovgpu_init_system: one feature's system as StateHelper::initialize takes it (include/ovgpu.h)."""
+    _fields_ = [("status", C.c_int32), ("feat_rep", C.c_int32), ("rows", C.c_int32), ("cols_f", C.c_int32), ("n_vars", C.c_int32),
+                ("h", C.c_int32), ("anchor_cam", C.c_int32), ("anchor_clone", C.c_int32), ("var_off", C.c_int64), ("hx_off", C.c_int64),
+                ("hf_off", C.c_int64), ("res_off", C.c_int64), ("chi2", C.c_double), ("chi2_thresh", C.c_double), ("p_seed", C.c_double * 3)]
+
+
 def _ptr(a, ctype):
     if a is None:
         return None
@@ -229,6 +241,9 @@ def declare(lib):
         "ovgpu_get_landmarks": (C.c_int, [ctxp, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p]),
         "ovgpu_slam_delayed_init": (C.c_int, [ctxp, C.c_int32, c_int32_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p, c_int32_p,
                                               c_int32_p, c_double_p, c_int32_p, c_double_p, C.POINTER(UpdateStats)]),
+        "ovgpu_slam_init_systems_len": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(InitSizes)]),
+        "ovgpu_slam_init_systems": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(InitSizes), C.POINTER(InitSystem), c_int32_p, c_int32_p, c_double_p,
+                                              c_double_p, c_double_p, C.POINTER(UpdateStats)]),
         "ovgpu_slam_compress": (C.c_int, [ctxp, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_double_p,
                                           c_double_p, C.POINTER(UpdateStats)]),
         "ovgpu_slam_update": (C.c_int, [ctxp, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -160,6 +160,11 @@ struct ovgpu_ctx {
   // UpdaterSLAM::delayed_init
   DevBuf<double> Ppad, init_ws, dx_seq;
   DevBuf<int32_t> init_ctr, feat_slot;
+  // ovgpu_slam_init_systems: the chain runs on scratch copies and exports every feature's system (k_init_export)
+  bool init_export = false;         // the chain in flight is the speculative one: rejected features keep their rows
+  DevBuf<double> isx_arena, isx_save; // exported H_x | H_f | res of all features; the values the chain moves (clones, calibration, landmarks)
+  DevBuf<int32_t> isx_cols;         // per feature: the context's column of every H_x column, in Hx_order
+  std::vector<int32_t> h_isx_cols;
 
   // ---- features
   bool have_feats = false;

@@ -81,7 +81,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   if (p.slam) { // the landmarks' representation, not the MSCKF features'; single depth = MSCKF inverse depth Jacobians (UpdaterSLAM.cpp:338-341)
     p.lm_rep = c->lm_repd.p; // per landmark: k_system reads the representation and the size from the landmark each feature observes
   }
-  p.f_begin = 0, p.f_end = c->F, p.init = 0, p.init_out = nullptr, p.init_flag = nullptr, p.order = c->sys_order.p;
+  p.f_begin = 0, p.f_end = c->F, p.init = 0, p.init_out = nullptr, p.init_flag = nullptr, p.init_keep = 0, p.order = c->sys_order.p;
   HIPCHK(c->rows_used.reserve(2));
   p.rows_used = c->rows_used.p;
   p.Lw = (whiten && f_one < 0) ? c->Lw.p : nullptr;
@@ -96,6 +96,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     p.order = nullptr;
     p.rows_used = nullptr;
     p.f_begin = f_one, p.f_end = f_one + 1, p.init = 1, p.init_out = c->init_ws.p, p.init_flag = c->init_ctr.p + 2;
+    p.init_keep = c->init_export ? 1 : 0; // ovgpu_slam_init_systems: the host decides the gate again, rejected features are exported too
     p.opt.feat_rep = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH : init_rep; // UpdaterSLAM.cpp:151-155
     p.init_dof_less = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 2 : 0;
     grid = 1;

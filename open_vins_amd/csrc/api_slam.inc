@@ -150,6 +150,34 @@ int ovgpu_slam_compress(ovgpu_ctx *c, const int32_t *lm_index, int32_t *feat_sta
 // (the rows / columns of landmarks that do not exist yet are zero, which every kernel of the update treats exactly), the
 // current dimension and landmark count live in a device counter.
 // ---------------------------------------------------------------------------
+// One feature of the delayed initialisation's chain (UpdaterSLAM.cpp:147-239) at the state the previous ones left: its system, StateHelper::
+// initialize_invertible, the EKF update of its 2m - 3 projected rows (StateHelper.cpp:476-478) and the resident landmarks' share of it.  `exp`
+// (ovgpu_slam_init_systems): the system is copied out between the first two.  Lcap: landmark slots the update kernel covers.
+static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap, size_t init_lds, double *dx, const InitExportParams *exp) {
+  hipStream_t s = c->stream;
+  const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+  int rc = enqueue_system(c, f, rep);
+  if (rc != OVGPU_OK) return rc;
+  if (exp && exp->rows * std::max(exp->h, 3) > 0) {
+    hipLaunchKernelGGL(k_init_export, dim3((exp->rows * std::max(exp->h, 3) + 255) / 256), dim3(256), 0, s, *exp);
+    HIPCHK(hipGetLastError());
+  }
+  InitParams ip;
+  ip.N = Nmax, ip.D = c->D, ip.LD = c->LD, ip.rep = rep, ip.f = f, ip.sz = lm_dof(rep), ip.col_cov = c->col_cov.p, ip.init_out = c->init_ws.p, ip.P = c->P.p;
+  ip.sigma2 = c->dopt.sigma_pix_sq, ip.ctr = c->init_ctr.p, ip.p_FinG = c->pG.p, ip.p_FinA = c->pA.p, ip.meas_cc = c->meas_cc.p;
+  ip.anchor_meas = c->anchor.p, ip.lm = landmark_store(c), ip.feat_slot = c->feat_slot.p;
+  hipLaunchKernelGGL(k_init_invertible, dim3(1), dim3(256), init_lds, s, ip);
+  HIPCHK(hipGetLastError());
+  EkfJob job;
+  job.R = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, job.rows = 2 * m - 3, job.pred = c->init_ctr.p + 2, job.dx = dx;
+  job.keep_flags = true;
+  if ((rc = enqueue_ekf(c, job)) != OVGPU_OK) return rc;
+  hipLaunchKernelGGL(k_landmark_update, dim3((3 * Lcap + 255) / 256), dim3(256), 0, s, 0, (const int32_t *)(c->init_ctr.p + 1), (const int32_t *)c->lm_repd.p, job.dx,
+                     c->lm_cov.p, c->lm_val.p, job.pred);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
 int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
                             double *lm_value, double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone, double *dx_seq, int32_t *N_out,
                             double *P_out, ovgpu_update_stats *stats) {
@@ -214,22 +242,8 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   const size_t init_lds = ((size_t)3 * c->LD + (size_t)3 * Nmax + 16) * sizeof(double);
   // ---- 4. one feature after the other (UpdaterSLAM.cpp:147-239)
   for (int f = 0; f < F && rc == OVGPU_OK; f++) {
-    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
-    if (m < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
-    if ((rc = enqueue_system(c, f, rep_of(f))) != OVGPU_OK) break;
-    InitParams ip;
-    ip.N = Nmax, ip.D = c->D, ip.LD = c->LD, ip.rep = rep_of(f), ip.f = f, ip.sz = lm_dof(rep_of(f)), ip.col_cov = c->col_cov.p, ip.init_out = c->init_ws.p, ip.P = c->P.p;
-    ip.sigma2 = c->dopt.sigma_pix_sq, ip.ctr = c->init_ctr.p, ip.p_FinG = c->pG.p, ip.p_FinA = c->pA.p, ip.meas_cc = c->meas_cc.p;
-    ip.anchor_meas = c->anchor.p, ip.lm = landmark_store(c), ip.feat_slot = c->feat_slot.p;
-    hipLaunchKernelGGL(k_init_invertible, dim3(1), dim3(256), init_lds, s, ip);
-    HIPCHK(hipGetLastError());
-    EkfJob job;
-    job.R = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, job.rows = 2 * m - 3, job.pred = c->init_ctr.p + 2, job.dx = c->dx_seq.p + (size_t)f * Nmax;
-    job.keep_flags = true;
-    if ((rc = enqueue_ekf(c, job)) != OVGPU_OK) break; // StateHelper.cpp:476-478
-    hipLaunchKernelGGL(k_landmark_update, dim3((3 * (L0 + F) + 255) / 256), dim3(256), 0, s, 0, (const int32_t *)(c->init_ctr.p + 1), (const int32_t *)c->lm_repd.p, job.dx,
-                       c->lm_cov.p, c->lm_val.p, job.pred);
-    HIPCHK(hipGetLastError());
+    if (c->h_offsets[f + 1] - c->h_offsets[f] < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
+    rc = enqueue_init_feature(c, f, rep_of(f), Nmax, L0 + F, init_lds, c->dx_seq.p + (size_t)f * Nmax, nullptr);
   }
   // ---- results
   int32_t ctr[4] = {N0, L0, 0, 0};
@@ -315,6 +329,240 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   return OVGPU_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// Mode A of UpdaterSLAM::delayed_init: the chain of ovgpu_slam_delayed_init run speculatively on scratch copies, every feature's
+// system exported in the form StateHelper::initialize takes (k_init_export).  The host replays the systems through its own
+// initialize and calls again from the feature after the first one whose gate it decided differently.
+// ---------------------------------------------------------------------------
+// The ragged outputs' layout, from the batch alone: every feature from `first` on with two measurements or more gets 2m rows (2m - 2 for
+// the single depth) and the variables its measurements touch (UpdaterHelper::get_feature_jacobian_full's Hx_order: the clones, the
+// extrinsics and intrinsics of the observing cameras that the state estimates; an anchor is one of the feature's own clones / cameras),
+// ordered by covariance id.  Reads the packed measurement codes back (one synchronisation).
+struct InitSysLayout {
+  ovgpu_init_sizes tot{};
+  std::vector<int32_t> rows, nvar, h, var_id, var_size, cols; // cols: the context's column of every H_x column, feature after feature
+  std::vector<int64_t> var_off, hx_off, hf_off, res_off, col_off;
+};
+static int init_sys_layout(ovgpu_ctx *c, int32_t feat_rep, int first, InitSysLayout &lo) {
+  if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state was never called");
+  if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features was never called (or the state changed since)");
+  if (feat_rep < OVGPU_REP_GLOBAL_3D || feat_rep > OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) return set_err(OVGPU_ERR_INVALID, "unknown landmark representation");
+  const int F = c->F, M = c->M;
+  if (first < 0 || first > F) return set_err(OVGPU_ERR_INVALID, "first_feature out of range");
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<uint16_t> cc(std::max(M, 1));
+  if (M > 0) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(upload_sync(c, c->stream));
+  const bool per_feature = (int)c->h_feat_rep.size() == F && F > 0;
+  std::vector<int32_t> col_of(std::max(c->N, 1), -1);
+  for (int j = 0; j < c->D; j++) col_of[c->h_col_cov[j]] = j;
+  lo = InitSysLayout();
+  lo.rows.assign(F, 0), lo.nvar.assign(F, 0), lo.h.assign(F, 0);
+  lo.var_off.assign(F, 0), lo.hx_off.assign(F, 0), lo.hf_off.assign(F, 0), lo.res_off.assign(F, 0), lo.col_off.assign(F, 0);
+  std::vector<std::pair<int32_t, int32_t>> vars; // (covariance id, size)
+  std::vector<char> seen_clone(c->C), seen_cam(c->K);
+  for (int f = 0; f < F; f++) {
+    lo.var_off[f] = lo.tot.n_vars, lo.hx_off[f] = lo.tot.n_hx, lo.hf_off[f] = lo.tot.n_hf, lo.res_off[f] = lo.tot.n_res, lo.col_off[f] = (int64_t)lo.cols.size();
+    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+    if (f < first || m < 2) continue;
+    const bool single = (per_feature ? (int)c->h_feat_rep[f] : (int)feat_rep) == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE;
+    vars.clear();
+    std::fill(seen_clone.begin(), seen_clone.end(), 0), std::fill(seen_cam.begin(), seen_cam.end(), 0);
+    for (int i = c->h_offsets[f]; i < c->h_offsets[f + 1]; i++) {
+      const int cam = cc[i] >> 10, cl = cc[i] & 1023;
+      if (!seen_clone[cl]) seen_clone[cl] = 1, vars.push_back({c->h_clone_cov[cl], 6});
+      if (!seen_cam[cam]) {
+        seen_cam[cam] = 1;
+        if (c->h_calib_cov[cam] >= 0) vars.push_back({c->h_calib_cov[cam], 6});
+        if (c->h_intr_cov[cam] >= 0) vars.push_back({c->h_intr_cov[cam], 8});
+      }
+    }
+    std::sort(vars.begin(), vars.end());
+    int h = 0;
+    for (const auto &v : vars) {
+      lo.var_id.push_back(v.first), lo.var_size.push_back(v.second);
+      for (int i = 0; i < v.second; i++) lo.cols.push_back(col_of[v.first + i]);
+      h += v.second;
+    }
+    const int rows = single ? 2 * m - 2 : 2 * m;
+    lo.rows[f] = rows, lo.nvar[f] = (int)vars.size(), lo.h[f] = h;
+    lo.tot.n_vars += (int64_t)vars.size(), lo.tot.n_hx += (int64_t)rows * h, lo.tot.n_hf += (int64_t)rows * (single ? 1 : 3), lo.tot.n_res += rows;
+  }
+  return OVGPU_OK;
+}
+
+int ovgpu_slam_init_systems_len(ovgpu_ctx *c, int32_t feat_rep, int32_t first_feature, ovgpu_init_sizes *sizes) {
+  if (!c || !sizes) return set_err(OVGPU_ERR_INVALID, "null argument");
+  InitSysLayout lo;
+  const int rc = init_sys_layout(c, feat_rep, first_feature, lo);
+  if (rc != OVGPU_OK) return rc;
+  *sizes = lo.tot;
+  return OVGPU_OK;
+}
+
+int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_feature, const ovgpu_init_sizes *cap, ovgpu_init_system *sys, int32_t *var_id,
+                            int32_t *var_size, double *H_x, double *H_f, double *res, ovgpu_update_stats *stats) {
+  if (!c || !cap) return set_err(OVGPU_ERR_INVALID, "null argument");
+  { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }  // the chain uses the factorisation's work matrices
+  InitSysLayout lo;
+  int rc = init_sys_layout(c, feat_rep, first_feature, lo);
+  if (rc != OVGPU_OK) return rc;
+  const int F = c->F, N0 = c->N, L0 = c->L, C = c->C, K = c->K, first = first_feature;
+  if (F > 0 && !sys) return set_err(OVGPU_ERR_INVALID, "null sys");
+  if ((lo.tot.n_vars > 0 && (!var_id || !var_size)) || (lo.tot.n_hx > 0 && !H_x) || (lo.tot.n_hf > 0 && (!H_f || !res)))
+    return set_err(OVGPU_ERR_INVALID, "null output arrays");
+  if (cap->n_vars < lo.tot.n_vars || cap->n_hx < lo.tot.n_hx || cap->n_hf < lo.tot.n_hf || cap->n_res < lo.tot.n_res)
+    return set_err(OVGPU_ERR_CAPACITY, "output capacities below ovgpu_slam_init_systems_len");
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const bool per_feature = (int)c->h_feat_rep.size() == F && F > 0;
+  auto rep_of = [&](int f) { return per_feature ? (int)c->h_feat_rep[f] : (int)feat_rep; };
+  int Nmax = N0, r_max = 1;
+  bool new_anchored = false;
+  for (int f = first; f < F; f++) {
+    Nmax += lm_dof(rep_of(f)), new_anchored = new_anchored || rep_of(f) >= OVGPU_REP_ANCHORED_3D;
+    r_max = std::max(r_max, 2 * (c->h_offsets[f + 1] - c->h_offsets[f]) - 3);
+  }
+  hipStream_t s = c->stream;
+  // the row layout of the delayed initialisation (as ovgpu_slam_delayed_init); the batch's own is put back at the end
+  const int stride0 = c->row_stride;
+  const bool slam_rows0 = c->slam_rows;
+  const int want_stride = (new_anchored || c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D || lm_any_anchored(c)) ? 72 : 48;
+  if (c->slam_rows || want_stride != c->row_stride) {
+    c->row_stride = want_stride;
+    if ((rc = set_row_layout(c, false)) != OVGPU_OK) return rc;
+  }
+  // ---- workspaces
+  if ((rc = reserve_landmarks(c, L0 + F, L0)) != OVGPU_OK) return rc;
+  const size_t n_out = (size_t)(lo.tot.n_hx + lo.tot.n_hf + lo.tot.n_res);
+  const size_t n_save = (size_t)7 * C + 7 * K + 8 * K + 3 * L0;
+  HIPCHK(c->Ppad.reserve((size_t)Nmax * Nmax));
+  HIPCHK(c->init_ws.reserve((size_t)3 * c->LD + 16));
+  HIPCHK(c->init_ctr.reserve(4));
+  HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
+  HIPCHK(c->dx_seq.reserve(Nmax));
+  HIPCHK(c->Mt.reserve((size_t)std::max(r_max, c->D) * Nmax));
+  HIPCHK(c->Aaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
+  HIPCHK(c->Yaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
+  HIPCHK(c->dx.reserve(Nmax));
+  HIPCHK(c->isx_arena.reserve(std::max<size_t>(n_out, 1)));
+  HIPCHK(c->isx_cols.reserve(std::max<size_t>(lo.cols.size(), 1)));
+  HIPCHK(c->isx_save.reserve(n_save));
+  // ---- what the chain moves, kept aside: clones, calibration, intrinsics, the resident landmarks' values
+  double *sv = c->isx_save.p;
+  HIPCHK(hipMemcpyAsync(sv, c->clone_qp.p, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(sv + 7 * C, c->calib_qp.p, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(sv + 7 * C + 7 * K, c->intr.p, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
+  if (L0 > 0) HIPCHK(hipMemcpyAsync(sv + 7 * C + 15 * K, c->lm_val.p, sizeof(double) * 3 * L0, hipMemcpyDeviceToDevice, s));
+  // ---- the triangulation at entry (UpdaterSLAM.cpp:121-144), or the caller's (ovgpu_set_triangulation: a restart)
+  if (!c->given_tri) {
+    if ((rc = enqueue_triangulate(c)) != OVGPU_OK) return rc;
+  } else if (F > 0) {
+    HIPCHK(hipMemcpyAsync(c->status.p, c->given_status.p, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
+  }
+  // ---- the chain works on a padded copy of P; the resident one waits in Ppad
+  {
+    dim3 g((Nmax + 255) / 256, Nmax);
+    hipLaunchKernelGGL(k_cov_copy, g, dim3(256), 0, s, N0, Nmax, c->P.p, N0, c->Ppad.p, Nmax);
+    HIPCHK(hipGetLastError());
+    std::swap(c->P, c->Ppad);
+    c->N = Nmax;
+  }
+  const int32_t ctr0[4] = {N0, L0, 0, 0};
+  HIPCHK(upload(c->init_ctr.p, ctr0, sizeof(ctr0), s));
+  if (!lo.cols.empty()) HIPCHK(upload(c->isx_cols.p, lo.cols.data(), sizeof(int32_t) * lo.cols.size(), s));
+  HIPCHK(upload_sync(c, s)); // (host sources on the stack)
+  HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
+  HIPCHK(hipMemsetAsync(c->feat_slot.p, 0xFF, sizeof(int32_t) * std::max(F, 1), s));
+  const size_t init_lds = ((size_t)3 * c->LD + (size_t)3 * Nmax + 16) * sizeof(double);
+  double *a_hx = c->isx_arena.p, *a_hf = a_hx + lo.tot.n_hx, *a_res = a_hf + lo.tot.n_hf;
+  c->init_export = true;
+  for (int f = first; f < F && rc == OVGPU_OK; f++) {
+    if (lo.rows[f] == 0) continue; // fewer than two measurements: OVGPU_FEAT_TOO_FEW_MEAS
+    InitExportParams ep;
+    ep.LD = c->LD, ep.D = c->D, ep.h = lo.h[f], ep.rows = lo.rows[f], ep.single = rep_of(f) == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE, ep.f = f;
+    ep.init_out = c->init_ws.p, ep.stack = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, ep.cols = c->isx_cols.p + lo.col_off[f];
+    ep.feat_sigma = c->have_feat_sigma ? c->feat_sigma.p : nullptr, ep.sigma = std::sqrt(c->dopt.sigma_pix_sq);
+    ep.Hx = a_hx + lo.hx_off[f], ep.Hf = a_hf + lo.hf_off[f], ep.res = a_res + lo.res_off[f];
+    rc = enqueue_init_feature(c, f, rep_of(f), Nmax, L0 + F, init_lds, c->dx_seq.p, &ep);
+  }
+  c->init_export = false;
+  // ---- results: one gather, one synchronisation
+  std::vector<int32_t> st(std::max(F, 1), OVGPU_FEAT_TOO_FEW_MEAS), am(std::max(F, 1), -1), slot(std::max(F, 1), -1);
+  std::vector<double> x2(std::max(F, 1)), thr(std::max(F, 1)), pA(3 * (size_t)std::max(F, 1)), pG(3 * (size_t)std::max(F, 1));
+  std::vector<uint16_t> cc(std::max(c->M, 1), 0);
+  int32_t flags[4] = {0, 0, 0, 0};
+  if (rc == OVGPU_OK && F > 0) {
+    HIPCHK(hipMemcpyAsync(st.data(), c->status.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(x2.data(), c->chi2.p, sizeof(double) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(thr.data(), c->chi2_thr.p, sizeof(double) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(slot.data(), c->feat_slot.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pA.data(), c->pA.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pG.data(), c->pG.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if (!c->given_tri || c->given_has_anchor) HIPCHK(hipMemcpyAsync(am.data(), c->anchor.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
+    if (c->M > 0) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * c->M, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(flags, c->flags.p, sizeof(flags), hipMemcpyDeviceToHost, s));
+    if (lo.tot.n_hx > 0) HIPCHK(hipMemcpyAsync(H_x, a_hx, sizeof(double) * lo.tot.n_hx, hipMemcpyDeviceToHost, s));
+    if (lo.tot.n_hf > 0) HIPCHK(hipMemcpyAsync(H_f, a_hf, sizeof(double) * lo.tot.n_hf, hipMemcpyDeviceToHost, s));
+    if (lo.tot.n_res > 0) HIPCHK(hipMemcpyAsync(res, a_res, sizeof(double) * lo.tot.n_res, hipMemcpyDeviceToHost, s));
+  }
+  // ---- the resident state as it was: P back from Ppad, the saved values, the pose tables, the batch's row layout
+  std::swap(c->P, c->Ppad);
+  c->N = N0;
+  HIPCHK(hipMemcpyAsync(c->clone_qp.p, sv, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->calib_qp.p, sv + 7 * C, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->intr.p, sv + 7 * C + 7 * K, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
+  if (L0 > 0) HIPCHK(hipMemcpyAsync(c->lm_val.p, sv + 7 * C + 15 * K, sizeof(double) * 3 * L0, hipMemcpyDeviceToDevice, s));
+  {
+    const int rct = launch_build_tables(c);
+    if (rc == OVGPU_OK) rc = rct;
+  }
+  if (c->row_stride != stride0 || c->slam_rows != slam_rows0) {
+    c->row_stride = stride0;
+    const int rcl = set_row_layout(c, slam_rows0);
+    if (rc == OVGPU_OK) rc = rcl;
+  }
+  HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
+  c->ctrl_pre = 0; // the chain used the control block: the next update zeroes what it needs itself
+  HIPCHK(upload_sync(c, s));
+  if (rc != OVGPU_OK) return rc;
+  // ---- per feature
+  const double qnan = std::nan("");
+  for (int i = 0; i < lo.tot.n_vars; i++) var_id[i] = lo.var_id[i], var_size[i] = lo.var_size[i];
+  int n_acc = 0;
+  for (int f = 0; f < F; f++) {
+    ovgpu_init_system &o = sys[f];
+    std::memset(&o, 0, sizeof(o));
+    o.feat_rep = rep_of(f);
+    o.var_off = lo.var_off[f], o.hx_off = lo.hx_off[f], o.hf_off = lo.hf_off[f], o.res_off = lo.res_off[f];
+    o.chi2 = o.chi2_thresh = qnan;
+    o.anchor_cam = o.anchor_clone = -1;
+    if (f < first) {
+      o.status = -1;
+      continue;
+    }
+    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+    o.status = m < 2 ? OVGPU_FEAT_TOO_FEW_MEAS : st[f];
+    const bool has_system = lo.rows[f] > 0 && (o.status == OVGPU_FEAT_USED || o.status == OVGPU_FEAT_CHI2_REJECTED);
+    if (has_system) {
+      o.rows = lo.rows[f], o.n_vars = lo.nvar[f], o.h = lo.h[f], o.cols_f = o.feat_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 1 : 3;
+      o.chi2 = x2[f], o.chi2_thresh = thr[f];
+    }
+    n_acc += slot[f] >= 0;
+    if (am[f] >= 0 && am[f] < c->M) o.anchor_cam = cc[am[f]] >> 10, o.anchor_clone = cc[am[f]] & 1023;
+    const double *p = (o.feat_rep >= OVGPU_REP_ANCHORED_3D ? pA.data() : pG.data()) + 3 * f;
+    for (int i = 0; i < 3; i++) o.p_seed[i] = p[i];
+  }
+  if (stats) stats->n_used = n_acc, stats->D = c->D;
+  int status = OVGPU_OK;
+  if (flags[0]) status = OVGPU_ERR_NOT_SPD;
+  else if (flags[1]) status = OVGPU_ERR_NEGATIVE_DIAGONAL;
+  c->chol_timed_out = flags[2] != 0;
+  if (flags[2]) return set_err(OVGPU_ERR_HIP, "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup (options.no_single_launch_cholesky = 1 selects the step-wise kernels)");
+  if (stats) stats->status = status;
+  if (status != OVGPU_OK) return set_err(status, status == OVGPU_ERR_NOT_SPD ? "innovation covariance not SPD in the chain" : "negative covariance diagonal in the chain");
+  return OVGPU_OK;
+}
 
 // ---------------------------------------------------------------------------
 // Window bookkeeping on the resident covariance (SURVEY.md 8f N3): StateHelper::marginalize, clone / augment_clone,

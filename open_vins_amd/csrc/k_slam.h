@@ -268,6 +268,41 @@ __global__ void k_anchor_change(AnchorParams p) {
   p.lm.anchor[l] = (p.new_cam << 10) | p.new_clone;
 }
 
+// ovgpu_slam_init_systems: feature f's system as StateHelper::initialize takes it (StateHelper.cpp:393-481), copied out of the
+// separated form the chain has just built, before k_init_invertible / the EKF run: the three rows Q1^T [H_x | res] with H_f = R1
+// (init_out) on top of the 2m - 3 projected rows Q2^T [H_x | res] with H_f = 0 (the feature's rows of the stack).  A single-depth
+// feature keeps the third row only (its H_f = R1(2, 2)): 1 + 2m - 3 = 2m - 2 rows, the bearing projected out (UpdaterSLAM.cpp:181-196).
+// H_x is compacted to the feature's Hx_order (cols: the context's column of each of its h columns); the per-feature noise scaling of the
+// stack (sigma / sigma_f, k_system.h) is undone, so that R = sigma_f^2 I.  One thread per element of H_x, rows x h, row-major: the stores
+// are consecutive, the loads one row of the source per h threads.
+struct InitExportParams {
+  int LD, D, h, rows, single, f;
+  const double *init_out;    // [3 * LD + 9]
+  const double *stack;       // the feature's first row of the stack, stride LD (rows - 3 + 2 single of them)
+  const int32_t *cols;       // [h]
+  const double *feat_sigma;  // [F] or nullptr
+  double sigma;              // the context's sigma_pix
+  double *Hx, *Hf, *res;     // [rows * h], [rows * (single ? 1 : 3)], [rows]
+};
+
+__global__ void __launch_bounds__(256) k_init_export(InitExportParams p) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int top = p.single ? 1 : 3; // rows taken from init_out
+  const double scale = p.feat_sigma ? p.feat_sigma[p.f] / p.sigma : 1.0;
+  auto src_row = [&](int r) -> const double * { return r < top ? p.init_out + (size_t)(r + 3 - top) * p.LD : p.stack + (size_t)(r - top) * p.LD; };
+  if (t < p.rows * p.h) {
+    const int r = t / p.h, j = t - r * p.h;
+    p.Hx[t] = scale * src_row(r)[p.cols[j]];
+  }
+  if (t < p.rows) p.res[t] = scale * src_row(t)[p.D];
+  const int cf = p.single ? 1 : 3;
+  if (t < p.rows * cf) {
+    const int r = t / cf, j = t - r * cf;
+    const double *R1 = p.init_out + (size_t)3 * p.LD; // upper triangular, row-major
+    p.Hf[t] = r < top ? scale * R1[3 * (r + 3 - top) + j + 3 - cf] : 0.0;
+  }
+}
+
 struct InitParams {
   int N, D, LD;             // N = leading dimension of P (the padded capacity)
   int rep, f;

@@ -705,7 +705,7 @@ template <bool RG> __global__ void __launch_bounds__(SYS_NT) k_system_t(SysParam
       }
     }
     __syncthreads();
-    if (hq[57] != 0.0) {
+    if (hq[57] != 0.0 && !(p.init && p.init_keep)) {
       for (int64_t e = tid; e < (int64_t)n_out * LD; e += SYS_NT) p.Hbig[orow0 * LD + e] = 0.0;
       continue;
     }

@@ -106,6 +106,7 @@ struct SysParams {
   int init;
   double *init_out;
   int32_t *init_flag; // [0] = 1 when the feature passed the gate
+  int init_keep;      // init mode: a feature the gate rejects still leaves its rows (init_out and the stack) for an export (ovgpu_slam_init_systems)
   int32_t *rows_used; // optional counters: [0] rows of the stack that belong to accepted features, [1] features the gate's residual bound passed
   const double *Lw;   // [D x D] row-major, lower triangular with explicit zeros above the diagonal: L = U1^T, P_DD = L L^T (k_ekf.h).
                       // Non-null: the rows leave the kernel whitened by the prior, Q^T [H_x L | res] (the Gram route)

@@ -8,8 +8,14 @@
 // StateHelper::initialize chain on the CPU.  Every feature is initialised in the representation the reference gives it —
 // StateOptions::feat_rep_aruco for an ArUco corner, feat_rep_slam otherwise (:160-166; ovgpu_set_feature_reps, ABI 7) — with the
 // ArUco corners' sigma and chi2 multiplier from _options_aruco, next to resident landmarks of any representation.
+//
+// -DOVGPU_SHIM_DELAYED_INIT_A selects the mode-A body instead (ovgpu_delayed_init_a.h): no friend line, the stock StateHelper::initialize
+// applies the systems the library exports (ovgpu_slam_init_systems).
 #include "UpdaterSLAM.h"
 
+#ifdef OVGPU_SHIM_DELAYED_INIT_A
+#include "ovgpu_delayed_init_a.h"
+#else
 #include "ovgpu_shim_common.h"
 #include "ovgpu_state_access.h"
 
@@ -152,3 +158,4 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
     ++it;
   }
 }
+#endif // OVGPU_SHIM_DELAYED_INIT_A

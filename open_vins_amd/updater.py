@@ -255,6 +255,36 @@ class UpdaterMSCKF:
         self.N = n
         return out
 
+    def init_systems(self, feat_rep=0, first_feature=0, feat_rep_each=None):
+        """Mode A of the delayed initialisation (ovgpu_slam_init_systems): the chain of delayed_init run on copies, the resident state
+        left as it was.  Returns one dict per feature: status (the device's gate, -1 before first_feature), feat_rep, Hx_order
+        [(cov_id, size)], H_x, H_f, res (numpy; None without a system), chi2, chi2_thresh, anchor_cam, anchor_clone, p_seed."""
+        F = self.F
+        if feat_rep_each is not None:
+            reps = np.ascontiguousarray(feat_rep_each, dtype=np.int32)
+            capi.check(self.lib.ovgpu_set_feature_reps(self._ctx, _ip(reps)), "ovgpu_set_feature_reps")
+        sz = capi.InitSizes()
+        capi.check(self.lib.ovgpu_slam_init_systems_len(self._ctx, int(feat_rep), int(first_feature), C.byref(sz)), "ovgpu_slam_init_systems_len")
+        sys_ = (capi.InitSystem * max(F, 1))()
+        vid, vsz = np.zeros(max(sz.n_vars, 1), np.int32), np.zeros(max(sz.n_vars, 1), np.int32)
+        Hx, Hf, res = np.zeros(max(sz.n_hx, 1)), np.zeros(max(sz.n_hf, 1)), np.zeros(max(sz.n_res, 1))
+        stats = capi.UpdateStats()
+        capi.check(self.lib.ovgpu_slam_init_systems(self._ctx, int(feat_rep), int(first_feature), C.byref(sz), sys_, _ip(vid), _ip(vsz), _dp(Hx),
+                                                    _dp(Hf), _dp(res), C.byref(stats)), "ovgpu_slam_init_systems")
+        out = []
+        for f in range(F):
+            s = sys_[f]
+            d = dict(status=s.status, feat_rep=s.feat_rep, chi2=s.chi2, chi2_thresh=s.chi2_thresh, anchor_cam=s.anchor_cam, anchor_clone=s.anchor_clone,
+                     p_seed=np.array(s.p_seed[:]), Hx_order=None, H_x=None, H_f=None, res=None)
+            if s.rows > 0:
+                d["Hx_order"] = [(int(vid[s.var_off + i]), int(vsz[s.var_off + i])) for i in range(s.n_vars)]
+                d["H_x"] = Hx[s.hx_off: s.hx_off + s.rows * s.h].reshape(s.rows, s.h).copy()
+                d["H_f"] = Hf[s.hf_off: s.hf_off + s.rows * s.cols_f].reshape(s.rows, s.cols_f).copy()
+                d["res"] = res[s.res_off: s.res_off + s.rows].copy()
+            out.append(d)
+        self.init_stats = stats.as_dict()
+        return out
+
     def get_landmarks(self):
         L = C.c_int32(0)
         capi.check(self.lib.ovgpu_get_landmarks(self._ctx, C.byref(L), None, None, None, None, None), "ovgpu_get_landmarks")

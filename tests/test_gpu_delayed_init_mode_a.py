@@ -1,0 +1,389 @@
+"""GPU tests (`-m gpu`) of mode A of UpdaterSLAM::delayed_init (ovgpu_slam_init_systems).
+
+The library runs the delayed initialisation's chain on copies of the resident state and exports every feature's system in the form
+StateHelper::initialize takes; the host replays those systems through its own initialize (here: a numpy restatement of
+StateHelper.cpp:393-577 with the oracle's EKF update and box-plus) and calls again from the feature after one whose gate it decided
+differently.  The replayed filter is held to the reference's own UpdaterSLAM::delayed_init (oracle/_ref) and to mode B
+(ovgpu_slam_delayed_init) on the same inputs.
+"""
+import types
+
+import numpy as np
+import pytest
+
+from open_vins_amd import capi, synth
+from oracle import pyoracle, pyref
+from parity_util import GATE_MARGIN
+
+pytestmark = pytest.mark.gpu
+
+SINGLE = capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE
+
+
+@pytest.fixture(scope="module")
+def Updater():
+    import torch
+    assert torch.cuda.is_available(), "these tests need a GPU"
+    from open_vins_amd.updater import UpdaterMSCKF
+    return UpdaterMSCKF
+
+
+def _rel(a, b):
+    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
+
+
+def _from_xyz(rep, p):
+    """Landmark::set_from_xyz (Landmark.cpp:66-141) in representation coordinates (the single depth keeps its bearing as the first two)."""
+    p = np.asarray(p, dtype=np.float64)
+    if rep in (capi.REP_GLOBAL_FULL_INVERSE_DEPTH, capi.REP_ANCHORED_FULL_INVERSE_DEPTH):
+        rho = 1.0 / np.linalg.norm(p)
+        return np.array([np.arctan2(p[1], p[0]), np.arccos(rho * p[2]), rho])
+    if rep in (capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, SINGLE):
+        return np.array([p[0] / p[2], p[1] / p[2], 1.0 / p[2]])
+    return p.copy()
+
+
+def _problem(C, K, fisheye, F, seed, L=3, lm_rep=0):
+    """State with L resident landmarks + F fresh tracks (20 % outliers) on the same clones; and the tracks on the state without them."""
+    kw = dict(C=C, K=K, fisheye=fisheye, min_obs=3)
+    prob = synth.make_slam_problem(2, L=L, lm_rep=lm_rep, seed=seed, **kw)
+    tracks = synth.make_problem(2, F=F, seed=seed, outlier_frac=0.2, shard=1, **kw)  # (a feature stream of its own)
+    for k in ("meas_offsets", "uv", "uvn", "clone_idx", "cam_idx"):
+        setattr(prob, k, getattr(tracks, k))
+    return prob, tracks
+
+
+def _ref_tri(opts, tracks):
+    """The reference's own triangulation, as ovgpu_set_triangulation takes it (anchor as a measurement index)."""
+    prob = tracks
+    t = pyref.triangulate(opts, capi.Views(tracks))
+    F = len(prob.meas_offsets) - 1
+    am = np.full(F, -1, np.int32)
+    for f in range(F):
+        for i in range(prob.meas_offsets[f], prob.meas_offsets[f + 1]):
+            if prob.cam_idx[i] == t["anchor_cam"][f] and prob.clone_idx[i] == t["anchor_clone"][f]:
+                am[f] = i
+                break
+    ok = t["status"] == capi.FEAT_USED
+    assert (am[ok] >= 0).all()
+    return dict(p_FinG=t["p_FinG"], p_FinA=t["p_FinA"], anchor_meas=am, status=t["status"].astype(np.int32))
+
+
+class HostFilter:
+    """The host's side of mode A: the state the stock StateHelper::initialize works on, restated in numpy."""
+
+    def __init__(self, opts, prob):
+        self.opts = opts
+        self.cur = types.SimpleNamespace(**{k: getattr(prob, k) for k in vars(prob)})
+        self.cur.P = np.array(prob.P, dtype=np.float64)
+        self.cur.clone_q_p, self.cur.calib_q_p, self.cur.intrinsics = (np.array(getattr(prob, k), dtype=np.float64)
+                                                                       for k in ("clone_q_p", "calib_q_p", "intrinsics"))
+        L = len(prob.lm_cov_id)
+        reps = prob.lm_rep_each if getattr(prob, "lm_rep_each", None) is not None else np.full(L, prob.lm_rep, np.int32)
+        ac = getattr(prob, "lm_anchor_cam", None)
+        acl = getattr(prob, "lm_anchor_clone", None)
+        self.lm = [dict(value=np.array(prob.lm_value[l], dtype=np.float64), fej=np.array(prob.lm_fej[l], dtype=np.float64), cov=int(prob.lm_cov_id[l]),
+                        rep=int(reps[l]), anchor_cam=int(ac[l]) if ac is not None else -1, anchor_clone=int(acl[l]) if acl is not None else -1)
+                   for l in range(L)]
+        self.L0 = L
+
+    @property
+    def N(self):
+        return self.cur.P.shape[0]
+
+    def initialize(self, s, sigma2, mult):
+        """StateHelper::initialize (StateHelper.cpp:393-481) + initialize_invertible (:484-577) on system s; True if accepted."""
+        nl = s["H_f"].shape[1]
+        idx = np.concatenate([np.arange(c, c + n) for c, n in s["Hx_order"]])
+        Q, _ = np.linalg.qr(s["H_f"], mode="complete")
+        HR, HL, r = Q.T @ s["H_x"], Q.T @ s["H_f"], Q.T @ s["res"]
+        Hxi, Hfi, ri, Hup, rup = HR[:nl], HL[:nl, :nl], r[:nl], HR[nl:], r[nl:]
+        P = self.cur.P
+        Pu = P[np.ix_(idx, idx)]
+        S = Hup @ Pu @ Hup.T + sigma2 * np.eye(len(rup))
+        chi2 = float(rup @ np.linalg.solve(S, rup))
+        thr = mult * pyoracle.chi2_quantile_95(len(s["res"]))
+        if chi2 > thr:
+            return False, chi2, thr
+        N = self.N
+        Hinv = np.linalg.inv(Hfi)
+        M_a = P[:, idx] @ Hxi.T
+        Pn = np.zeros((N + nl, N + nl))
+        Pn[:N, :N] = P
+        Pn[:N, N:] = -M_a @ Hinv.T
+        Pn[N:, :N] = Pn[:N, N:].T
+        Pn[N:, N:] = Hinv @ (Hxi @ Pu @ Hxi.T + sigma2 * np.eye(nl)) @ Hinv.T
+        rep = s["feat_rep"]
+        v0 = _from_xyz(rep, s["p_seed"])
+        v = v0.copy()
+        v[3 - nl:] += Hinv @ ri
+        self.cur.P = Pn
+        self.lm.append(dict(value=v, fej=v0, cov=N, rep=rep, anchor_cam=s["anchor_cam"] if rep >= capi.REP_ANCHORED_3D else -1,
+                            anchor_clone=s["anchor_clone"] if rep >= capi.REP_ANCHORED_3D else -1))
+        if len(rup):
+            self.ekf(Hup, rup, idx, sigma2)
+        return True, chi2, thr
+
+    def ekf(self, H, res, idx, sigma2):
+        """StateHelper::EKFUpdate with the oracle's update, box-plus of the clones / calibration, Landmark::update."""
+        st, P, dx = pyoracle.ekf_update(self.cur.P, H, res, idx.astype(np.int32), sigma2)
+        assert st == 0
+        self.cur.P, self.cur.N = P, P.shape[0]
+        post = pyoracle.apply_dx(self.opts, capi.Views(self.cur), dx)
+        for k, a in post.items():
+            setattr(self.cur, k, a)
+        for lm in self.lm:
+            sz = 1 if lm["rep"] == SINGLE else 3
+            lm["value"][3 - sz:] += dx[lm["cov"]: lm["cov"] + sz]
+
+    def upload(self, up, tracks, tri, reps, sig, mult):
+        """The host's state back to the device: ovgpu_set_state / _landmarks / _features, the options, the entry triangulation."""
+        p = types.SimpleNamespace(**vars(self.cur))
+        p.N = self.N
+        for k in ("meas_offsets", "uv", "uvn", "clone_idx", "cam_idx"):
+            setattr(p, k, getattr(tracks, k))
+        p.lm_value = np.array([l["value"] for l in self.lm])
+        p.lm_fej = np.array([l["fej"] for l in self.lm])
+        p.lm_cov_id = np.array([l["cov"] for l in self.lm], np.int32)
+        p.lm_rep_each = np.array([l["rep"] for l in self.lm], np.int32)
+        p.lm_rep = int(p.lm_rep_each[0])
+        p.lm_anchor_cam = np.array([l["anchor_cam"] for l in self.lm], np.int32)
+        p.lm_anchor_clone = np.array([l["anchor_clone"] for l in self.lm], np.int32)
+        p.lm_index = np.zeros(len(tracks.meas_offsets) - 1, np.int32)
+        up.set_slam_problem(p)
+        _options(up, tri, reps, sig, mult)
+
+
+def _options(up, tri, reps, sig, mult):
+    up.set_triangulation(tri["p_FinG"], tri["p_FinA"], tri["anchor_meas"], tri["status"])
+    up.set_feature_options(sig, mult)
+    capi.check(up.lib.ovgpu_set_feature_reps(up._ctx, reps.ctypes.data_as(capi.c_int32_p)), "ovgpu_set_feature_reps")
+
+
+def _replay(up, opts, prob, tri, rep_slam, reps, sig, mult):
+    """Mode A's host loop: one device call, the systems in order through the host's initialize, a restart after a differing gate."""
+    host = HostFilter(opts, prob)
+    F = len(reps)
+    status = np.full(F, -1, np.int32)
+    sys_ = up.init_systems(rep_slam)
+    calls = 1
+    for f in range(F):
+        s = sys_[f]
+        if s["H_x"] is None:
+            status[f] = s["status"]
+            continue
+        ok, chi2, thr = host.initialize(s, sig[f] ** 2, mult[f])
+        status[f] = capi.FEAT_USED if ok else capi.FEAT_CHI2_REJECTED
+        if ok != (s["status"] == capi.FEAT_USED):
+            assert abs(chi2 / thr - 1.0) < GATE_MARGIN, (f, chi2, thr, s["chi2"], s["chi2_thresh"])
+            host.upload(up, prob, tri, reps, sig, mult)
+            sys_ = up.init_systems(rep_slam, first_feature=f + 1)
+            calls += 1
+    return host, status, calls
+
+
+CASES = [  # (clones, cameras, fisheye, features, seed)
+    (6, 3, False, 16, 21),
+    (12, 2, True, 16, 22),
+    (30, 4, False, 24, 23),
+    (40, 2, False, 20, 24),
+]
+
+
+@pytest.mark.parametrize("rep_slam", range(6))
+@pytest.mark.parametrize("case", CASES, ids=lambda c: f"C{c[0]}K{c[1]}{'fe' if c[2] else ''}F{c[3]}")
+def test_replay_equals_the_reference_and_mode_b(Updater, rep_slam, case):
+    C, K, fisheye, F, seed = case
+    rep_aruco = (rep_slam + 3) % 6
+    prob, tracks = _problem(C, K, fisheye, F, seed, lm_rep=[0, 2, 5][seed % 3])
+    opts = capi.default_options(chi2_multipler=1.0)
+    rng = np.random.default_rng(seed)
+    tag = rng.random(F) < 0.3
+    reps = np.where(tag, rep_aruco, rep_slam).astype(np.int32)
+    sig, mult = np.where(tag, 2.5, 1.0), np.where(tag, 3.0, 1.0)
+    tri = _ref_tri(opts, tracks)
+    ref = pyref.slam_delayed_init(opts, capi.Views(prob), feat_rep=rep_slam, feat_sigma=sig, feat_chi2mult=mult, feat_rep_aruco=rep_aruco,
+                                  feat_is_aruco=tag.astype(np.int32))
+    up = Updater(opts)
+    up.set_slam_problem(prob)
+    _options(up, tri, reps, sig, mult)
+    host, status, calls = _replay(up, opts, prob, tri, rep_slam, reps, sig, mult)
+    # against the reference: the accepted set (a gate within GATE_MARGIN of its threshold may go either way), N, ids, P, landmarks
+    acc_ref = ref["lm_cov_id"] >= 0
+    acc = status == capi.FEAT_USED
+    assert 0 < acc.sum() and np.array_equal(acc, acc_ref), (status, ref["feat_status"])
+    new = host.lm[host.L0:]
+    assert host.N == ref["N"] and [l["cov"] for l in new] == list(ref["lm_cov_id"][acc_ref])
+    assert _rel(host.cur.P, ref["P"]) <= 1e-11
+    got = np.array([l["value"] for l in new])
+    want = ref["lm_value"][acc_ref]
+    assert np.abs(got - want).max() <= 1e-11 * max(np.abs(want).max(), 1.0)
+    old = np.array([l["value"] for l in host.lm[:host.L0]])
+    assert np.abs(old - ref["landmarks_existing"]).max() <= 1e-11 * max(np.abs(ref["landmarks_existing"]).max(), 1.0)
+    # against mode B on the same inputs
+    upb = Updater(opts)
+    upb.set_slam_problem(prob)
+    _options(upb, tri, reps, sig, mult)
+    outb = upb.delayed_init(rep_slam, feat_rep_each=reps)
+    assert np.array_equal(outb["lm_cov_id"] >= 0, acc) and outb["N"] == host.N
+    assert np.array_equal(outb["lm_cov_id"][acc], [l["cov"] for l in new])
+    assert _rel(host.cur.P, outb["P"]) <= 1e-11
+    assert np.abs(outb["lm_value"][acc] - got).max() <= 1e-11 * max(np.abs(got).max(), 1.0)
+    print(f"rep {rep_slam}/{rep_aruco}: {acc.sum()} of {F} accepted, {calls} device call(s), |dP|/|P| vs reference {_rel(host.cur.P, ref['P']):.1e}")
+    up.close()
+    upb.close()
+
+
+def _invariants(A, r):
+    return A.T @ A, A.T @ r, r @ r
+
+
+def _expand(s, N):
+    """[H_x | H_f] with H_x in covariance-id columns."""
+    A = np.zeros((s["H_x"].shape[0], N + s["H_f"].shape[1]))
+    j = 0
+    for c, n in s["Hx_order"]:
+        A[:, c:c + n] = s["H_x"][:, j:j + n]
+        j += n
+    A[:, N:] = s["H_f"]
+    return A
+
+
+@pytest.mark.parametrize("rep", range(6))
+def test_first_system_matches_the_reference_jacobian(Updater, rep):
+    """Feature 0 is linearised at the entry state: its system against UpdaterHelper::get_feature_jacobian_full at the entry
+    triangulation (the single depth with its bearing projected out, UpdaterSLAM.cpp:181-196), through row-invariant quantities."""
+    prob, tracks = _problem(12, 2, False, 6, 31)
+    opts = capi.default_options(chi2_multipler=1.0)
+    tri = _ref_tri(opts, tracks)
+    up = Updater(opts)
+    up.set_slam_problem(prob)
+    up.set_triangulation(tri["p_FinG"], tri["p_FinA"], tri["anchor_meas"], tri["status"])
+    sys_ = up.init_systems(rep)
+    f = next(i for i in range(6) if sys_[i]["H_x"] is not None)
+    s = sys_[f]
+    v = capi.Views(tracks)  # (the driver's state has no landmarks; the Jacobian touches none)
+    am = tri["anchor_meas"][f]
+    jrep = capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH if rep == SINGLE else rep
+    H_f, H_x, res = pyref.feature_jacobian(opts, v, f, jrep, tri["p_FinG"][f], tri["p_FinA"][f], prob.cam_idx[am], prob.clone_idx[am])
+    if rep == SINGLE:
+        _, Hxf, res = pyoracle.nullspace_project(H_f[:, :2], np.hstack([H_x, H_f[:, 2:]]), res)
+        H_x, H_f = Hxf[:, :-1], Hxf[:, -1:]
+    N = tracks.N
+    A = np.hstack([H_x, H_f])
+    got, want = _invariants(_expand(s, N), s["res"]), _invariants(A, res)
+    for g, w in zip(got, want):
+        assert _rel(np.asarray(g), np.asarray(w)) <= 1e-12
+    assert np.allclose(s["p_seed"], tri["p_FinA"][f] if rep >= capi.REP_ANCHORED_3D else tri["p_FinG"][f], rtol=0, atol=0)
+    up.close()
+
+
+def test_restart_reproduces_the_tail(Updater):
+    """Replay the first k systems on the host, upload that state, call with first_feature = k + 1: the systems equal the full call's tail."""
+    prob, tracks = _problem(30, 2, False, 16, 41)
+    opts = capi.default_options(chi2_multipler=1.0)
+    F = 16
+    reps = np.full(F, capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, np.int32)
+    sig, mult = np.ones(F), np.ones(F)
+    tri = _ref_tri(opts, tracks)
+    up = Updater(opts)
+    up.set_slam_problem(prob)
+    _options(up, tri, reps, sig, mult)
+    full = up.init_systems(reps[0])
+    host = HostFilter(opts, prob)
+    k = 6
+    for f in range(k + 1):
+        if full[f]["H_x"] is not None:
+            ok, _, _ = host.initialize(full[f], 1.0, 1.0)
+            assert ok == (full[f]["status"] == capi.FEAT_USED)
+    host.upload(up, prob, tri, reps, sig, mult)
+    tail = up.init_systems(reps[0], first_feature=k + 1)
+    assert all(tail[f]["status"] == -1 and tail[f]["H_x"] is None for f in range(k + 1))
+    n = 0
+    for f in range(k + 1, F):
+        a, b = tail[f], full[f]
+        assert a["status"] == b["status"] and (a["H_x"] is None) == (b["H_x"] is None)
+        if a["H_x"] is None:
+            continue
+        assert a["Hx_order"] == b["Hx_order"]
+        for g, w in zip(_invariants(_expand(a, host.N), a["res"]), _invariants(_expand(b, host.N), b["res"])):
+            assert _rel(np.asarray(g), np.asarray(w)) <= 1e-11
+        n += 1
+    assert n >= 4
+    up.close()
+
+
+def test_no_side_effects(Updater):
+    """The resident state reads back bit for bit, and a following MSCKF update equals one on a context that never made the call."""
+    prob = synth.make_problem(2, F=24, seed=51, C=30, K=2, outlier_frac=0.2)
+    opts = capi.default_options(chi2_multipler=1.0)
+    a, b = Updater(opts), Updater(opts)
+    a.set_problem(prob)
+    b.set_problem(prob)
+    before = a.get_state(P=True)
+    sys_ = a.init_systems(capi.REP_ANCHORED_3D)
+    assert sum(s["status"] == capi.FEAT_USED for s in sys_) >= 4
+    after = a.get_state(P=True)
+    for k in before:
+        assert np.array_equal(before[k], after[k]), k
+    assert a.get_landmarks()["value"].shape[0] == 0
+    ua, ub = a.update(), b.update()
+    for k in ("feat_status", "dx", "P"):
+        assert np.array_equal(ua[k], ub[k]), k
+    a.close()
+    b.close()
+
+
+def test_no_side_effects_on_landmarks(Updater):
+    prob, _ = _problem(12, 2, False, 10, 52, L=4, lm_rep=2)
+    opts = capi.default_options(chi2_multipler=1.0)
+    up = Updater(opts)
+    up.set_slam_problem(prob)
+    lm0, st0 = up.get_landmarks(), up.get_state(P=True)
+    sys_ = up.init_systems(0)
+    assert sum(s["status"] == capi.FEAT_USED for s in sys_) >= 2
+    lm1, st1 = up.get_landmarks(), up.get_state(P=True)
+    for k in lm0:
+        assert np.array_equal(lm0[k], lm1[k]), k
+    for k in st0:
+        assert np.array_equal(st0[k], st1[k]), k
+    up.close()
+
+
+def test_edge_cases(Updater):
+    """No features; tracks with fewer than two measurements (no system); a batch the gate rejects completely."""
+    opts = capi.default_options(chi2_multipler=1.0)
+    prob = synth.make_problem(2, F=8, seed=61, C=12, K=2, outlier_frac=0.2)
+    up = Updater(opts)
+    empty = types.SimpleNamespace(**vars(prob))
+    empty.meas_offsets = np.zeros(1, np.int32)
+    for k in ("uv", "uvn"):
+        setattr(empty, k, np.zeros(0, np.float32))
+    empty.clone_idx = empty.cam_idx = np.zeros(0, np.int32)
+    up.set_problem(empty)
+    assert up.init_systems(0) == []
+    # one-measurement tracks
+    short = types.SimpleNamespace(**vars(prob))
+    keep = np.concatenate([np.arange(prob.meas_offsets[f], prob.meas_offsets[f] + (1 if f % 2 else prob.meas_offsets[f + 1] - prob.meas_offsets[f]))
+                           for f in range(8)])
+    cnt = [1 if f % 2 else prob.meas_offsets[f + 1] - prob.meas_offsets[f] for f in range(8)]
+    short.meas_offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+    short.uv = np.asarray(prob.uv).reshape(-1, 2)[keep].reshape(-1)
+    short.uvn = np.asarray(prob.uvn).reshape(-1, 2)[keep].reshape(-1)
+    short.clone_idx, short.cam_idx = prob.clone_idx[keep], prob.cam_idx[keep]
+    up.set_problem(short)
+    sys_ = up.init_systems(0)
+    for f in range(1, 8, 2):
+        assert sys_[f]["status"] == capi.FEAT_TOO_FEW_MEAS and sys_[f]["H_x"] is None
+    assert any(sys_[f]["H_x"] is not None for f in range(0, 8, 2))
+    # every feature rejected: a tiny multiplier; the systems are still exported, the state is untouched
+    tight = capi.default_options(chi2_multipler=1e-9)
+    ut = Updater(tight)
+    ut.set_problem(prob)
+    before = ut.get_state(P=True)
+    sys_ = ut.init_systems(0)
+    assert all(s["status"] != capi.FEAT_USED for s in sys_)
+    assert sum(s["status"] == capi.FEAT_CHI2_REJECTED and s["H_x"] is not None for s in sys_) >= 4
+    assert np.array_equal(ut.get_state(P=True)["P"], before["P"])
+    up.close()
+    ut.close()
