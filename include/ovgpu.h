@@ -69,8 +69,14 @@ extern "C" {
 /*      the Gram matrix as a compressed system: a documented negative result)   */
 /*      is gone: ovgpu_create returns OVGPU_ERR_INVALID for it.  Nothing else   */
 /*      changed shape.  New: ovgpu_comm_info.                                   */
+/*   9  ovgpu_set_active_landmarks: the Jacobian columns of the SLAM calls cover */
+/*      the landmarks the caller names instead of every resident one.           */
+/*      ovgpu_set_landmarks no longer returns OVGPU_ERR_CAPACITY when all        */
+/*      landmarks together exceed 511 columns: the SLAM call whose EFFECTIVE     */
+/*      column set exceeds them does.  A caller that never names a set and stays */
+/*      under that bound sees what ABI 8 computed.  Nothing changed shape.       */
 /* ------------------------------------------------------------------------- */
-#define OVGPU_ABI_VERSION 8
+#define OVGPU_ABI_VERSION 9
 int ovgpu_abi_version(void);
 
 /* ------------------------------------------------------------------------- */
@@ -446,8 +452,42 @@ typedef struct {
 } ovgpu_landmarks_view;
 
 /* Uploads the landmarks the next ovgpu_slam_update works on; their 3 columns each join the
- * canonical column order (sorted by covariance id).  Call after ovgpu_set_state.             */
+ * canonical column order (sorted by covariance id).  Call after ovgpu_set_state.
+ * L is bounded by 4096 and by the memory of the N x N covariance that holds the landmarks;
+ * the number of Jacobian COLUMNS is bounded per SLAM call, not here: a call over more than 511
+ * (calibration + 6 per clone + the dof of every landmark that has columns) returns
+ * OVGPU_ERR_CAPACITY.  With 30 clones, stereo and online calibration that is 101 landmarks
+ * with columns at a time: name the ones a call needs with ovgpu_set_active_landmarks.        */
 int ovgpu_set_landmarks(ovgpu_ctx *ctx, const ovgpu_landmarks_view *lm);
+
+/* The active landmark set: the resident landmarks that get Jacobian columns in the SLAM calls
+ * that follow.  UpdaterSLAM::update builds Hx_order from the variables its batch's features
+ * touch (UpdaterSLAM.cpp:300-340), and delayed_init gives resident landmarks no column at all
+ * (UpdaterSLAM.cpp:147-239, StateHelper.cpp:393-482): every other landmark is corrected
+ * through the covariance alone.  The same here — the column order narrows to the calibrated
+ * camera variables, the clones and the n landmarks lm_index names (by covariance id, as
+ * before); a landmark outside the set has no column and still receives its share of dx.  In
+ * exact arithmetic the results equal those over all landmarks (columns that are zero for the
+ * whole stack change nothing); in floating point they differ at rounding level.
+ *   n == 0  the empty set: what ovgpu_slam_delayed_init, ovgpu_slam_init_systems(_len) and
+ *           ovgpu_slam_change_anchor(s) need;  n < 0  every resident landmark again.
+ *   lm_index [n]  indices into the landmark view; one named twice is in the set once.
+ * Holds until the next ovgpu_set_landmarks, ovgpu_set_state or call with n < 0.  Landmarks
+ * appended by ovgpu_slam_delayed_init are outside it; ovgpu_state_marginalize of a landmark
+ * removes it and the set follows the indices of the others.
+ * ORDER: ovgpu_set_state, ovgpu_set_landmarks, ovgpu_set_active_landmarks,
+ * ovgpu_set_features, the SLAM call.  The batch's layout depends on the column count, so a
+ * batch uploaded before this call is no longer resident: the SLAM call returns
+ * OVGPU_ERR_NO_STATE until ovgpu_set_features is called again (n < 0 without a set in force
+ * changes nothing and keeps the batch).  ovgpu_slam_update / _compress return
+ * OVGPU_ERR_INVALID for a batch that observes a landmark outside the set, and
+ * ovgpu_slam_update / _compress / _delayed_init / _init_systems(_len) return
+ * OVGPU_ERR_CAPACITY when the set in force (all landmarks when none was named) has more than
+ * 511 columns; until one that fits is named no landmark has a column.
+ * ovgpu_slam_change_anchor(s) read no column table and run under any set.
+ * The tables are built on the device in one launch on the context's stream; the call does
+ * not wait for it.                                                                          */
+int ovgpu_set_active_landmarks(ovgpu_ctx *ctx, int32_t n, const int32_t *lm_index);
 
 /* UpdaterSLAM::update on the resident state, landmarks and feature tracks: feature f observes
  * landmark lm_index[f].  Per feature the Jacobian of UpdaterHelper::get_feature_jacobian_full

@@ -138,6 +138,15 @@ struct ovgpu_ctx {
   std::vector<int32_t> h_lm_cov, h_lm_col, h_lm_anchor; // h_lm_anchor: packed (camera << 10 | clone) or -1, mirror of lm_anchor
   DevBuf<double> pFej, lm_val, lm_fej; // landmark values in representation coordinates (ov_type::Landmark::value / fej)
   DevBuf<int32_t> feat_lm, feat_lmcol, feat_lmcov, feat_anchor, lm_cov, lm_col, lm_anchor, lm_repd, lm_index;
+  // ovgpu_set_active_landmarks: the landmarks that get Jacobian columns in the calls that follow (UpdaterSLAM.cpp:300-340 builds Hx_order from
+  // what the batch touches); without one every resident landmark has a column block
+  bool active_given = false;
+  std::vector<uint8_t> h_lm_active;  // [L] 1: named by the active set
+  std::vector<HVar> h_sorted;        // h_vars and the resident landmarks by covariance id (build_columns); layout_columns walks it, no sort per call
+  DevBuf<int32_t> var_tab, active_idx; // device copy of h_sorted (4 ints per variable) and the uploaded lm_index of the set: k_active_columns' inputs
+  bool var_tab_ok = false;           // var_tab holds h_sorted
+  bool cols_over = false;            // the column set asked for has more than 511 columns: no landmark has a column and the SLAM entry points refuse
+  std::string cols_over_msg;
   bool slam_rows = false; // row layout of the uploaded batch: 2m rows per feature (SLAM update) or 2m - 3 (MSCKF, delayed init)
   // device-resident FeatureDatabase (ovgpu_tracks_*)
   int trk_max = 0, trk_obs = 0;

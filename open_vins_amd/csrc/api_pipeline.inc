@@ -637,6 +637,7 @@ static int enqueue_speculative_prior(ovgpu_ctx *c) {
   if (!c->speculative_prior || c->prior_pending || !c->have_state || c->poses_only || c->D < 1) return OVGPU_OK;
   if (!(c->stream2 && c->ev_fork && c->ev_join && c->prior_overlap)) return OVGPU_OK;
   if (c->compress_gram != 1 || (c->D + 1 + 15) / 16 > gram::GR_NT_BLK || !c->whiten || !chol_pipe_usable(c, c->D)) return OVGPU_OK;
+  if (c->L != 0 || c->force_tsqr) return OVGPU_OK; // the update will not take the Gram route (need_prior, enqueue_pipeline_body): it would drop the factorisation and wait for it
   const int rc = enqueue_ekf_gram(c, 1, true);
   if (rc != OVGPU_OK) return rc;
   // The update that follows would zero three more views of the control block one by one, each a launch of its own on its critical path (row

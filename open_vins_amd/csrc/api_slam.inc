@@ -38,6 +38,7 @@ int ovgpu_set_landmarks(ovgpu_ctx *c, const ovgpu_landmarks_view *lm) {
   }
   HIPCHK(hipSetDevice(c->device));
   c->L = lm->L;
+  c->active_given = false, c->h_lm_active.clear(); // new landmarks: every one has a column block until a set is named
   c->h_lm_rep.assign(reps.begin(), reps.begin() + lm->L);
   c->row_stride = (relative || c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D) ? 72 : 48;
   c->h_lm_cov.assign(lm->cov_id, lm->cov_id + lm->L);
@@ -52,6 +53,25 @@ int ovgpu_set_landmarks(ovgpu_ctx *c, const ovgpu_landmarks_view *lm) {
     HIPCHK(upload(c->lm_repd.p, reps.data(), sizeof(int32_t) * lm->L, c->stream));
   }
   return build_columns(c); // synchronises; the feature batch has to be uploaded again (row counts and D changed)
+}
+
+// UpdaterSLAM::update's Hx_order holds the variables its batch touches (UpdaterSLAM.cpp:300-340); delayed_init's systems touch no resident
+// landmark (:147-239).  The set narrows the column map to that; the other landmarks are corrected through P, as there.
+int ovgpu_set_active_landmarks(ovgpu_ctx *c, int32_t n, const int32_t *lm_index) {
+  if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
+  if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state (and ovgpu_set_landmarks) must precede ovgpu_set_active_landmarks");
+  if (n > 0 && c->L <= 0) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_landmarks must precede ovgpu_set_active_landmarks");
+  if (n > 0 && !lm_index) return set_err(OVGPU_ERR_INVALID, "null lm_index");
+  for (int i = 0; i < n; i++)
+    if (lm_index[i] < 0 || lm_index[i] >= c->L) return set_err(OVGPU_ERR_INVALID, "active landmark index out of range");
+  if (n < 0 && !c->active_given) return OVGPU_OK; // every landmark has its columns already: nothing changes, the resident batch stays
+  { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; } // the column map changes: a prior-block factorisation started for the old one is stale
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(upload_begin(c));
+  c->active_given = n >= 0;
+  c->h_lm_active.assign(n >= 0 ? c->L : 0, 0);
+  for (int i = 0; i < n; i++) c->h_lm_active[lm_index[i]] = 1; // (a landmark named twice is in the set once)
+  return layout_columns(c); // the feature batch has to be uploaded again (D and the LDS carve of the per-feature kernel changed)
 }
 
 int ovgpu_get_landmarks(ovgpu_ctx *c, int32_t *L_out, double *value, double *fej, int32_t *cov_id, int32_t *anchor_cam, int32_t *anchor_clone) {
@@ -93,8 +113,11 @@ static int slam_prepare(ovgpu_ctx *c, const int32_t *lm_index, ovgpu_update_stat
   if (stats) std::memset(stats, 0, sizeof(*stats));
   const int F = c->F;
   hipStream_t s = c->stream;
-  for (int f = 0; f < F; f++)
+  if (c->cols_over) return set_err(OVGPU_ERR_CAPACITY, c->cols_over_msg);
+  for (int f = 0; f < F; f++) {
     if (lm_index[f] < 0 || lm_index[f] >= c->L) return set_err(OVGPU_ERR_INVALID, "lm_index out of range");
+    if (c->h_lm_col[lm_index[f]] < 0) return set_err(OVGPU_ERR_INVALID, "a feature of the batch observes a landmark outside the active landmark set (ovgpu_set_active_landmarks)");
+  }
   const size_t n = (size_t)std::max(F, 1);
   HIPCHK(c->pFej.reserve(3 * n));
   HIPCHK(c->feat_lm.reserve(n));
@@ -187,6 +210,7 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features was never called (or the state changed since)");
   if (feat_rep < OVGPU_REP_GLOBAL_3D || feat_rep > OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE)
     return set_err(OVGPU_ERR_INVALID, "unknown landmark representation");
+  if (c->cols_over) return set_err(OVGPU_ERR_CAPACITY, c->cols_over_msg);
   HIPCHK(hipSetDevice(c->device));
   if (stats) std::memset(stats, 0, sizeof(*stats));
   // the representation each feature is initialised in: the call's, or ovgpu_set_feature_reps' (UpdaterSLAM.cpp:160-166: feat_rep_aruco for an
@@ -350,6 +374,7 @@ static int init_sys_layout(ovgpu_ctx *c, int32_t feat_rep, int first, InitSysLay
   if (feat_rep < OVGPU_REP_GLOBAL_3D || feat_rep > OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) return set_err(OVGPU_ERR_INVALID, "unknown landmark representation");
   const int F = c->F, M = c->M;
   if (first < 0 || first > F) return set_err(OVGPU_ERR_INVALID, "first_feature out of range");
+  if (c->cols_over) return set_err(OVGPU_ERR_CAPACITY, c->cols_over_msg);
   HIPCHK(hipSetDevice(c->device));
   std::vector<uint16_t> cc(std::max(M, 1));
   if (M > 0) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, c->stream));

@@ -112,7 +112,7 @@ void ovgpu_destroy(ovgpu_ctx *c) {
   c->P.release(), c->P0.release(), c->clone_qp.release(), c->clone_qp0.release(), c->clone_fej.release();
   c->calib_qp.release(), c->calib_qp0.release(), c->intr.release(), c->intr0.release(), c->fisheye.release();
   c->clone_cov.release(), c->calib_cov.release(), c->intr_cov.release(), c->clone_col.release(), c->calib_col.release();
-  c->intr_col.release(), c->col_cov.release(), c->col_kind.release(), c->col_sub.release(), c->col_var.release();
+  c->intr_col.release(), c->var_tab.release(), c->active_idx.release(), c->col_cov.release(), c->col_kind.release(), c->col_sub.release(), c->col_var.release();
   c->tab_clone.release(), c->tab_cam.release(), c->tab_cc.release();
   c->retri_sys[0].release(), c->retri_sys[1].release(), c->retri_pos.release(), c->retri_uvd.release(), c->retri_int.release(), c->retri_f.release(), c->marg_idx.release(), c->marg_out.release(), c->seed_anchor.release(), c->seed_pA.release();
   c->meas_offsets.release(), c->meas_cc.release(), c->uv.release(), c->uvn.release(), c->row_off.release();
@@ -180,23 +180,76 @@ static int launch_build_tables(ovgpu_ctx *c) {
 }
 
 // Canonical column order of the stacked Jacobian: calibrated camera variables, clones and (SLAM) landmarks sorted by
-// covariance id.  Called by ovgpu_set_state and ovgpu_set_landmarks.
+// covariance id.  build_columns sorts the resident variables (ovgpu_set_state, ovgpu_set_landmarks and every structural change of the
+// state); layout_columns lays the columns out over that sorted list for the active landmark set (ovgpu_set_active_landmarks: a linear
+// walk, no sort) or, without one, for every resident landmark.
+static int layout_columns(ovgpu_ctx *c, bool defer_flush = false);
 static int build_columns(ovgpu_ctx *c, bool defer_flush = false) {
   std::vector<ovgpu_ctx::HVar> vars = c->h_vars;
   for (int l = 0; l < c->L; l++) vars.push_back({c->h_lm_cov[l], lm_dof(c->h_lm_rep[l]), COL_LANDMARK, l});
   std::stable_sort(vars.begin(), vars.end(), [](const ovgpu_ctx::HVar &a, const ovgpu_ctx::HVar &b) { return a.cov < b.cov; });
+  for (const auto &v : vars)
+    if (v.cov < 0 || v.cov + v.size > c->N) return set_err(OVGPU_ERR_INVALID, "covariance id out of range");
+  c->h_sorted.swap(vars);
+  c->var_tab_ok = false;
+  if (c->active_given) c->h_lm_active.resize(c->L, 0); // (landmarks the delayed initialisation appended are outside the set)
+  return layout_columns(c, defer_flush);
+}
+
+// (the uploads are flushed HERE whatever the caller's defer_flush says: the kernel reads them; ovgpu_set_state, the one caller that defers, has no set)
+// the device builds the tables of an active set itself, in one launch behind the two small uploads (k_active_columns, k_slam.h); the host's walk
+// in layout_columns is the mirror that sizes the workspaces and nobody waits for the device
+static int enqueue_active_columns(ovgpu_ctx *c, const std::vector<int32_t> &active_idx, int D) {
+  const int V = (int)c->h_sorted.size();
+  if (!c->var_tab_ok) {
+    std::vector<int32_t> tab((size_t)4 * std::max(V, 1), 0);
+    for (int v = 0; v < V; v++) tab[4 * v] = c->h_sorted[v].cov, tab[4 * v + 1] = c->h_sorted[v].size, tab[4 * v + 2] = c->h_sorted[v].kind, tab[4 * v + 3] = c->h_sorted[v].index;
+    HIPCHK(c->var_tab.reserve(tab.size()));
+    HIPCHK(upload_deferred(c, c->var_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
+    c->var_tab_ok = true;
+  }
+  HIPCHK(c->active_idx.reserve(std::max<size_t>(active_idx.size(), 1)));
+  HIPCHK(upload_deferred(c, c->active_idx.p, active_idx.data(), sizeof(int32_t) * active_idx.size()));
+  HIPCHK(upload_fence(c, c->stream));
+  HIPCHK(c->lm_col.reserve(std::max(c->L, 1)));
+  ActiveColsParams ap;
+  ap.V = V, ap.L = c->L, ap.C = c->C, ap.K = c->K, ap.n_active = (int)active_idx.size(), ap.Dcap = D;
+  ap.vars = c->var_tab.p, ap.active_idx = c->active_idx.p;
+  ap.clone_col = c->clone_col.p, ap.calib_col = c->calib_col.p, ap.intr_col = c->intr_col.p, ap.lm_col = c->lm_col.p, ap.col_cov = c->col_cov.p;
+  ap.col_kind = c->col_kind.p, ap.col_sub = c->col_sub.p, ap.col_var = c->col_var.p;
+  hipLaunchKernelGGL(k_active_columns, dim3(1), dim3(64), (size_t)((c->L + 15) & ~15), c->stream, ap);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+static int layout_columns(ovgpu_ctx *c, bool defer_flush) {
+  const std::vector<ovgpu_ctx::HVar> &vars = c->h_sorted;
   const int C = c->C, K = c->K, N = c->N;
-  std::vector<int32_t> clone_col(C, -1), calib_col(K, -1), intr_col(K, -1), col_cov;
+  const bool act = c->active_given;
+  // More than 511 columns: no call can carry them (k_system's and the factorisations' tables).  The map falls back to calibration and clones,
+  // which every other entry point can still use, and the SLAM entry points return OVGPU_ERR_CAPACITY with cols_over_msg until a set that fits is named.
+  int D_want = 0, n_act = 0;
+  for (const auto &v : vars) {
+    const bool on = v.kind != COL_LANDMARK || !act || c->h_lm_active[v.index];
+    D_want += on ? v.size : 0, n_act += (on && v.kind == COL_LANDMARK) ? 1 : 0;
+  }
+  c->cols_over = D_want + 1 > 512;
+  if (c->cols_over)
+    c->cols_over_msg = std::string("the active landmark set (") + (act ? std::to_string(n_act) + " landmarks named by ovgpu_set_active_landmarks" : "all " + std::to_string(c->L) + " resident landmarks: no set was named") +
+                       ") gives " + std::to_string(D_want) + " Jacobian columns, more than 511: name the batch's landmarks with ovgpu_set_active_landmarks";
+  // (with an active set only D, h_col_cov, h_lm_col, active_idx and the raw-stack classes of this walk are used: the tables themselves are k_active_columns',
+  //  k_slam.h, which repeats the walk on the device — change the two together)
+  std::vector<int32_t> clone_col(C, -1), calib_col(K, -1), intr_col(K, -1), col_cov, active_idx;
   std::vector<uint8_t> col_kind, col_sub;
   std::vector<uint16_t> col_var;
   c->h_lm_col.assign(c->L, -1);
   int D = 0;
   for (const auto &v : vars) {
-    if (v.cov < 0 || v.cov + v.size > N) return set_err(OVGPU_ERR_INVALID, "covariance id out of range");
+    if (v.kind == COL_LANDMARK && (c->cols_over || (act && !c->h_lm_active[v.index]))) continue;
     if (v.kind == COL_CLONE) clone_col[v.index] = D;
     if (v.kind == COL_CALIB_POSE) calib_col[v.index] = D;
     if (v.kind == COL_CALIB_INTR) intr_col[v.index] = D;
-    if (v.kind == COL_LANDMARK) c->h_lm_col[v.index] = D;
+    if (v.kind == COL_LANDMARK) c->h_lm_col[v.index] = D, active_idx.push_back(v.index);
     for (int i = 0; i < v.size; i++) {
       col_cov.push_back(v.cov + i);
       col_kind.push_back((uint8_t)v.kind);
@@ -205,7 +258,6 @@ static int build_columns(ovgpu_ctx *c, bool defer_flush = false) {
     }
     D += v.size;
   }
-  if (D + 1 > 512) return set_err(OVGPU_ERR_CAPACITY, "more than 511 Jacobian columns");
   c->D = D, c->LD = D + 1;
   { // the regions of the unprojected stack (ovgpu_types.h: RawStack): classes of clones by the tile column their block ends in
     c->raw_cols_ok = false, c->raw_ncls = 0, c->raw_tables_ok = false;
@@ -246,17 +298,23 @@ static int build_columns(ovgpu_ctx *c, bool defer_flush = false) {
   HIPCHK(c->Yaug.reserve((size_t)D * (D + N + 1)));
   hipStream_t s = c->stream;
   (void)s;
-  HIPCHK(upload_deferred(c, c->clone_col.p, clone_col.data(), sizeof(int32_t) * C));
-  HIPCHK(upload_deferred(c, c->calib_col.p, calib_col.data(), sizeof(int32_t) * K));
-  HIPCHK(upload_deferred(c, c->intr_col.p, intr_col.data(), sizeof(int32_t) * K));
-  HIPCHK(upload_deferred(c, c->col_cov.p, col_cov.data(), sizeof(int32_t) * D));
-  HIPCHK(upload_deferred(c, c->col_kind.p, col_kind.data(), D));
-  HIPCHK(upload_deferred(c, c->col_sub.p, col_sub.data(), D));
-  HIPCHK(upload_deferred(c, c->col_var.p, col_var.data(), sizeof(uint16_t) * D));
-  if (c->L > 0) HIPCHK(upload_deferred(c, c->lm_col.p, c->h_lm_col.data(), sizeof(int32_t) * c->L));
-  // host staging vectors go out of scope: their bytes sit in the page-locked arena (round 6: no synchronisation; the scatter launch that
-  // carries them may be the caller's — ovgpu_set_state adds its own arrays to it — and is flushed here otherwise)
-  if (!defer_flush) HIPCHK(upload_fence(c, c->stream));
+  if (act) { // tables of an active set: built on the device
+    const int rca = enqueue_active_columns(c, active_idx, D);
+    if (rca != OVGPU_OK) return rca;
+    if (!defer_flush) HIPCHK(upload_fence(c, c->stream));
+  } else {
+    HIPCHK(upload_deferred(c, c->clone_col.p, clone_col.data(), sizeof(int32_t) * C));
+    HIPCHK(upload_deferred(c, c->calib_col.p, calib_col.data(), sizeof(int32_t) * K));
+    HIPCHK(upload_deferred(c, c->intr_col.p, intr_col.data(), sizeof(int32_t) * K));
+    HIPCHK(upload_deferred(c, c->col_cov.p, col_cov.data(), sizeof(int32_t) * D));
+    HIPCHK(upload_deferred(c, c->col_kind.p, col_kind.data(), D));
+    HIPCHK(upload_deferred(c, c->col_sub.p, col_sub.data(), D));
+    HIPCHK(upload_deferred(c, c->col_var.p, col_var.data(), sizeof(uint16_t) * D));
+    if (c->L > 0) HIPCHK(upload_deferred(c, c->lm_col.p, c->h_lm_col.data(), sizeof(int32_t) * c->L));
+    // host staging vectors go out of scope: their bytes sit in the page-locked arena (round 6: no synchronisation; the scatter launch that
+    // carries them may be the caller's — ovgpu_set_state adds its own arrays to it — and is flushed here otherwise)
+    if (!defer_flush) HIPCHK(upload_fence(c, c->stream));
+  }
   c->have_feats = false;           // workspaces depend on D
   c->tri_readable = false;
   return OVGPU_OK;
@@ -283,6 +341,7 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
   for (int i = 0; i < C; i++) c->h_vars.push_back({st->clone_cov_id[i], 6, COL_CLONE, i});
   c->N = N, c->C = C, c->K = K;
   c->L = 0, c->h_lm_rep.clear(), c->h_lm_cov.clear(), c->h_lm_col.clear(), c->h_lm_anchor.clear();
+  c->active_given = false, c->h_lm_active.clear(); // an active landmark set holds until the state or the landmarks are replaced
   c->row_stride = (c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D) ? 72 : 48;
   HIPCHK(c->clone_col.reserve(C));
   HIPCHK(c->calib_col.reserve(K));

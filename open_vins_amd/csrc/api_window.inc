@@ -92,6 +92,7 @@ int ovgpu_state_marginalize(ovgpu_ctx *c, int32_t cov_id, int32_t size) {
     c->h_lm_rep.erase(c->h_lm_rep.begin() + drop_lm);
     c->h_lm_cov.erase(c->h_lm_cov.begin() + drop_lm);
     c->h_lm_anchor.erase(c->h_lm_anchor.begin() + drop_lm);
+    if (c->active_given && drop_lm < (int)c->h_lm_active.size()) c->h_lm_active.erase(c->h_lm_active.begin() + drop_lm); // the set follows the landmarks' indices
     c->L -= 1;
   }
   HIPCHK(upload_sync(c, s)); // the scratch copies go out of scope

@@ -70,6 +70,64 @@ __global__ void k_slam_gather(int F, const int32_t *__restrict__ lm_index, const
   status[f] = (meas_offsets[f + 1] - meas_offsets[f] >= min_meas) ? OVGPU_FEAT_USED : OVGPU_FEAT_TOO_FEW_MEAS;
 }
 
+// ovgpu_set_active_landmarks: the column map of the calls that follow, from the resident variables sorted by covariance id (`vars`: covariance
+// id, size, kind, index of each) and the landmarks the caller named (`active_idx`).  UpdaterSLAM::update gives columns to the variables its
+// batch touches (UpdaterSLAM.cpp:300-340), delayed_init to no resident landmark at all (:147-239): a landmark outside the set keeps column
+// -1 and is corrected through its covariance rows alone (k_landmark_update reads dx by covariance id).  Calibration and clones always have
+// columns.  ONE wavefront: the set changes with every call and the map is a few hundred entries, so the launch is latency, not work — a
+// wave-level inclusive scan of the block widths, 64 variables a step, gives every variable its first column; no LDS traffic and no barrier
+// inside the scan loop (the two barriers in front of it separate the set's flags from their readers).
+// The walk — which variables get columns, col_sub of a single-depth landmark — is layout_columns' (api_state.inc), kept in step with it by hand.
+// Every store is bounded by the capacity the host reserved from its own mirror of the same walk (Dcap, L, C, K).
+struct ActiveColsParams {
+  int V, L, C, K, n_active, Dcap;
+  const int32_t *vars;       // [4 V]
+  const int32_t *active_idx; // [n_active], duplicates allowed
+  int32_t *clone_col, *calib_col, *intr_col, *lm_col, *col_cov;
+  uint8_t *col_kind, *col_sub;
+  uint16_t *col_var;
+};
+__global__ void __launch_bounds__(64) k_active_columns(ActiveColsParams p) {
+  extern __shared__ uint8_t act_lm[]; // [L]
+  const int lane = threadIdx.x;
+  for (int l = lane; l < p.L; l += 64) act_lm[l] = 0, p.lm_col[l] = -1;
+  for (int i = lane; i < p.C; i += 64) p.clone_col[i] = -1;
+  for (int k = lane; k < p.K; k += 64) p.calib_col[k] = -1, p.intr_col[k] = -1; // (a calibration that is not estimated has no column)
+  __syncthreads();
+  for (int i = lane; i < p.n_active; i += 64) {
+    const int l = p.active_idx[i];
+    if (l >= 0 && l < p.L) act_lm[l] = 1; // (a duplicate stores the same byte)
+  }
+  __syncthreads();
+  int base = 0;
+  for (int v0 = 0; v0 < p.V; v0 += 64) {
+    const int v = v0 + lane;
+    int cov = 0, size = 0, kind = COL_CLONE, index = 0, w = 0;
+    if (v < p.V) {
+      cov = p.vars[4 * v], size = p.vars[4 * v + 1], kind = p.vars[4 * v + 2], index = p.vars[4 * v + 3];
+      const bool in_range = kind == COL_LANDMARK ? (index >= 0 && index < p.L) : (index >= 0 && index < (kind == COL_CLONE ? p.C : p.K));
+      w = (in_range && (kind != COL_LANDMARK || act_lm[index])) ? size : 0;
+    }
+    int x = w;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int y = __shfl_up(x, off, 64);
+      if (lane >= off) x += y;
+    }
+    const int start = base + x - w;
+    if (w > 0 && start + w <= p.Dcap) {
+      if (kind == COL_CLONE) p.clone_col[index] = start;
+      else if (kind == COL_CALIB_POSE) p.calib_col[index] = start;
+      else if (kind == COL_CALIB_INTR) p.intr_col[index] = start;
+      else p.lm_col[index] = start;
+      for (int i = 0; i < w; i++) {
+        p.col_cov[start + i] = cov + i, p.col_kind[start + i] = (uint8_t)kind, p.col_var[start + i] = (uint16_t)index;
+        p.col_sub[start + i] = (uint8_t)((kind == COL_LANDMARK && size == 1) ? 2 : i); // the depth is column 2 of H_f
+      }
+    }
+    base += __shfl(x, 63, 64);
+  }
+}
+
 // Landmark::update: value += dx[id .. id+2]     (L from a device counter when the count changes inside a stream of launches)
 // state dof of a landmark: 3, or 1 for a single-depth landmark whose state variable is the LAST of its three stored values
 __global__ void k_landmark_update(int L, const int32_t *__restrict__ L_dev, const int32_t *__restrict__ lm_rep, const double *__restrict__ dx,

@@ -21,9 +21,12 @@ void UpdaterSLAM::change_anchors(std::shared_ptr<State> state) {
   const ovgpu_shim::CloneIndex clones(snap.fs.clone_times);
   ovgpu_shim::FlatLandmarks fl;
   bool any = false;
+  std::vector<int32_t> moving; // indices into the view of the landmarks anchored in the clone that leaves
   for (const auto &kv : state->_features_SLAM) {
+    const bool moves = LandmarkRepresentation::is_relative_representation(kv.second->_feat_representation) && kv.second->_anchor_clone_timestamp == marg_timestep; // :498-500
+    if (moves) moving.push_back((int32_t)fl.cov.size());
     fl.add(kv.second, snap, clones);
-    any |= LandmarkRepresentation::is_relative_representation(kv.second->_feat_representation) && kv.second->_anchor_clone_timestamp == marg_timestep; // :498-500
+    any |= moves;
   }
   if (!any) return;
   FeatureInitializerOptions fo;
@@ -32,6 +35,8 @@ void UpdaterSLAM::change_anchors(std::shared_ptr<State> state) {
   const ovgpu_landmarks_view lv = fl.view();
   cx.check(ovgpu_set_state(cx.get(), &sv), "ovgpu_set_state");
   cx.check(ovgpu_set_landmarks(cx.get(), &lv), "ovgpu_set_landmarks");
+  // (perform_anchor_change reads no column table: the set costs one small launch here and keeps the context's map no wider than the call needs)
+  cx.check(ovgpu_shim::set_active_landmarks(cx.get(), (int32_t)moving.size(), moving.data()), "ovgpu_set_active_landmarks");
   int32_t moved = 0;
   cx.check(ovgpu_slam_change_anchors(cx.get(), clones.find(marg_timestep), clones.find(state->_timestamp), &moved), "ovgpu_slam_change_anchors");
   if (moved == 0) return;

@@ -68,6 +68,7 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
   const ovgpu_landmarks_view lv = old.view();
   cx.check(ovgpu_set_state(ctx, &sv), "ovgpu_set_state");
   cx.check(ovgpu_set_landmarks(ctx, &lv), "ovgpu_set_landmarks");
+  cx.check(ovgpu_shim::set_active_landmarks(ctx, 0, nullptr), "ovgpu_set_active_landmarks"); // no resident landmark has a column in StateHelper::initialize
   cx.check(ovgpu_set_features(ctx, &fv), "ovgpu_set_features");
   if (any_aruco) cx.check(ovgpu_set_feature_options(ctx, f_sigma.data(), f_mult.data()), "ovgpu_set_feature_options");
   if (any_aruco && state->_options.feat_rep_aruco != rep) cx.check(ovgpu_set_feature_reps(ctx, f_rep.data()), "ovgpu_set_feature_reps");

@@ -60,6 +60,17 @@ void update_all(UpdaterOptions &opt_slam, UpdaterOptions &opt_aruco, std::shared
   const ovgpu_landmarks_view lv = fl.view();
   ctx.check(ovgpu_set_state(ctx.get(), &sv), "ovgpu_set_state");
   ctx.check(ovgpu_set_landmarks(ctx.get(), &lv), "ovgpu_set_landmarks");
+  // Hx_order of the reference holds what the batch touches (:300-340).  The view above holds the batch's landmarks and nothing else, so every
+  // landmark of it has a column anyway: naming them would cost a table launch per frame and narrow nothing.  The set is named only when the view
+  // holds a landmark that no feature of the batch observes.
+  {
+    std::vector<char> seen((size_t)lv.L, 0);
+    int32_t distinct = 0;
+    for (const int32_t l : lm_index)
+      if (!seen[(size_t)l]) seen[(size_t)l] = 1, ++distinct;
+    if (distinct < lv.L)
+      ctx.check(ovgpu_shim::set_active_landmarks(ctx.get(), (int32_t)lm_index.size(), lm_index.data()), "ovgpu_set_active_landmarks");
+  }
   ctx.check(ovgpu_set_features(ctx.get(), &fv), "ovgpu_set_features");
   if (any_aruco) // rows come back scaled to _options_slam.sigma_pix, so R_big below stays isotropic
     ctx.check(ovgpu_set_feature_options(ctx.get(), f_sigma.data(), f_mult.data()), "ovgpu_set_feature_options");

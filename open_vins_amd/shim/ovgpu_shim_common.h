@@ -29,7 +29,19 @@
 #include "ovgpu.h"
 #include "ovgpu_flatten.h"
 
+// ovgpu_set_active_landmarks came with ABI 9.  A weak reference keeps the drop-in loadable next to a library that does not export it: the
+// calls then run over the columns of every uploaded landmark, as they did before (set_active_landmarks below).
+#pragma weak ovgpu_set_active_landmarks
+
 namespace ovgpu_shim {
+
+// The landmarks that need Jacobian columns in the SLAM calls that follow (include/ovgpu.h): the batch's for UpdaterSLAM::update
+// (UpdaterSLAM.cpp:300-340), none for delayed_init (:147-239), the ones that move for change_anchors.  Between ovgpu_set_landmarks and
+// ovgpu_set_features.  Returns OVGPU_OK without a call when the library has no such entry.
+inline int set_active_landmarks(ovgpu_ctx *ctx, int32_t n, const int32_t *lm_index) {
+  if (!ovgpu_set_active_landmarks) return OVGPU_OK;
+  return ovgpu_set_active_landmarks(ctx, n, lm_index);
+}
 
 // One context per distinct option set (VioManager owns one UpdaterMSCKF and one UpdaterSLAM, so in practice one or two): the
 // options are compared on every call, an updater constructed later with other thresholds gets its own context.

@@ -192,6 +192,17 @@ class UpdaterMSCKF:
         capi.check(self.lib.ovgpu_set_landmarks(self._ctx, C.byref(v.landmarks)), "ovgpu_set_landmarks")
         capi.check(self.lib.ovgpu_set_features(self._ctx, C.byref(v.features)), "ovgpu_set_features")
 
+    def set_active_landmarks(self, lm_index=None):
+        """The resident landmarks that get Jacobian columns in the SLAM calls that follow (ovgpu_set_active_landmarks; UpdaterSLAM.cpp:300-340:
+        Hx_order holds what the batch touches).  lm_index: indices into the landmark view, [] for the empty set (delayed_init, init_systems,
+        change_anchors), None for every resident landmark again.  Call between set_landmarks and set_features: the batch is laid out for the
+        column count of the set, so upload it (again) afterwards."""
+        if lm_index is None:
+            capi.check(self.lib.ovgpu_set_active_landmarks(self._ctx, -1, None), "ovgpu_set_active_landmarks")
+            return
+        idx = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
+        capi.check(self.lib.ovgpu_set_active_landmarks(self._ctx, int(idx.size), _ip(idx)), "ovgpu_set_active_landmarks")
+
     def slam_update(self, lm_index=None):
         """lm_index [F]: the resident landmark each uploaded track observes (default: the snapshot's)."""
         v = self._views
