@@ -75,8 +75,12 @@ extern "C" {
 /*      landmarks together exceed 511 columns: the SLAM call whose EFFECTIVE     */
 /*      column set exceeds them does.  A caller that never names a set and stays */
 /*      under that bound sees what ABI 8 computed.  Nothing changed shape.       */
+/*  10  ovgpu_slam_change_anchors_batched (every moving landmark in a fixed      */
+/*      number of launches) and ovgpu_slam_anchor_systems(_len) (mode A of       */
+/*      UpdaterSLAM::change_anchors).  Nothing changed shape; the entries of     */
+/*      ABI 9 compute what they computed.                                        */
 /* ------------------------------------------------------------------------- */
-#define OVGPU_ABI_VERSION 9
+#define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
 
 /* ------------------------------------------------------------------------- */
@@ -639,6 +643,51 @@ int ovgpu_slam_change_anchor(ovgpu_ctx *ctx, int32_t lm_index, int32_t new_ancho
  * reference passes state->_timestamp), same camera.  n_changed (optional) = how many moved.  */
 int ovgpu_slam_change_anchors(ovgpu_ctx *ctx, int32_t marg_clone, int32_t new_clone,
                               int32_t *n_changed);
+
+/* The same call in a fixed number of launches (ABI 10): one kernel forms the transition matrix Phi_l,
+ * the new value / first estimate and the new anchor of EVERY moving landmark at the entry state
+ * (perform_anchor_change builds Phi from state values alone, and no anchor change moves a clone or a
+ * calibration), three more apply the joint StateHelper::EKFPropagation whose transition matrix has
+ * the block rows Phi_l.  Contract, checks and error codes are ovgpu_slam_change_anchors'; the
+ * covariance differs from its result by the rounding of another order of summation and is exactly
+ * symmetric.  ovgpu_slam_change_anchors itself launches per landmark, as before.                  */
+int ovgpu_slam_change_anchors_batched(ovgpu_ctx *ctx, int32_t marg_clone, int32_t new_clone,
+                                      int32_t *n_changed);
+
+/* Mode A of UpdaterSLAM::change_anchors (ABI 10), shaped like ovgpu_slam_init_systems: what
+ * perform_anchor_change hands to StateHelper::EKFPropagation (:612-640) and writes into the landmark
+ * (:642-646), for every resident landmark anchored in `marg_clone`, in landmark order.  The resident
+ * state (P, landmarks, anchors, column map, a pending prior factorisation) is left exactly as it was:
+ * the host replays the systems through the stock EKFPropagation(state, {landmark}, phi_order_OLD,
+ * Phi, Q = 0), one landmark after the other.  Each Phi depends on state values only, so the replay
+ * in order reproduces the reference's sequence.  Per landmark (ovgpu_anchor_system):
+ *   lm_index, cov_id   the landmark (index into the landmark view, covariance id); lsz = 3, or 1 for the single depth
+ *   n_vars, n_old      phi_order_OLD = var_id / var_size [var_off .. var_off + n_vars) in the REFERENCE's order (:592-610): old
+ *                      anchor clone, old extrinsics (if estimated), new anchor clone, new extrinsics (if estimated and
+ *                      another camera), the landmark; n_old = the sum of the sizes
+ *   Phi [phi_off .. + lsz * n_old]   row-major
+ *   value / fej [3 * k .. 3 * k + 3) of system k   the landmark in its new anchor, representation coordinates as
+ *                      ovgpu_get_landmarks gives them (single depth: bearing x, bearing y, rho)
+ *   anchor_cam, anchor_clone   the new anchor
+ * The arrays are sized by ovgpu_slam_anchor_systems_len (same state, marg_clone, new_clone): sys / value / fej by
+ * n_sys, var_id / var_size by n_vars, Phi by n_phi; OVGPU_ERR_CAPACITY when `cap` is smaller.  Without an anchored
+ * landmark both return OVGPU_OK with all sizes 0.  A resident state and landmarks are all they need.             */
+typedef struct {
+  int64_t n_sys;  /* moving landmarks               */
+  int64_t n_vars; /* entries of var_id / var_size   */
+  int64_t n_phi;  /* doubles of Phi                 */
+} ovgpu_anchor_sizes;
+
+typedef struct {
+  int32_t lm_index, cov_id, lsz, feat_rep, n_vars, n_old, anchor_cam, anchor_clone;
+  int64_t var_off, phi_off;
+} ovgpu_anchor_system;
+
+int ovgpu_slam_anchor_systems_len(ovgpu_ctx *ctx, int32_t marg_clone, int32_t new_clone,
+                                  ovgpu_anchor_sizes *sizes);
+int ovgpu_slam_anchor_systems(ovgpu_ctx *ctx, int32_t marg_clone, int32_t new_clone,
+                              const ovgpu_anchor_sizes *cap, ovgpu_anchor_system *sys, int32_t *var_id,
+                              int32_t *var_size, double *Phi, double *value, double *fej);
 
 /* Per-feature landmark representation for ovgpu_slam_delayed_init on the uploaded batch: UpdaterSLAM::delayed_init
  * initialises an ArUco corner in StateOptions::feat_rep_aruco and every other feature in feat_rep_slam

@@ -112,6 +112,17 @@ class InitSystem(C.Structure):
                 ("hf_off", C.c_int64), ("res_off", C.c_int64), ("chi2", C.c_double), ("chi2_thresh", C.c_double), ("p_seed", C.c_double * 3)]
 
 
+class AnchorSizes(C.Structure):
+    """ovgpu_anchor_sizes: lengths of the outputs of ovgpu_slam_anchor_systems."""
+    _fields_ = [("n_sys", C.c_int64), ("n_vars", C.c_int64), ("n_phi", C.c_int64)]
+
+
+class AnchorSystem(C.Structure):
+    """ovgpu_anchor_system: one moving landmark as perform_anchor_change hands it to StateHelper::EKFPropagation (include/ovgpu.h)."""
+    _fields_ = [("lm_index", C.c_int32), ("cov_id", C.c_int32), ("lsz", C.c_int32), ("feat_rep", C.c_int32), ("n_vars", C.c_int32),
+                ("n_old", C.c_int32), ("anchor_cam", C.c_int32), ("anchor_clone", C.c_int32), ("var_off", C.c_int64), ("phi_off", C.c_int64)]
+
+
 def _ptr(a, ctype):
     if a is None:
         return None
@@ -235,6 +246,10 @@ def declare(lib):
         "ovgpu_get_features": (C.c_int, [ctxp, c_int32_p, c_int32_p, c_int32_p, c_float_p, c_float_p, c_int32_p, c_int32_p]),
         "ovgpu_slam_change_anchor": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.c_int32]),
         "ovgpu_slam_change_anchors": (C.c_int, [ctxp, C.c_int32, C.c_int32, c_int32_p]),
+        "ovgpu_slam_change_anchors_batched": (C.c_int, [ctxp, C.c_int32, C.c_int32, c_int32_p]),
+        "ovgpu_slam_anchor_systems_len": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(AnchorSizes)]),
+        "ovgpu_slam_anchor_systems": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(AnchorSizes), C.POINTER(AnchorSystem), c_int32_p, c_int32_p,
+                                                c_double_p, c_double_p, c_double_p]),
         "ovgpu_state_marginalize": (C.c_int, [ctxp, C.c_int32, C.c_int32]),
         "ovgpu_state_augment_clone": (C.c_int, [ctxp, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_int32_p]),
         "ovgpu_state_propagate": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),

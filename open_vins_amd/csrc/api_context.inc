@@ -128,6 +128,10 @@ struct ovgpu_ctx {
   std::vector<int32_t> h_clone_cov, h_calib_cov, h_intr_cov; // covariance ids as the kernels see them (-1: not estimated)
   DevBuf<double> prop_w, prop_in; // EKFPropagation workspaces
   DevBuf<int32_t> prop_ids;
+  // the batched anchor change (k_anchor_change_all, k_cov_propagate_multi): entry table | gmap | rowg, the ragged ids, Phi | value | fej, W | G
+  DevBuf<int32_t> anc_tab, anc_ids;
+  DevBuf<double> anc_phi, anc_w;
+  std::vector<int32_t> h_anc_tab; // the table's host source (outlives the call that uploads it)
   // SLAM landmarks (ovgpu_set_landmarks); L > 0 switches the per-feature kernel to the UpdaterSLAM rules
   int L = 0;
   // the resident landmarks' representations, one each (Landmark::_feat_representation: StateOptions::feat_rep_slam, or feat_rep_aruco for

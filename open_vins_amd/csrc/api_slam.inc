@@ -692,6 +692,146 @@ int ovgpu_slam_change_anchors(ovgpu_ctx *c, int32_t marg_clone, int32_t new_clon
   return OVGPU_OK;
 }
 
+// ---------------------------------------------------------------------------
+// UpdaterSLAM::change_anchors for all moving landmarks at once: k_anchor_change_all + k_cov_propagate_multi (mode B), or the first alone
+// with its outputs handed to the host (mode A)
+// ---------------------------------------------------------------------------
+// The landmarks anchored in marg_clone, in landmark order, and the ragged layout of what the kernels write for them (host prefix sums)
+struct AnchorBatchPlan {
+  int n = 0, S = 0;              // moving landmarks, the sum of their dof
+  int64_t n_ids = 0, n_phi = 0;  // sum of n_old, sum of dof * n_old
+  int64_t n_vars = 0;
+  std::vector<int32_t> tab;      // 8 ints per landmark (k_anchor_change_all)
+};
+// ovgpu_slam_change_anchors' checks; *none = there is nothing to move and the call returns OVGPU_OK (:493-496: global landmarks are skipped)
+static int anchor_batch_plan(ovgpu_ctx *c, int marg_clone, int new_clone, AnchorBatchPlan &pl, bool *none) {
+  *none = false;
+  if (c && c->have_state && !c->poses_only && (c->L <= 0 || !lm_any_anchored(c))) {
+    *none = true;
+    return OVGPU_OK;
+  }
+  int rc = anchor_change_checks(c);
+  if (rc != OVGPU_OK) return rc;
+  if (marg_clone < 0 || marg_clone >= c->C || new_clone < 0 || new_clone >= c->C || marg_clone == new_clone)
+    return set_err(OVGPU_ERR_INVALID, "clone index out of range");
+  pl = AnchorBatchPlan();
+  for (int l = 0; l < c->L; l++) {
+    const int32_t a = c->h_lm_anchor[l];
+    if (a < 0 || (a & 1023) != marg_clone) continue;
+    const int cam = a >> 10, lsz = lm_dof(c->h_lm_rep[l]); // same camera (:499-500): its extrinsics appear once in phi_order_OLD
+    const int est = c->h_calib_cov[cam] >= 0 ? 1 : 0;
+    const int n_old = 6 + 6 * est + 6 + lsz;
+    const int32_t e[8] = {l, cam, new_clone, lsz, n_old, (int32_t)pl.n_phi, (int32_t)pl.n_ids, c->h_lm_cov[l]};
+    pl.tab.insert(pl.tab.end(), e, e + 8);
+    pl.n++, pl.S += lsz, pl.n_ids += n_old, pl.n_phi += (int64_t)lsz * n_old, pl.n_vars += 3 + est;
+  }
+  *none = pl.n == 0;
+  return OVGPU_OK;
+}
+
+// the table on the device and ONE launch of k_anchor_change_all; Phi | value | fej in anc_phi, the ids in anc_ids
+static int enqueue_anchor_change_all(ovgpu_ctx *c, const AnchorBatchPlan &pl, bool rewrite, size_t tab_ints) {
+  hipStream_t s = c->stream;
+  HIPCHK(c->anc_tab.reserve(tab_ints));
+  HIPCHK(c->anc_ids.reserve((size_t)pl.n_ids));
+  HIPCHK(c->anc_phi.reserve((size_t)pl.n_phi + 6 * (size_t)pl.n));
+  HIPCHK(upload(c->anc_tab.p, c->h_anc_tab.data(), sizeof(int32_t) * tab_ints, s));
+  AnchorAllParams ap;
+  ap.n = pl.n, ap.do_fej = c->dopt.do_fej, ap.rewrite = rewrite ? 1 : 0, ap.tab = c->anc_tab.p;
+  ap.tab_clone = c->tab_clone.p, ap.tab_cam = c->tab_cam.p, ap.clone_cov = c->clone_cov.p, ap.calib_cov = c->calib_cov.p;
+  ap.lm = landmark_store(c), ap.phi = c->anc_phi.p, ap.ids = c->anc_ids.p;
+  ap.val = c->anc_phi.p + pl.n_phi, ap.fej = ap.val + 3 * (size_t)pl.n;
+  hipLaunchKernelGGL(k_anchor_change_all, dim3(pl.n), dim3(64), 0, s, ap);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+int ovgpu_slam_change_anchors_batched(ovgpu_ctx *c, int32_t marg_clone, int32_t new_clone, int32_t *n_changed) {
+  if (n_changed) *n_changed = 0;
+  AnchorBatchPlan pl;
+  bool none = false;
+  int rc = anchor_batch_plan(c, marg_clone, new_clone, pl, &none);
+  if (rc != OVGPU_OK || none) return rc;
+  { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }
+  hipStream_t s = c->stream;
+  const int N = c->N, S = pl.S;
+  // table | gmap [S]: (entry << 2 | row) of every joint row | rowg [N]: the joint row of every covariance row
+  const size_t tab_ints = pl.tab.size() + (size_t)S + (size_t)N;
+  c->h_anc_tab = pl.tab;
+  c->h_anc_tab.resize(pl.tab.size() + S);
+  c->h_anc_tab.resize(tab_ints, -1);
+  int32_t *gmap = c->h_anc_tab.data() + pl.tab.size(), *rowg = gmap + S;
+  for (int b = 0, g = 0; b < pl.n; b++) {
+    const int32_t *e = pl.tab.data() + 8 * b;
+    if (e[7] < 0 || e[7] + e[3] > N) return set_err(OVGPU_ERR_INVALID, "a landmark's covariance id lies outside the covariance");
+    for (int a = 0; a < e[3]; a++, g++) gmap[g] = (b << 2) | a, rowg[e[7] + a] = g;
+  }
+  HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
+  HIPCHK(c->anc_w.reserve((size_t)N * S + (size_t)S * S));
+  if ((rc = enqueue_anchor_change_all(c, pl, true, tab_ints)) != OVGPU_OK) return rc;
+  PropMultiParams pp;
+  pp.N = N, pp.S = S, pp.tab = c->anc_tab.p, pp.gmap = c->anc_tab.p + pl.tab.size(), pp.rowg = pp.gmap + S;
+  pp.ids = c->anc_ids.p, pp.phi = c->anc_phi.p, pp.P = c->P.p, pp.W = c->anc_w.p, pp.G = c->anc_w.p + (size_t)N * S, pp.flags = c->flags.p;
+  for (int pass = 0; pass < 3; pass++) {
+    const int nt = pass == 1 ? S * S : N * S;
+    hipLaunchKernelGGL(k_cov_propagate_multi, dim3((nt + 255) / 256), dim3(256), 0, s, pp, pass);
+  }
+  HIPCHK(hipGetLastError());
+  for (int b = 0; b < pl.n; b++) c->h_lm_anchor[pl.tab[8 * b]] = (pl.tab[8 * b + 1] << 10) | new_clone;
+  if (n_changed) *n_changed = pl.n;
+  return OVGPU_OK;
+}
+
+int ovgpu_slam_anchor_systems_len(ovgpu_ctx *c, int32_t marg_clone, int32_t new_clone, ovgpu_anchor_sizes *sizes) {
+  if (!c || !sizes) return set_err(OVGPU_ERR_INVALID, "null argument");
+  sizes->n_sys = sizes->n_vars = sizes->n_phi = 0;
+  AnchorBatchPlan pl;
+  bool none = false;
+  const int rc = anchor_batch_plan(c, marg_clone, new_clone, pl, &none);
+  if (rc != OVGPU_OK || none) return rc;
+  sizes->n_sys = pl.n, sizes->n_vars = pl.n_vars, sizes->n_phi = pl.n_phi;
+  return OVGPU_OK;
+}
+
+int ovgpu_slam_anchor_systems(ovgpu_ctx *c, int32_t marg_clone, int32_t new_clone, const ovgpu_anchor_sizes *cap, ovgpu_anchor_system *sys, int32_t *var_id,
+                              int32_t *var_size, double *Phi, double *value, double *fej) {
+  if (!c || !cap) return set_err(OVGPU_ERR_INVALID, "null argument");
+  AnchorBatchPlan pl;
+  bool none = false;
+  int rc = anchor_batch_plan(c, marg_clone, new_clone, pl, &none);
+  if (rc != OVGPU_OK || none) return rc;
+  if (cap->n_sys < pl.n || cap->n_vars < pl.n_vars || cap->n_phi < pl.n_phi)
+    return set_err(OVGPU_ERR_CAPACITY, "output capacities below ovgpu_slam_anchor_systems_len");
+  if (!sys || !var_id || !var_size || !Phi || !value || !fej) return set_err(OVGPU_ERR_INVALID, "null output arrays");
+  // nothing of the resident state is written: no flag is cleared, a prior-block factorisation in flight stays valid (it reads P only)
+  hipStream_t s = c->stream;
+  c->h_anc_tab = pl.tab;
+  if ((rc = enqueue_anchor_change_all(c, pl, false, pl.tab.size())) != OVGPU_OK) return rc;
+  std::vector<double> out((size_t)pl.n_phi + 6 * (size_t)pl.n);
+  HIPCHK(hipMemcpyAsync(out.data(), c->anc_phi.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, s)); // Phi | value | fej: one gather
+  HIPCHK(upload_sync(c, s));
+  std::memcpy(Phi, out.data(), sizeof(double) * pl.n_phi);
+  std::memcpy(value, out.data() + pl.n_phi, sizeof(double) * 3 * pl.n);
+  std::memcpy(fej, out.data() + pl.n_phi + 3 * (size_t)pl.n, sizeof(double) * 3 * pl.n);
+  // phi_order_OLD (:592-610) from the host's mirrors of the ids: the kernel's column walk
+  int64_t nv = 0;
+  for (int b = 0; b < pl.n; b++) {
+    const int32_t *e = pl.tab.data() + 8 * b;
+    const int l = e[0], cam = e[1];
+    ovgpu_anchor_system &o = sys[b];
+    std::memset(&o, 0, sizeof(o));
+    o.lm_index = l, o.cov_id = e[7], o.lsz = e[3], o.feat_rep = c->h_lm_rep[l], o.n_old = e[4], o.anchor_cam = cam, o.anchor_clone = new_clone;
+    o.var_off = nv, o.phi_off = e[5];
+    auto push = [&](int32_t id, int32_t size) { var_id[nv] = id, var_size[nv] = size, nv++; };
+    push(c->h_clone_cov[marg_clone], 6);
+    if (c->h_calib_cov[cam] >= 0) push(c->h_calib_cov[cam], 6);
+    push(c->h_clone_cov[new_clone], 6);
+    push(e[7], e[3]);
+    o.n_vars = (int32_t)(nv - o.var_off);
+  }
+  return OVGPU_OK;
+}
+
 int ovgpu_set_feature_reps(ovgpu_ctx *c, const int32_t *feat_rep) {
   if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
   if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "no feature batch is resident");

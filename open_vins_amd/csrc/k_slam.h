@@ -326,6 +326,191 @@ __global__ void k_anchor_change(AnchorParams p) {
   p.lm.anchor[l] = (p.new_cam << 10) | p.new_clone;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// UpdaterSLAM::change_anchors (UpdaterSLAM.cpp:481-504) for EVERY landmark that moves, in one launch: workgroup b (one wavefront) does for
+// entry b of `tab` what k_anchor_change does for its landmark.  Phi is built from state VALUES alone (clone poses, extrinsics, the landmark's
+// own value / first estimate) and an anchor change moves no clone and no calibration, so all of them can be formed at the entry state; the
+// covariance follows in k_cov_propagate_multi.
+// tab, 8 ints per entry: landmark, new camera, new clone, dof (3 / 1), n_old, first element of its Phi (dof x n_old, row-major) in `phi`,
+// first of its n_old covariance ids in `ids`, the landmark's own covariance id (k_cov_propagate_multi).  The offsets are the host's prefix
+// sums; n_old is the host's count of the same column walk (phi_order_OLD, :592-610) the kernel does.
+// The lanes: the two Jacobian triples are the same few hundred flops for every lane (one lane's time); lane 0 parks them in LDS.  The three
+// columns of H_f_new^-1 are three independent solves, lanes 0..2; the dof x n_old entries of Phi (3 x 3 by 3 x 6 / 3 x 3 products, one dot
+// product of length 3 each) and the n_old ids go one per lane.  Entry for entry the arithmetic is k_anchor_change's.
+// rewrite != 0: the resident landmark gets its new value / first estimate / anchor (mode B); 0: the store is only read (mode A export).
+// ---------------------------------------------------------------------------------------------------
+struct AnchorAllParams {
+  int n, do_fej, rewrite;
+  const int32_t *tab;                // [8 n]
+  const double *tab_clone, *tab_cam; // [C*24], [K*12]
+  const int32_t *clone_cov, *calib_cov;
+  LandmarkStore lm;
+  double *phi;       // the Phi of every entry, ragged
+  int32_t *ids;      // the covariance ids of every entry's columns, ragged
+  double *val, *fej; // [3 n] the landmarks in their new anchors
+};
+
+__global__ void __launch_bounds__(64) k_anchor_change_all(AnchorAllParams p) {
+  __shared__ double sH[6][18]; // Ha_old, Hc_old, Ha_new, Hc_new (3 x 6), Hf_old, Hf_new (3 x 3)
+  __shared__ double sInv[9];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= p.n) return;
+  const int32_t *e = p.tab + 8 * b;
+  const int l = e[0], new_cam = e[1], new_clone = e[2], sz = e[3], n_old = e[4];
+  const int rep = p.lm.rep[l];
+  const int old_cam = p.lm.anchor[l] >> 10, old_clone = p.lm.anchor[l] & 1023;
+  // the "first estimate" of ANCHORED_MSCKF_INVERSE_DEPTH and of the single depth reads the current value (k_anchor_change; Landmark.cpp:47-59)
+  const bool fej_reads_value = rep == OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH || rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE;
+  const V3 pA_old = lm_to_xyz(rep, p.lm.value + 3 * l), pA_old_fej = lm_to_xyz(rep, (fej_reads_value ? p.lm.value : p.lm.fej) + 3 * l);
+  double Hf_old[9], Ha_old[18], Hc_old[18], Hf_new[9], Ha_new[18], Hc_new[18];
+  const int jrep = rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH : rep;
+  anchored_rep_jacobian(jrep, p.do_fej, p.tab_cam + 12 * old_cam, p.tab_clone + 24 * old_clone, pA_old, Hf_old, Ha_old, Hc_old); // :523-526
+  V3 pA_new, pA_new_fej;
+  for (int fej = 0; fej < 2; fej++) { // :536-551, :556-571
+    const int o = fej ? 12 : 0;
+    const M3 R_GtoOLD = mul(load_m3(p.tab_cam + 12 * old_cam), load_m3(p.tab_clone + 24 * old_clone + o));
+    const V3 p_OLDinG = load_v3(p.tab_clone + 24 * old_clone + o + 9) - mulT(R_GtoOLD, load_v3(p.tab_cam + 12 * old_cam + 9));
+    const M3 R_GtoNEW = mul(load_m3(p.tab_cam + 12 * new_cam), load_m3(p.tab_clone + 24 * new_clone + o));
+    const V3 p_NEWinG = load_v3(p.tab_clone + 24 * new_clone + o + 9) - mulT(R_GtoNEW, load_v3(p.tab_cam + 12 * new_cam + 9));
+    const M3 R_OLDtoNEW = mul(R_GtoNEW, transpose(R_GtoOLD));
+    const V3 p_OLDinNEW = mul(R_GtoNEW, p_OLDinG - p_NEWinG);
+    const V3 r = mul(R_OLDtoNEW, fej ? pA_old_fej : pA_old) + p_OLDinNEW;
+    if (fej) pA_new_fej = r;
+    else pA_new = r;
+  }
+  anchored_rep_jacobian(jrep, p.do_fej, p.tab_cam + 12 * new_cam, p.tab_clone + 24 * new_clone, pA_new, Hf_new, Ha_new, Hc_new); // :577-580
+  const int j0 = 3 - sz; // rows of the inverse / columns of H_f that belong to the landmark's state
+  // H_f_new^-1 (:621): column `lane` of the inverse is the solve for the unit vector e_lane; single depth: the pseudo-inverse of the 3 x 1 (:619)
+  {
+    const M3 A{Hf_new[0], Hf_new[1], Hf_new[2], Hf_new[3], Hf_new[4], Hf_new[5], Hf_new[6], Hf_new[7], Hf_new[8]};
+    const int j = lane % 3;
+    const V3 cj = colpiv_qr_solve3(A, V3{j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0});
+    if (lane < 3) {
+      if (sz == 3) {
+        sInv[lane] = cj.x, sInv[3 + lane] = cj.y, sInv[6 + lane] = cj.z;
+      } else {
+        const double h0 = Hf_new[2], h1 = Hf_new[5], h2 = Hf_new[8], nn = 1.0 / (h0 * h0 + h1 * h1 + h2 * h2);
+        sInv[lane] = 0.0, sInv[3 + lane] = 0.0, sInv[6 + lane] = nn * (lane == 0 ? h0 : lane == 1 ? h1 : h2);
+      }
+    }
+  }
+  if (lane == 0) {
+    for (int i = 0; i < 18; i++) sH[0][i] = Ha_old[i], sH[1][i] = Hc_old[i], sH[2][i] = Ha_new[i], sH[3][i] = Hc_new[i];
+    for (int i = 0; i < 9; i++) sH[4][i] = Hf_old[i], sH[5][i] = Hf_new[i];
+  }
+  __syncthreads(); // (also: every lane has read the landmark before lane 0 rewrites it below)
+  // ---- column layout (phi_order_OLD)
+  int n = 6, col_ok = -1, col_nc, col_nk = -1, col_lm; // the old anchor clone has columns 0 .. 5
+  if (p.calib_cov[old_cam] >= 0) col_ok = n, n += 6;
+  col_nc = n, n += 6;
+  if (p.calib_cov[new_cam] >= 0) {
+    if (new_cam == old_cam) col_nk = col_ok;
+    else col_nk = n, n += 6;
+  }
+  col_lm = n, n += sz;
+  if (n != n_old) return; // the host counted another layout: nothing is written (it cannot happen while the host mirrors of the ids hold)
+  int32_t *ids = p.ids + e[6];
+  for (int j = lane; j < n; j += 64) {
+    int id;
+    if (j >= col_lm) id = p.lm.cov[l] + j - col_lm;
+    else if (col_nk >= 0 && col_nk != col_ok && j >= col_nk) id = p.calib_cov[new_cam] + j - col_nk;
+    else if (j >= col_nc) id = p.clone_cov[new_clone] + j - col_nc;
+    else if (col_ok >= 0 && j >= col_ok) id = p.calib_cov[old_cam] + j - col_ok;
+    else id = p.clone_cov[old_clone] + j;
+    ids[j] = id;
+  }
+  // Phi(a, col) = sum over the blocks that own the column of sign * (inv H)(a, .), accumulated in k_anchor_change's order
+  auto prod = [&](int a, const double *H, int w, int bcol) {
+    double sv = 0.0;
+    for (int k = 0; k < 3; k++) sv = fma(sInv[3 * (a + j0) + k], H[w * k + bcol], sv);
+    return sv;
+  };
+  double *phi = p.phi + e[5];
+  for (int t = lane; t < sz * n; t += 64) {
+    const int a = t / n, j = t - a * n;
+    double v = 0.0;
+    if (j < 6) v += prod(a, sH[0], 6, j);                                                  // :626-628
+    if (col_ok >= 0 && j >= col_ok && j < col_ok + 6) v += prod(a, sH[1], 6, j - col_ok);
+    if (j >= col_lm) v += prod(a, sH[4], 3, j - col_lm + j0);                              // :631
+    if (j >= col_nc && j < col_nc + 6) v += -1.0 * prod(a, sH[2], 6, j - col_nc);          // :634-636
+    if (col_nk >= 0 && j >= col_nk && j < col_nk + 6) v += -1.0 * prod(a, sH[3], 6, j - col_nk);
+    phi[t] = v;
+  }
+  // ---- the landmark in its new anchor (:642-647)
+  if (lane == 0) {
+    double v[3], vf[3];
+    lm_from_xyz(rep, pA_new, v);
+    lm_from_xyz(rep, pA_new_fej, vf);
+    for (int i = 0; i < 3; i++) p.val[3 * b + i] = v[i], p.fej[3 * b + i] = vf[i];
+    if (p.rewrite) {
+      for (int i = 0; i < 3; i++) p.lm.value[3 * l + i] = v[i], p.lm.fej[3 * l + i] = vf[i];
+      p.lm.anchor[l] = (new_cam << 10) | new_clone;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The joint StateHelper::EKFPropagation (StateHelper.cpp:36-114, Q = 0) of n anchor changes in THREE launches whatever n is.  No Phi_l has a
+// column in another moving landmark, so the reference's sequence of propagations is one propagation whose transition matrix has the block
+// rows Phi_l.  S = sum of the landmarks' dof; gmap[g] = (entry << 2 | row) of joint row g; rowg[i] = the joint row of covariance row i, -1 if
+// i belongs to no moving landmark.  Kernel boundaries are the only ordering: pass 0 reads P, pass 1 reads W, pass 2 alone writes P.
+//   pass 0: W[i][g]  = sum_k P[i][old_l[k]] Phi_l[a][k]              every row i < N, every joint row g = (l, a)    (k_cov_propagate's pass 0)
+//   pass 1: G[g][h]  = sum_k Phi_l[a][k] W[old_l[k]][h]              g <= h, stored at [g][h] and [h][g]: Phi_l P(old_l, old_m) Phi_m^T
+//   pass 2: P(i, new_g) = P(new_g, i) = W[i][g] for the rows of no moving landmark, P(new_g, new_h) = G[g][h]; negative diagonal -> flags[1]
+// Every element of P' that has a mirror image gets the same value as it: P' is exactly symmetric.
+// ---------------------------------------------------------------------------------------------------
+struct PropMultiParams {
+  int N, S;
+  const int32_t *tab, *gmap, *rowg; // [8 n], [S], [N]
+  const int32_t *ids;
+  const double *phi;
+  double *P, *W, *G; // [N * N], [N * S], [S * S]
+  int32_t *flags;
+};
+
+__global__ void __launch_bounds__(256) k_cov_propagate_multi(PropMultiParams p, int pass) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = p.N, S = p.S;
+  if (pass == 0) {
+    if (t >= N * S) return;
+    const int i = t / S, g = t - i * S;
+    const int32_t *e = p.tab + 8 * (p.gmap[g] >> 2);
+    const int a = p.gmap[g] & 3, n_old = e[4];
+    const int32_t *ids = p.ids + e[6];
+    const double *phi = p.phi + e[5] + (size_t)a * n_old;
+    double s = 0.0;
+    for (int k = 0; k < n_old; k++) s = fma(p.P[(size_t)i * N + ids[k]], phi[k], s);
+    p.W[t] = s;
+  } else if (pass == 1) {
+    if (t >= S * S) return;
+    const int g = t / S, h = t - g * S;
+    if (g > h) return;
+    const int32_t *e = p.tab + 8 * (p.gmap[g] >> 2);
+    const int a = p.gmap[g] & 3, n_old = e[4];
+    const int32_t *ids = p.ids + e[6];
+    const double *phi = p.phi + e[5] + (size_t)a * n_old;
+    double s = 0.0;
+    for (int k = 0; k < n_old; k++) s = fma(phi[k], p.W[(size_t)ids[k] * S + h], s);
+    p.G[(size_t)g * S + h] = s;
+    p.G[(size_t)h * S + g] = s;
+  } else {
+    if (t >= N * S) return;
+    const int i = t / S, g = t - i * S;
+    const int32_t *e = p.tab + 8 * (p.gmap[g] >> 2);
+    const int col = e[7] + (p.gmap[g] & 3); // covariance id of joint row g
+    const int gi = p.rowg[i];
+    if (gi >= 0) {
+      const double v = p.G[(size_t)gi * S + g];
+      p.P[(size_t)i * N + col] = v;
+      if (gi == g && v < 0.0) p.flags[1] = 1;
+    } else {
+      const double v = p.W[t];
+      p.P[(size_t)i * N + col] = v;
+      p.P[(size_t)col * N + i] = v;
+    }
+  }
+}
+
 // ovgpu_slam_init_systems: feature f's system as StateHelper::initialize takes it (StateHelper.cpp:393-481), copied out of the
 // separated form the chain has just built, before k_init_invertible / the EKF run: the three rows Q1^T [H_x | res] with H_f = R1
 // (init_out) on top of the 2m - 3 projected rows Q2^T [H_x | res] with H_f = 0 (the feature's rows of the stack).  A single-depth

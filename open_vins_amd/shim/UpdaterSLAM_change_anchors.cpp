@@ -2,11 +2,21 @@
 // rpng/open_vins v2.7): every anchored landmark whose anchor clone is about to be marginalised moves to the newest clone, same
 // camera; perform_anchor_change (:506-647: both representation Jacobians, Phi = H_f_new^-1 [H_x_old | H_f_old | -H_x_new],
 // StateHelper::EKFPropagation) runs on the device for all of them (ovgpu_slam_change_anchors).  Needs the StateAccess line of
-// ovgpu_state_access.h (it writes State::_Cov); without it keep the reference's change_anchors.
+// ovgpu_state_access.h (it writes State::_Cov).
+//
+// -DOVGPU_SHIM_CHANGE_ANCHORS_A selects the mode-A body instead (ovgpu_change_anchors_a.h): no friend line, the stock
+// StateHelper::EKFPropagation applies the transition matrices the library exports (ovgpu_slam_anchor_systems).
 #include "UpdaterSLAM.h"
 
+#ifdef OVGPU_SHIM_CHANGE_ANCHORS_A
+#include "ovgpu_change_anchors_a.h"
+#else
 #include "ovgpu_shim_common.h"
 #include "ovgpu_state_access.h"
+
+// ovgpu_slam_change_anchors_batched came with ABI 10 (every moving landmark in a fixed number of launches).  A weak reference keeps the
+// drop-in loadable next to a library that does not export it: the per-landmark entry then does the work, as before.
+#pragma weak ovgpu_slam_change_anchors_batched
 
 using namespace ov_core;
 using namespace ov_type;
@@ -16,7 +26,7 @@ void UpdaterSLAM::change_anchors(std::shared_ptr<State> state) {
   if ((int)state->_clones_IMU.size() <= state->_options.max_clone_size) return; // :484-486
   const double marg_timestep = state->margtimestep();
   // every landmark of the state in ONE view, each with its own representation (ABI 7): the global ones are skipped by the library as
-  // :493-496 skips them, the anchored ones move one after the other on the covariance the previous move left
+  // :493-496 skips them, the anchored ones move together (one joint propagation; one after the other next to a library before ABI 10)
   const ovgpu_shim::StateSnapshot snap(state);
   const ovgpu_shim::CloneIndex clones(snap.fs.clone_times);
   ovgpu_shim::FlatLandmarks fl;
@@ -38,7 +48,10 @@ void UpdaterSLAM::change_anchors(std::shared_ptr<State> state) {
   // (perform_anchor_change reads no column table: the set costs one small launch here and keeps the context's map no wider than the call needs)
   cx.check(ovgpu_shim::set_active_landmarks(cx.get(), (int32_t)moving.size(), moving.data()), "ovgpu_set_active_landmarks");
   int32_t moved = 0;
-  cx.check(ovgpu_slam_change_anchors(cx.get(), clones.find(marg_timestep), clones.find(state->_timestamp), &moved), "ovgpu_slam_change_anchors");
+  if (ovgpu_slam_change_anchors_batched)
+    cx.check(ovgpu_slam_change_anchors_batched(cx.get(), clones.find(marg_timestep), clones.find(state->_timestamp), &moved), "ovgpu_slam_change_anchors_batched");
+  else
+    cx.check(ovgpu_slam_change_anchors(cx.get(), clones.find(marg_timestep), clones.find(state->_timestamp), &moved), "ovgpu_slam_change_anchors");
   if (moved == 0) return;
   // ---- write back: covariance, and value / first estimate / anchor of every landmark that moved
   std::vector<double> P((size_t)sv.N * sv.N);
@@ -65,3 +78,4 @@ void UpdaterSLAM::change_anchors(std::shared_ptr<State> state) {
     }
   }
 }
+#endif // OVGPU_SHIM_CHANGE_ANCHORS_A

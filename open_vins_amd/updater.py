@@ -416,6 +416,34 @@ class UpdaterMSCKF:
         capi.check(self.lib.ovgpu_slam_change_anchors(self._ctx, int(marg_clone), int(new_clone), C.byref(n)), "ovgpu_slam_change_anchors")
         return n.value
 
+    def change_anchors_batched(self, marg_clone, new_clone):
+        """change_anchors in a fixed number of launches (ovgpu_slam_change_anchors_batched): every Phi at the entry state, one joint
+        EKFPropagation.  Returns how many landmarks moved."""
+        n = C.c_int32(0)
+        capi.check(self.lib.ovgpu_slam_change_anchors_batched(self._ctx, int(marg_clone), int(new_clone), C.byref(n)),
+                   "ovgpu_slam_change_anchors_batched")
+        return n.value
+
+    def anchor_systems(self, marg_clone, new_clone):
+        """Mode A of change_anchors (ovgpu_slam_anchor_systems): the resident state is left as it was.  Returns one dict per moving landmark,
+        in landmark order: lm_index, cov_id, lsz, feat_rep, phi_order [(cov_id, size)] in the reference's phi_order_OLD order, Phi
+        (lsz x n_old), value, fej (representation coordinates), anchor_cam, anchor_clone."""
+        sz = capi.AnchorSizes()
+        capi.check(self.lib.ovgpu_slam_anchor_systems_len(self._ctx, int(marg_clone), int(new_clone), C.byref(sz)), "ovgpu_slam_anchor_systems_len")
+        n = int(sz.n_sys)
+        sys_ = (capi.AnchorSystem * max(n, 1))()
+        vid, vsz = np.zeros(max(sz.n_vars, 1), np.int32), np.zeros(max(sz.n_vars, 1), np.int32)
+        Phi, val, fej = np.zeros(max(sz.n_phi, 1)), np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
+        capi.check(self.lib.ovgpu_slam_anchor_systems(self._ctx, int(marg_clone), int(new_clone), C.byref(sz), sys_, _ip(vid), _ip(vsz), _dp(Phi),
+                                                      _dp(val), _dp(fej)), "ovgpu_slam_anchor_systems")
+        out = []
+        for k in range(n):
+            s = sys_[k]
+            out.append(dict(lm_index=s.lm_index, cov_id=s.cov_id, lsz=s.lsz, feat_rep=s.feat_rep, anchor_cam=s.anchor_cam, anchor_clone=s.anchor_clone,
+                            phi_order=[(int(vid[s.var_off + i]), int(vsz[s.var_off + i])) for i in range(s.n_vars)],
+                            Phi=Phi[s.phi_off: s.phi_off + s.lsz * s.n_old].reshape(s.lsz, s.n_old).copy(), value=val[k].copy(), fej=fej[k].copy()))
+        return out
+
     # ---- window bookkeeping on the resident covariance (StateHelper::marginalize / clone / EKFPropagation) ----
     def _refresh_dims(self):
         n, c = C.c_int32(0), C.c_int32(0)
