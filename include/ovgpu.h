@@ -79,6 +79,9 @@ extern "C" {
 /*      number of launches) and ovgpu_slam_anchor_systems(_len) (mode A of       */
 /*      UpdaterSLAM::change_anchors).  Nothing changed shape; the entries of     */
 /*      ABI 9 compute what they computed.                                        */
+/*      Added later under the same number (nothing changed shape or result):    */
+/*      ovgpu_state_marginalize_batched.  Callers discover it by symbol (a weak */
+/*      reference in C / C++, hasattr in Python), not by the ABI number.        */
 /* ------------------------------------------------------------------------- */
 #define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
@@ -718,6 +721,25 @@ int ovgpu_set_feature_options(ovgpu_ctx *ctx, const double *sigma_pix, const dou
  * clones / landmarks behind it move down by one INDEX as well (StateHelper::marginalize_old_clone,
  * marginalize_slam, :618-651); a calibration variable at cov_id stops being estimated.      */
 int ovgpu_state_marginalize(ovgpu_ctx *ctx, int32_t cov_id, int32_t size);
+
+/* The same for n blocks in ONE device pass (StateHelper::marginalize_slam drops every lost
+ * landmark of a frame, :618-651): three launches and one ovgpu_state_marginalize's worth of
+ * table rebuilding whatever n is, where the chain pays a covariance copy, up to six record
+ * shifts and a host wait per block.
+ *   cov_id, size [n]  blocks of the covariance AS IT IS AT ENTRY (not the ids a chain of single
+ *                     calls would see after its earlier removals), in any order
+ * Per block the rules of ovgpu_state_marginalize hold; in addition the blocks must not overlap or
+ * repeat (OVGPU_ERR_INVALID), and a landmark anchored in a clone that leaves is legal only if
+ * that landmark leaves in the same call.  At least one clone must remain.  Every check runs
+ * before anything is modified: a refused call leaves the context as it was.  n == 0 is a no-op.
+ * Afterwards the context is in the state the chain would have left (ids shifted, anchors
+ * renumbered to the new clone indices, the active landmark set following the landmarks' indices).
+ * The covariance is SELECTED, P'[i][j] = P[keep[i]][keep[j]]: no value is touched.  (A chain of
+ * single calls takes the lower-left block of every step from the upper-right one, :303-304; the
+ * two agree bit for bit on a covariance that is symmetric bit for bit.)
+ * Not in every libovgpu.so that reports ABI 10: resolve it by symbol.                          */
+int ovgpu_state_marginalize_batched(ovgpu_ctx *ctx, int32_t n, const int32_t *cov_id,
+                                    const int32_t *size);
 
 /* StateHelper::clone of a 6-dof pose at the end of the covariance (StateHelper.cpp:341-391) plus
  * the time-offset part of StateHelper::augment_clone (:601-615).

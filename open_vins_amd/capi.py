@@ -251,6 +251,7 @@ def declare(lib):
         "ovgpu_slam_anchor_systems": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(AnchorSizes), C.POINTER(AnchorSystem), c_int32_p, c_int32_p,
                                                 c_double_p, c_double_p, c_double_p]),
         "ovgpu_state_marginalize": (C.c_int, [ctxp, C.c_int32, C.c_int32]),
+        "ovgpu_state_marginalize_batched": (C.c_int, [ctxp, C.c_int32, c_int32_p, c_int32_p]),
         "ovgpu_state_augment_clone": (C.c_int, [ctxp, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_int32_p]),
         "ovgpu_state_propagate": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
         "ovgpu_state_dims": (C.c_int, [ctxp, c_int32_p, c_int32_p]),

@@ -132,6 +132,10 @@ struct ovgpu_ctx {
   DevBuf<int32_t> anc_tab, anc_ids;
   DevBuf<double> anc_phi, anc_w;
   std::vector<int32_t> h_anc_tab; // the table's host source (outlives the call that uploads it)
+  // ovgpu_state_marginalize_batched (k_marg_plan, k_cov_remove_many, k_records_compact): blocks | clone flags | landmark flags from the host, the index
+  // lists behind them; the record arrays' second buffers (each swaps with its array, as Ppad does with P)
+  DevBuf<int32_t> marg_tab, lm_anchor_b, lm_repd_b;
+  DevBuf<double> clone_qp_b, clone_fej_b, lm_val_b, lm_fej_b;
   // SLAM landmarks (ovgpu_set_landmarks); L > 0 switches the per-feature kernel to the UpdaterSLAM rules
   int L = 0;
   // the resident landmarks' representations, one each (Landmark::_feat_representation: StateOptions::feat_rep_slam, or feat_rep_aruco for

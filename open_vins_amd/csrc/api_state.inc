@@ -124,6 +124,7 @@ void ovgpu_destroy(ovgpu_ctx *c) {
   c->feat_anchor.release(), c->lm_col.release(), c->lm_anchor.release(), c->lm_index.release(), c->Ppad.release(), c->init_ws.release(), c->dx_seq.release();
   c->init_ctr.release(), c->feat_slot.release(), c->prop_w.release(), c->prop_in.release(), c->prop_ids.release();
   c->anc_tab.release(), c->anc_ids.release(), c->anc_phi.release(), c->anc_w.release();
+  c->marg_tab.release(), c->lm_anchor_b.release(), c->lm_repd_b.release(), c->clone_qp_b.release(), c->clone_fej_b.release(), c->lm_val_b.release(), c->lm_fej_b.release();
   c->trk_count.release(), c->trk_cam.release(), c->trk_slot_in.release(), c->trk_cam_in.release(), c->trk_sel.release(), c->trk_nvalid.release(), c->trk_flag.release();
   c->trk_time.release(), c->trk_clone_times.release(), c->trk_aux.release(), c->trk_uv.release(), c->trk_uvn.release(), c->trk_uv_in.release(), c->trk_uvn_in.release();
   c->dx.release(), c->given_status.release();

@@ -115,6 +115,121 @@ int ovgpu_state_marginalize(ovgpu_ctx *c, int32_t cov_id, int32_t size) {
   return rebuild_variables(c);
 }
 
+// StateHelper::marginalize_slam + marginalize_old_clone of one frame (StateHelper.cpp:618-651) as ONE removal: the blocks name the covariance as
+// it is at entry.  Three launches (k_marg_plan, k_cov_remove_many, k_records_compact) and one rebuild_variables whatever n is; the only host
+// copy is the block list, which travels through the page-locked arena.
+int ovgpu_state_marginalize_batched(ovgpu_ctx *c, int32_t n, const int32_t *cov_id, const int32_t *size) {
+  if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
+  if (n < 0 || (n > 0 && (!cov_id || !size))) return set_err(OVGPU_ERR_INVALID, "bad block arrays");
+  if (n == 0) return OVGPU_OK;
+  { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }  // the covariance changes: a prior-block factorisation started for a sharded update is stale
+  if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state was never called");
+  const int N = c->N, C = c->C, L = c->L, K = c->K;
+  // ---- checks: nothing is modified before all of them have passed
+  std::vector<std::pair<int32_t, int32_t>> blk(n);
+  for (int b = 0; b < n; b++) {
+    if (cov_id[b] < 0 || size[b] <= 0 || (int64_t)cov_id[b] + size[b] > N) return set_err(OVGPU_ERR_INVALID, "marginalised block outside the covariance");
+    blk[b] = {cov_id[b], size[b]};
+  }
+  std::sort(blk.begin(), blk.end());
+  for (int b = 1; b < n; b++)
+    if (blk[b].first < blk[b - 1].first + blk[b - 1].second) return set_err(OVGPU_ERR_INVALID, "marginalised blocks overlap or repeat");
+  // the block that touches [id, id + sz), if any (the blocks are disjoint: when it IS the variable no other one touches it); -1: none, -2: one that cuts it
+  auto block_of = [&](int id, int sz) {
+    if (id < 0) return -1;
+    auto it = std::upper_bound(blk.begin(), blk.end(), id, [](int v, const std::pair<int32_t, int32_t> &b) { return v < b.first + b.second; }); // first block that ends behind id
+    if (it == blk.end() || it->first >= id + sz) return -1;
+    return (it->first == id && it->second == sz) ? (int)(it - blk.begin()) : -2;
+  };
+  std::vector<int32_t> tab((size_t)2 * n + C + L); // blocks | clone_keep | lm_keep: what k_marg_plan reads
+  int32_t *clone_keep = tab.data() + 2 * n, *lm_keep = clone_keep + C;
+  int Cn = 0, Ln = 0;
+  for (int i = 0; i < C; i++) {
+    const int b = block_of(c->h_clone_cov[i], 6);
+    if (b == -2) return set_err(OVGPU_ERR_INVALID, "block cuts through a clone (or it is the last one)");
+    clone_keep[i] = b < 0, Cn += b < 0;
+  }
+  if (Cn < 1) return set_err(OVGPU_ERR_INVALID, "block cuts through a clone (or it is the last one)");
+  for (int l = 0; l < L; l++) {
+    const int b = block_of(c->h_lm_cov[l], lm_dof(c->h_lm_rep[l]));
+    if (b == -2) return set_err(OVGPU_ERR_INVALID, "block cuts through a landmark");
+    lm_keep[l] = b < 0, Ln += b < 0;
+  }
+  std::vector<uint8_t> calib_gone(K, 0), intr_gone(K, 0);
+  for (int k = 0; k < K; k++) {
+    const int bc = block_of(c->h_calib_cov[k], 6), bi = block_of(c->h_intr_cov[k], 8);
+    if (bc == -2) return set_err(OVGPU_ERR_INVALID, "block cuts through a camera pose");
+    if (bi == -2) return set_err(OVGPU_ERR_INVALID, "block cuts through camera intrinsics");
+    calib_gone[k] = bc >= 0, intr_gone[k] = bi >= 0;
+  }
+  if (Cn < C) // a landmark anchored in a clone that leaves must leave with it, or have been re-anchored before (UpdaterSLAM::change_anchors, VioManager.cpp:585-590)
+    for (int l = 0; l < L; l++)
+      if (lm_keep[l] && c->h_lm_anchor[l] >= 0 && !clone_keep[c->h_lm_anchor[l] & 1023])
+        return set_err(OVGPU_ERR_INVALID, "a resident landmark is anchored in the marginalised clone (ovgpu_slam_change_anchors first)");
+  int gone = 0;
+  for (int b = 0; b < n; b++) tab[2 * b] = blk[b].first, tab[2 * b + 1] = blk[b].second, gone += blk[b].second;
+  const int Nn = N - gone; // (>= 6: a clone stays)
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  HIPCHK(upload_begin(c));
+  HIPCHK(c->marg_tab.reserve(tab.size() + (size_t)N + 2 * (size_t)C + L));
+  HIPCHK(c->Ppad.reserve((size_t)Nn * Nn));
+  HIPCHK(c->clone_qp_b.reserve(std::max<size_t>(c->clone_qp.cap, 1)));
+  HIPCHK(c->clone_fej_b.reserve(std::max<size_t>(c->clone_fej.cap, 1)));
+  HIPCHK(c->lm_val_b.reserve(std::max<size_t>(c->lm_val.cap, 1)));
+  HIPCHK(c->lm_fej_b.reserve(std::max<size_t>(c->lm_fej.cap, 1)));
+  HIPCHK(c->lm_anchor_b.reserve(std::max<size_t>(c->lm_anchor.cap, 1)));
+  HIPCHK(c->lm_repd_b.reserve(std::max<size_t>(c->lm_repd.cap, 1)));
+  // ---- the device pass (a HIP error from here on is reported; the host tables below change only behind the launches)
+  HIPCHK(upload_deferred(c, c->marg_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
+  HIPCHK(upload_fence(c, s));
+  MargPlan mp;
+  mp.N = N, mp.C = C, mp.L = L, mp.n = n;
+  mp.blk = c->marg_tab.p, mp.clone_keep = mp.blk + 2 * n, mp.lm_keep = mp.clone_keep + C;
+  mp.keep = c->marg_tab.p + tab.size(), mp.clone_src = mp.keep + N, mp.clone_new = mp.clone_src + C, mp.lm_src = mp.clone_new + C;
+  hipLaunchKernelGGL(k_marg_plan, dim3(1), dim3(64), 0, s, mp);
+  hipLaunchKernelGGL(k_cov_remove_many, dim3((Nn + 255) / 256, Nn), dim3(256), 0, s, N, Nn, (const int32_t *)mp.keep, (const double *)c->P.p, c->Ppad.p);
+  RecordsCompact rp;
+  rp.Cn = Cn, rp.Ln = Ln, rp.clone_src = mp.clone_src, rp.clone_new = mp.clone_new, rp.lm_src = mp.lm_src;
+  rp.clone_qp = c->clone_qp.p, rp.clone_fej = c->clone_fej.p, rp.lm_val = c->lm_val.p, rp.lm_fej = c->lm_fej.p, rp.lm_anchor = c->lm_anchor.p, rp.lm_rep = c->lm_repd.p;
+  rp.clone_qp_out = c->clone_qp_b.p, rp.clone_fej_out = c->clone_fej_b.p, rp.lm_val_out = c->lm_val_b.p, rp.lm_fej_out = c->lm_fej_b.p;
+  rp.lm_anchor_out = c->lm_anchor_b.p, rp.lm_rep_out = c->lm_repd_b.p;
+  hipLaunchKernelGGL(k_records_compact, dim3((std::max(7 * Cn, 3 * Ln) + 255) / 256), dim3(256), 0, s, rp);
+  HIPCHK(hipGetLastError());
+  std::swap(c->P, c->Ppad);
+  std::swap(c->clone_qp, c->clone_qp_b), std::swap(c->clone_fej, c->clone_fej_b);
+  std::swap(c->lm_val, c->lm_val_b), std::swap(c->lm_fej, c->lm_fej_b), std::swap(c->lm_anchor, c->lm_anchor_b), std::swap(c->lm_repd, c->lm_repd_b);
+  // ---- the host's mirrors: what the chain of single calls leaves (ids behind a block move forward by its size, :320-323; indices close up)
+  std::vector<int32_t> before(n + 1, 0); // rows removed by the first b blocks
+  for (int b = 0; b < n; b++) before[b + 1] = before[b] + blk[b].second;
+  auto shifted = [&](int32_t id) {
+    if (id < 0) return id;
+    const int b = (int)(std::upper_bound(blk.begin(), blk.end(), std::make_pair(id, (int32_t)0x7fffffff)) - blk.begin()); // blocks that start at or before id
+    return id - before[b];
+  };
+  std::vector<int32_t> clone_new(C, -1);
+  for (int i = 0, w = 0; i < C; i++)
+    if (clone_keep[i]) clone_new[i] = w, c->h_clone_cov[w++] = shifted(c->h_clone_cov[i]);
+  c->h_clone_cov.resize(Cn);
+  for (int k = 0; k < K; k++) {
+    c->h_calib_cov[k] = calib_gone[k] ? -1 : shifted(c->h_calib_cov[k]);
+    c->h_intr_cov[k] = intr_gone[k] ? -1 : shifted(c->h_intr_cov[k]);
+  }
+  const bool act = c->active_given && (int)c->h_lm_active.size() >= L; // the set follows the landmarks' indices
+  for (int l = 0, w = 0; l < L; l++) {
+    if (!lm_keep[l]) continue;
+    const int32_t a = c->h_lm_anchor[l];
+    c->h_lm_rep[w] = c->h_lm_rep[l], c->h_lm_cov[w] = shifted(c->h_lm_cov[l]);
+    c->h_lm_anchor[w] = a >= 0 ? ((a >> 10) << 10) | clone_new[a & 1023] : a;
+    if (act) c->h_lm_active[w] = c->h_lm_active[l];
+    w++;
+  }
+  c->h_lm_rep.resize(Ln), c->h_lm_cov.resize(Ln), c->h_lm_anchor.resize(Ln);
+  if (act) c->h_lm_active.resize(Ln);
+  c->N = Nn, c->C = Cn, c->L = Ln;
+  return rebuild_variables(c);
+}
+
 int ovgpu_state_augment_clone(ovgpu_ctx *c, int32_t src_cov_id, const double *q_p, const double *q_p_fej, int32_t dt_cov_id, const double *dnc_dt,
                               int32_t *new_cov_id) {
   if (!c || !q_p || !q_p_fej) return set_err(OVGPU_ERR_INVALID, "null argument");

@@ -169,6 +169,96 @@ __global__ void k_cov_remove(int N, int id, int size, const double *__restrict__
   dst[(size_t)i * Nn + j] = src[(size_t)si * N + sj];
 }
 
+// ---------------------------------------------------------------------------------------------------
+// ovgpu_state_marginalize_batched: n blocks leave in ONE pass (three launches whatever n is).  Marginalisation only SELECTS rows and
+// columns of P, so the joint removal needs no order: k_marg_plan turns the block list into index lists, k_cov_remove_many gathers the
+// covariance through them, k_records_compact the resident clone / landmark records.
+// ---------------------------------------------------------------------------------------------------
+// One integer table on the device.  The host fills blk / clone_keep / lm_keep (its checks ran before: blocks sorted by id, disjoint, inside
+// [0, N)); k_marg_plan writes the rest.  Every list it writes has room for the UNCOMPACTED count, so no store depends on the flags' sum.
+struct MargPlan {
+  int N, C, L, n;
+  const int32_t *blk;        // [2 n] (id, size), ascending ids
+  const int32_t *clone_keep; // [C] 1: the clone stays
+  const int32_t *lm_keep;    // [L]
+  int32_t *keep;             // [N] old row / column of every new one
+  int32_t *clone_src;        // [C] old index of every new clone
+  int32_t *clone_new;        // [C] new index of every old clone, -1: it left
+  int32_t *lm_src;           // [L] old index of every new landmark
+};
+
+// stream compaction by ONE wavefront, 64 flags a step: the ballot's bits below a lane are its exclusive prefix sum (no LDS, no barrier)
+template <class Flag>
+__device__ __forceinline__ void wave_compact(int lane, int count, Flag flag, int32_t *src_of_new, int32_t *new_of_old) {
+  int run = 0;
+  for (int i0 = 0; i0 < count; i0 += 64) {
+    const int i = i0 + lane;
+    const bool f = i < count && flag(i);
+    const unsigned long long m = __ballot(f);
+    const int pos = run + __popcll(m & ((1ull << lane) - 1ull));
+    if (f) src_of_new[pos] = i; // pos <= i < count
+    if (new_of_old && i < count) new_of_old[i] = f ? pos : -1;
+    run += __popcll(m);
+  }
+}
+
+__global__ void __launch_bounds__(64) k_marg_plan(MargPlan p) {
+  const int lane = threadIdx.x;
+  // a row stays when no block holds it: the last block that starts at or before it (binary search over the sorted list) ends before it
+  wave_compact(lane, p.N, [&](int i) {
+    int lo = 0, hi = p.n; // blocks [0, lo) start at or before i
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (p.blk[2 * mid] <= i) lo = mid + 1;
+      else hi = mid;
+    }
+    return lo == 0 || p.blk[2 * (lo - 1)] + p.blk[2 * (lo - 1) + 1] <= i;
+  }, p.keep, nullptr);
+  wave_compact(lane, p.C, [&](int i) { return p.clone_keep[i] != 0; }, p.clone_src, p.clone_new);
+  wave_compact(lane, p.L, [&](int i) { return p.lm_keep[i] != 0; }, p.lm_src, nullptr);
+}
+
+// P'[i][j] = P[keep[i]][keep[j]]: one output row per grid row, consecutive lanes on consecutive j — the write is one contiguous row, the read
+// the runs of the source row between the removed blocks.  A copy: no arithmetic touches a value.
+__global__ void __launch_bounds__(256) k_cov_remove_many(int N, int Nn, const int32_t *__restrict__ keep, const double *__restrict__ src,
+                                                         double *__restrict__ dst) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+  if (i >= Nn || j >= Nn) return;
+  dst[(size_t)i * Nn + j] = src[(size_t)keep[i] * N + keep[j]];
+}
+
+// every resident record array through the index lists into its second buffer, in one launch: clone_qp / clone_fej (7 doubles a clone),
+// lm_val / lm_fej (3 doubles a landmark), lm_anchor / lm_rep (one int).  An anchor names its clone by INDEX: it is rewritten to the
+// clone's new one (the host has checked that no surviving landmark is anchored in a clone that leaves).
+struct RecordsCompact {
+  int Cn, Ln; // clones / landmarks that stay
+  const int32_t *clone_src, *clone_new, *lm_src;
+  const double *clone_qp, *clone_fej, *lm_val, *lm_fej;
+  const int32_t *lm_anchor, *lm_rep;
+  double *clone_qp_out, *clone_fej_out, *lm_val_out, *lm_fej_out;
+  int32_t *lm_anchor_out, *lm_rep_out;
+};
+__global__ void __launch_bounds__(256) k_records_compact(RecordsCompact p) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < 7 * p.Cn) {
+    const size_t s = (size_t)7 * p.clone_src[t / 7] + t % 7;
+    p.clone_qp_out[t] = p.clone_qp[s], p.clone_fej_out[t] = p.clone_fej[s];
+  }
+  if (t < 3 * p.Ln) {
+    const size_t s = (size_t)3 * p.lm_src[t / 3] + t % 3;
+    p.lm_val_out[t] = p.lm_val[s], p.lm_fej_out[t] = p.lm_fej[s];
+  }
+  if (t < p.Ln) {
+    const int s = p.lm_src[t];
+    int32_t a = p.lm_anchor[s];
+    if (a >= 0) {
+      const int32_t cl = p.clone_new[a & 1023];
+      a = cl >= 0 ? ((a >> 10) << 10) | cl : -1;
+    }
+    p.lm_anchor_out[t] = a, p.lm_rep_out[t] = p.lm_rep[s];
+  }
+}
+
 // StateHelper::clone (StateHelper.cpp:341-391): rows / columns [nid, nid + n) := those of [sid, sid + n); P has leading dimension N
 __global__ void k_cov_clone(int N, int n_old, int sid, int nid, int n, double *P) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x; // index over the OLD rows, or n_old .. n_old + n*n - 1 for the corner

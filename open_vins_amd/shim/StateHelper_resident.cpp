@@ -8,7 +8,8 @@
 //     the current one —
 //         EKFPropagation            ovgpu_state_propagate          (StateHelper.cpp:36-114)
 //         augment_clone             ovgpu_state_augment_clone      (:341-391, :579-616: the IMU pose's clone and its time-offset term)
-//         marginalize               ovgpu_state_marginalize        (:271-339)   [marginalize_old_clone, marginalize_slam call it]
+//         marginalize               ovgpu_state_marginalize        (:271-339)   [marginalize_old_clone calls it]
+//         marginalize_slam          ovgpu_state_marginalize_batched (:632-647)  [every flagged landmark in one call, where the library has the entry]
 //         get_marginal_covariance   ovgpu_state_marginal_covariance (:226-258)  [no N x N download for a chi2 test's block]
 //     — and do the HOST bookkeeping the reference does (variable ids, State::_variables, State::_clones_IMU, the size of State::_Cov);
 //     every other function brings the covariance to the host if it is not there, runs the reference's own code
@@ -23,6 +24,10 @@
 #include "utils/print.h"
 
 #include "ovgpu_resident_cov.h"
+
+// ovgpu_state_marginalize_batched is newer than the ABI number it shares with its library (10).  A weak reference keeps the drop-in loadable
+// next to a library that does not export it: marginalize_slam then takes the host path per landmark, as before.
+#pragma weak ovgpu_state_marginalize_batched
 
 namespace ov_msckf {
 // the reference's implementation under its build-time name (same signatures as state/StateHelper.h declares for StateHelper)
@@ -214,8 +219,49 @@ void StateHelper::marginalize_old_clone(std::shared_ptr<State> state) {
 }
 
 void StateHelper::marginalize_slam(std::shared_ptr<State> state) {
-  // :632-647: SLAM features flagged for marginalisation leave (never the ArUco tags' ids).  Landmarks are not resident in the MSCKF
-  // updater's context: a flagged one takes the host path (a filter without SLAM features never gets here with anything to do)
+  // :632-647: SLAM features flagged for marginalisation leave (never the ArUco tags' ids).
+  // With the covariance on the device and a library that has the batched entry, ALL of them leave in one call (landmarks are not resident in the
+  // MSCKF updater's context: their blocks belong to no resident variable and are simply removed); the host does StateHelper::marginalize's
+  // bookkeeping (:318-338) for the whole set.
+  {
+    ResidentCov &rc = ResidentCov::of(state);
+    const ResidentCov::Guard guard = rc.lock();
+    if (ovgpu_state_marginalize_batched && rc.on_device()) {
+      std::vector<std::shared_ptr<Type>> gone;
+      std::vector<int32_t> ids, sizes;
+      for (const auto &kv : state->_features_SLAM)
+        if (kv.second->should_marg && (int)kv.first > 4 * state->_options.max_aruco_features)
+          gone.push_back(kv.second), ids.push_back(kv.second->id()), sizes.push_back(kv.second->size());
+      if (gone.empty()) return;
+      std::vector<std::shared_ptr<Type>> &vars = StateAccess::variables(*state);
+      for (const auto &lm : gone)
+        if (std::find(vars.begin(), vars.end(), lm) == vars.end()) { // StateHelper.cpp:274-278
+          PRINT_ERROR(RED "StateHelper::marginalize() - Called on variable that is not in the state\n" RESET);
+          std::exit(EXIT_FAILURE);
+        }
+      rc.ctx().check(ovgpu_state_marginalize_batched(rc.ctx().get(), (int32_t)ids.size(), ids.data(), sizes.data()), "ovgpu_state_marginalize_batched");
+      // what stood behind a block moves forward by its size: every variable by the sizes of the blocks that started in front of it (ids at entry)
+      int total = 0;
+      std::vector<std::shared_ptr<Type>> remaining;
+      for (const auto &v : vars) {
+        if (std::find(gone.begin(), gone.end(), v) != gone.end()) continue;
+        int before = 0;
+        for (size_t b = 0; b < ids.size(); b++)
+          if (ids[b] < v->id()) before += sizes[b];
+        if (before > 0) v->set_local_id(v->id() - before);
+        remaining.push_back(v);
+      }
+      for (const auto &lm : gone) lm->set_local_id(-1), total += lm->size();
+      vars = remaining;
+      Eigen::MatrixXd &P = StateAccess::cov_raw(*state);
+      P.resize(P.rows() - total, P.cols() - total); // (content: on the device)
+      rc.device_written();
+      for (auto it = state->_features_SLAM.begin(); it != state->_features_SLAM.end();)
+        it = (it->second->should_marg && (int)it->first > 4 * state->_options.max_aruco_features) ? state->_features_SLAM.erase(it) : std::next(it);
+      return;
+    }
+  }
+  // otherwise a flagged one takes the host path (a filter without SLAM features never gets here with anything to do)
   auto it0 = state->_features_SLAM.begin();
   while (it0 != state->_features_SLAM.end()) {
     if ((*it0).second->should_marg && (int)(*it0).first > 4 * state->_options.max_aruco_features) {

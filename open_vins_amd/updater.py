@@ -454,6 +454,15 @@ class UpdaterMSCKF:
         capi.check(self.lib.ovgpu_state_marginalize(self._ctx, int(cov_id), int(size)), "ovgpu_state_marginalize")
         self._refresh_dims()
 
+    def state_marginalize_many(self, cov_ids, sizes):
+        """Every block in one device pass (ovgpu_state_marginalize_batched): ids of the covariance as it is NOW, any order, no overlap."""
+        ids = np.ascontiguousarray(cov_ids, dtype=np.int32).reshape(-1)
+        sz = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1)
+        if ids.shape != sz.shape:
+            raise ValueError("cov_ids and sizes differ in length")
+        capi.check(self.lib.ovgpu_state_marginalize_batched(self._ctx, int(ids.shape[0]), _ip(ids), _ip(sz)), "ovgpu_state_marginalize_batched")
+        self._refresh_dims()
+
     def state_augment_clone(self, src_cov_id, q_p, q_p_fej=None, dt_cov_id=-1, dnc_dt=None):
         q = np.ascontiguousarray(q_p, dtype=np.float64)
         qf = np.ascontiguousarray(q_p_fej if q_p_fej is not None else q_p, dtype=np.float64)
