@@ -82,6 +82,8 @@ extern "C" {
 /*      Added later under the same number (nothing changed shape or result):    */
 /*      ovgpu_state_marginalize_batched.  Callers discover it by symbol (a weak */
 /*      reference in C / C++, hasattr in Python), not by the ABI number.        */
+/*      Likewise ovgpu_slam_update_chunked (every chunk of a frame's SLAM        */
+/*      update in one device pass): a new symbol under the same number.          */
 /* ------------------------------------------------------------------------- */
 #define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
@@ -515,6 +517,50 @@ int ovgpu_set_active_landmarks(ovgpu_ctx *ctx, int32_t n, const int32_t *lm_inde
 int ovgpu_slam_update(ovgpu_ctx *ctx, const int32_t *lm_index, int32_t *feat_status,
                       double *chi2, double *chi2_thresh, double *dx, double *P_out,
                       double *lm_out, ovgpu_update_stats *stats);
+
+/* Every chunk of one frame's SLAM update in ONE device pass.  The reference calls
+ * UpdaterSLAM::update once per chunk of max_slam_in_update features (VioManager.cpp:529-547),
+ * chunk k + 1 linearised at the state chunk k left.  The result is that of this chain, for
+ * k = 0 .. n_chunks - 1, on a state carried from chunk to chunk:
+ *   1. ovgpu_set_active_landmarks with the distinct landmarks of
+ *      lm_index[chunk_first[k] .. chunk_first[k + 1]);
+ *   2. ovgpu_set_features with that range of the batch (and that range's per-feature sigma and
+ *      multiplier, ovgpu_set_feature_options);
+ *   3. ovgpu_slam_update —
+ * per-feature status, chi2 and thresholds, dx of every chunk, the final P', clone, calibration
+ * and intrinsic values, and every landmark (those no chunk observes are corrected through
+ * their rows of P, as in the single call).  The same kernels run on the same inputs as in the
+ * chain; what the chain pays per chunk besides — the host walk of the columns, the batch's
+ * uploads, the blocking upload of lm_index, a read-back and its synchronisation — is paid once:
+ * one upload, one gather, one synchronisation.
+ * ORDER: ovgpu_set_state, ovgpu_set_landmarks, ovgpu_set_features with the WHOLE frame's SLAM
+ * batch (chunks are contiguous feature ranges), optionally ovgpu_set_feature_options, this call.
+ *   n_chunks >= 1;  chunk_first [n_chunks + 1]  first feature of every chunk, chunk_first[0] = 0,
+ *                   chunk_first[n_chunks] = F, not decreasing; an empty chunk does nothing (its
+ *                   dx row is zero, its stats are zero)
+ *   lm_index [F];  feat_status, chi2, chi2_thresh [F];  dx_seq [n_chunks][N] or NULL;
+ *   P_out [N*N];  lm_out [3*L];  stats [n_chunks] or NULL (ms_* are 0: the pass records no
+ *   stage events)
+ * n_chunks == 1 is one ovgpu_slam_update under the batch's own active set.  All six landmark
+ * representations in any mix and the per-feature options behave as in the single call.
+ * Every check runs before anything changes, with the single call's codes: OVGPU_ERR_INVALID
+ * (null or decreasing chunk_first, a table that does not span [0, F], an index out of range),
+ * OVGPU_ERR_NO_STATE (no state, no landmarks, no batch), OVGPU_ERR_CAPACITY — the message names
+ * the chunk — when a chunk's column set exceeds 511 columns.
+ * ON RETURN the active set in force is "all", as after ovgpu_set_active_landmarks(n < 0) — so,
+ * as there, the batch has to be handed over again before another SLAM call — and
+ * ovgpu_get_triangulation answers for the whole batch as uploaded.
+ * A chunk whose flag word is set (a prior block that fails its pivot test, a Cholesky follower
+ * that timed out, a negative diagonal) is seen at the one synchronisation: the entry state is
+ * put back from a device copy and the chunks run one by one with the single call's fall-backs.
+ * OVGPU_ERR_NEGATIVE_DIAGONAL in chunk k then leaves the state as the chain would, and the
+ * per-feature outputs up to chunk k are written.  ovgpu_debug_option "slam_chunked_fallbacks"
+ * counts these passes.
+ * Not in every libovgpu.so that reports ABI 10: resolve it by symbol.                          */
+int ovgpu_slam_update_chunked(ovgpu_ctx *ctx, int32_t n_chunks, const int32_t *chunk_first,
+                              const int32_t *lm_index, int32_t *feat_status, double *chi2,
+                              double *chi2_thresh, double *dx_seq, double *P_out, double *lm_out,
+                              ovgpu_update_stats *stats);
 
 /* Mode A of the SLAM update (strict drop-in): everything of ovgpu_slam_update up to the
  * compressed stack, returned for the stock StateHelper::EKFUpdate exactly as
@@ -1035,6 +1081,10 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             are switched off on the device, the state stays untouched and the synchronous update calls repeat
  *                             the update with the step-wise kernels
  *   "chol_timeouts"           (read only) number of updates repeated that way
+ *   "slam_chunked_fallbacks"  number of ovgpu_slam_update_chunked passes that put the entry state back and ran the chunks one by one
+ *                             (a value >= 0 sets the counter)
+ *   "slam_chunked_fail_chunk" k >= 0: the next ovgpu_slam_update_chunked treats chunk k's flag word as failed after its pass and takes
+ *                             that path (one-shot; tests)
  *   "layout_every_update"     1: the integer tables ovgpu_set_features derives once per batch (anchor measurements, clone-major
  *                             positions, column-block lists) are built again at the head of every update — what a timing loop over
  *                             a resident batch has to add to stand for a filter that hands over a new batch per frame

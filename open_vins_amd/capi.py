@@ -252,6 +252,8 @@ def declare(lib):
                                                 c_double_p, c_double_p, c_double_p]),
         "ovgpu_state_marginalize": (C.c_int, [ctxp, C.c_int32, C.c_int32]),
         "ovgpu_state_marginalize_batched": (C.c_int, [ctxp, C.c_int32, c_int32_p, c_int32_p]),
+        "ovgpu_slam_update_chunked": (C.c_int, [ctxp, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                C.POINTER(UpdateStats)]),
         "ovgpu_state_augment_clone": (C.c_int, [ctxp, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_int32_p]),
         "ovgpu_state_propagate": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p]),
         "ovgpu_state_dims": (C.c_int, [ctxp, c_int32_p, c_int32_p]),

@@ -136,6 +136,14 @@ struct ovgpu_ctx {
   // lists behind them; the record arrays' second buffers (each swaps with its array, as Ppad does with P)
   DevBuf<int32_t> marg_tab, lm_anchor_b, lm_repd_b;
   DevBuf<double> clone_qp_b, clone_fej_b, lm_val_b, lm_fej_b;
+  // ovgpu_slam_update_chunked (k_slam_chunks.h): the call's integer table (chunk_first | every chunk's sorted column set | lm_index | every chunk's
+  // feature order) and row offsets from the host, the rebased meas_offsets the device writes, the per-chunk results (dx rows, flag words | gate
+  // counters) and the entry state kept aside for the restore-and-chain path
+  DevBuf<int32_t> chk_tab, chk_offs, chk_flags;
+  DevBuf<int64_t> chk_rowoff;
+  DevBuf<double> chk_dx, chk_save;
+  int chunk_fail_inject = -1;   // ovgpu_debug_option "slam_chunked_fail_chunk": this chunk's flag word reads as failed after the pass (one-shot; tests of the restore-and-chain path)
+  int64_t chunk_fallbacks = 0;  // ovgpu_debug_option "slam_chunked_fallbacks": how often ovgpu_slam_update_chunked put the entry state back and ran the chain
   // SLAM landmarks (ovgpu_set_landmarks); L > 0 switches the per-feature kernel to the UpdaterSLAM rules
   int L = 0;
   // the resident landmarks' representations, one each (Landmark::_feat_representation: StateOptions::feat_rep_slam, or feat_rep_aruco for

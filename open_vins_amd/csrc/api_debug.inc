@@ -5,6 +5,12 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   if (n == "chol_follow_spin_limit") {
     if (old_value) *old_value = c->chol_spin_limit;
     if (value >= 0) c->chol_spin_limit = (int)std::min<int64_t>(value, 1 << 30);
+  } else if (n == "slam_chunked_fail_chunk") { // k >= 0: the next ovgpu_slam_update_chunked reads chunk k's flag word as failed after its pass and takes the restore-and-chain path (one-shot)
+    if (old_value) *old_value = c->chunk_fail_inject;
+    c->chunk_fail_inject = value >= 0 ? (int)std::min<int64_t>(value, 1 << 20) : -1;
+  } else if (n == "slam_chunked_fallbacks") { // reads the count of restore-and-chain passes; a value >= 0 sets it
+    if (old_value) *old_value = c->chunk_fallbacks;
+    if (value >= 0) c->chunk_fallbacks = value;
   } else if (n == "gram_interleaved") {
     if (old_value) *old_value = c->gram_il ? 1 : 0;
     if (value >= 0) c->gram_il = value != 0;

@@ -168,6 +168,335 @@ int ovgpu_slam_compress(ovgpu_ctx *c, const int32_t *lm_index, int32_t *feat_sta
 }
 
 // ---------------------------------------------------------------------------
+// ovgpu_slam_update_chunked: the chunks of one frame's UpdaterSLAM::update (VioManager.cpp:529-547 calls it once per max_slam_in_update
+// features, chunk k + 1 linearised at the state chunk k left) in ONE device pass.  The chain of ovgpu_set_active_landmarks /
+// ovgpu_set_features / ovgpu_slam_update pays per chunk a host walk of the columns, the batch's uploads, a blocking upload of lm_index and a
+// read-back with its synchronisation; none of it is needed between chunks: the batch, the indices and every chunk's column set are known up
+// front, the host sizes follow from the integer structure, and nothing a gate decides changes what is enqueued next.  Here: one upload (the
+// chunk table, every chunk's column set in column order, lm_index, the feature orders and row offsets), per chunk a VIEW of the resident
+// batch (BatchView below: sizes and host mirrors of the chunk, the device arrays at the chunk's offset — so a chunk's per-feature outputs
+// land at its place in the whole-batch arrays — the rebased offsets of k_chunk_offsets) under which the single call's own enqueue functions
+// run unchanged, k_chunk_collect behind each (k_slam_chunks.h), one gather and one synchronisation at the end.
+// ---------------------------------------------------------------------------
+namespace {
+struct ChunkPlan {
+  int n = 0, F = 0;
+  std::vector<int32_t> first, act_off, act, D, order; // act: the chunks' column sets, concatenated, each in covariance order; order: by descending track length, per chunk
+  std::vector<int64_t> row_off;                       // per chunk F_k + 1 entries, at first[k] + k
+  std::vector<int32_t> tab;                           // first | act | lm_index | order, as uploaded
+  size_t o_act = 0, o_lm = 0, o_order = 0;
+  int D_max = 0, m_max = 0;
+  int64_t rows_max = 0;
+};
+// what a chunk's view replaces in the context
+struct BatchView {
+  int F, M, m_max;
+  int64_t rows_total;
+  std::vector<int32_t> h_offsets, h_order, h_feat_lm;
+  std::vector<int64_t> h_row_off;
+  bool have_sigma, have_mult, timing;
+  int32_t *meas_offsets, *sys_order, *status;
+  uint16_t *meas_cc;
+  float *uv, *uvn;
+  int64_t *row_off;
+  double *pA, *pG, *chi2, *chi2_thr, *feat_sigma, *feat_mult;
+  void save(ovgpu_ctx *c) {
+    F = c->F, M = c->M, m_max = c->m_max, rows_total = c->rows_total;
+    h_offsets = c->h_offsets, h_order = c->h_order, h_feat_lm = c->h_feat_lm, h_row_off = c->h_row_off;
+    have_sigma = c->have_feat_sigma, have_mult = c->have_feat_mult, timing = c->timing;
+    meas_offsets = c->meas_offsets.p, sys_order = c->sys_order.p, status = c->status.p, meas_cc = c->meas_cc.p, uv = c->uv.p, uvn = c->uvn.p;
+    row_off = c->row_off.p, pA = c->pA.p, pG = c->pG.p, chi2 = c->chi2.p, chi2_thr = c->chi2_thr.p, feat_sigma = c->feat_sigma.p, feat_mult = c->feat_mult.p;
+  }
+  void restore(ovgpu_ctx *c) const {
+    c->F = F, c->M = M, c->m_max = m_max, c->rows_total = rows_total;
+    c->h_offsets = h_offsets, c->h_order = h_order, c->h_feat_lm = h_feat_lm, c->h_row_off = h_row_off;
+    c->have_feat_sigma = have_sigma, c->have_feat_mult = have_mult, c->timing = timing;
+    c->meas_offsets.p = meas_offsets, c->sys_order.p = sys_order, c->status.p = status, c->meas_cc.p = meas_cc, c->uv.p = uv, c->uvn.p = uvn;
+    c->row_off.p = row_off, c->pA.p = pA, c->pG.p = pG, c->chi2.p = chi2, c->chi2_thr.p = chi2_thr, c->feat_sigma.p = feat_sigma, c->feat_mult.p = feat_mult;
+  }
+};
+} // namespace
+
+// Chunk k on the stream at the state the launches before it leave: the column map of its landmarks (k_active_columns on the resident set), the
+// view, the single call's gather / pipeline / landmark update, its results into slot k.  No upload, no wait.
+static int enqueue_chunk(ovgpu_ctx *c, const ChunkPlan &pl, const BatchView &w, int k) {
+  const int f0 = pl.first[k], Fk = pl.first[k + 1] - f0;
+  if (Fk == 0) return OVGPU_OK; // an empty chunk does nothing (its dx row and flag words were zeroed with the others)
+  hipStream_t s = c->stream;
+  c->active_given = true;
+  c->h_lm_active.assign(c->L, 0);
+  for (int i = pl.act_off[k]; i < pl.act_off[k + 1]; i++) c->h_lm_active[pl.act[i]] = 1;
+  int rc = layout_columns(c, false, c->chk_tab.p + pl.o_act + pl.act_off[k]);
+  if (rc != OVGPU_OK) return rc;
+  if (c->cols_over || c->D != pl.D[k]) return set_err(OVGPU_ERR_INVALID, "internal: a chunk's column count differs from the plan's");
+  // ---- the view
+  const int m0 = w.h_offsets[f0];
+  c->F = Fk, c->M = w.h_offsets[f0 + Fk] - m0;
+  c->h_offsets.resize(Fk + 1);
+  int m_max = 0;
+  for (int i = 0; i <= Fk; i++) c->h_offsets[i] = w.h_offsets[f0 + i] - m0;
+  for (int i = 0; i < Fk; i++) m_max = std::max(m_max, c->h_offsets[i + 1] - c->h_offsets[i]);
+  c->m_max = m_max;
+  c->h_order.assign(pl.order.begin() + f0, pl.order.begin() + f0 + Fk);
+  c->h_feat_lm.assign(pl.tab.begin() + pl.o_lm + f0, pl.tab.begin() + pl.o_lm + f0 + Fk);
+  c->meas_offsets.p = c->chk_offs.p + f0 + k, c->sys_order.p = c->chk_tab.p + pl.o_order + f0, c->row_off.p = c->chk_rowoff.p + f0 + k;
+  c->meas_cc.p = w.meas_cc + m0, c->uv.p = w.uv + 2 * (size_t)m0, c->uvn.p = w.uvn + 2 * (size_t)m0;
+  c->status.p = w.status + f0, c->chi2.p = w.chi2 + f0, c->chi2_thr.p = w.chi2_thr + f0, c->pA.p = w.pA + 3 * (size_t)f0, c->pG.p = w.pG + 3 * (size_t)f0;
+  c->have_feat_sigma = w.have_sigma, c->have_feat_mult = w.have_mult;
+  c->feat_sigma.p = w.have_sigma ? w.feat_sigma + f0 : w.feat_sigma, c->feat_mult.p = w.have_mult ? w.feat_mult + f0 : w.feat_mult;
+  if ((rc = set_row_layout(c, true, false, true)) != OVGPU_OK) return rc;
+  for (int i = 0; i <= Fk; i++)
+    if (c->h_row_off[i] != pl.row_off[(size_t)f0 + k + i]) return set_err(OVGPU_ERR_INVALID, "internal: a chunk's row layout differs from the plan's");
+  c->have_feats = true, c->given_tri = true;
+  // ---- the single call's launches
+  hipLaunchKernelGGL(k_slam_gather, dim3((Fk + 255) / 256), dim3(256), 0, s, Fk, (const int32_t *)(c->chk_tab.p + pl.o_lm + f0), (const int32_t *)c->meas_offsets.p,
+                     landmark_store(c), c->pG.p, c->pA.p, c->pFej.p, c->feat_lm.p, c->feat_lmcol.p, c->feat_lmcov.p, c->feat_anchor.p, c->given_status.p);
+  HIPCHK(hipGetLastError());
+  if ((rc = enqueue_pipeline(c, STAGE_LOCAL | STAGE_EKF, true)) != OVGPU_OK) return rc;
+  hipLaunchKernelGGL(k_landmark_update, dim3((3 * c->L + 255) / 256), dim3(256), 0, s, c->L, (const int32_t *)nullptr, (const int32_t *)c->lm_repd.p, c->dx.p,
+                     c->lm_cov.p, c->lm_val.p, (const int32_t *)nullptr);
+  ChunkCollect cc;
+  cc.N = c->N, cc.dx = c->dx.p, cc.flags = c->flags.p, cc.gate = c->rows_used.p + 1;
+  cc.dx_row = c->chk_dx.p + (size_t)k * c->N, cc.flags_out = c->chk_flags.p + 4 * k, cc.gate_out = c->chk_flags.p + 4 * pl.n + k;
+  hipLaunchKernelGGL(k_chunk_collect, dim3((std::max(c->N, 5) + 255) / 256), dim3(256), 0, s, cc);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+static int chunk_state_copy(ovgpu_ctx *c, bool put_back) {
+  const int C = c->C, K = c->K, L = c->L;
+  const size_t N = (size_t)c->N;
+  double *sv = c->chk_save.p;
+  double *live[CHUNK_COPY_SEGS] = {c->P.p, c->clone_qp.p, c->calib_qp.p, c->intr.p, c->lm_val.p};
+  const size_t len[CHUNK_COPY_SEGS] = {N * N, (size_t)7 * C, (size_t)7 * K, (size_t)8 * K, (size_t)3 * L};
+  ChunkCopy q;
+  size_t off = 0;
+  for (int i = 0; i < CHUNK_COPY_SEGS; i++) {
+    q.dst[i] = put_back ? live[i] : sv + off, q.src[i] = put_back ? sv + off : live[i], q.n[i] = (uint32_t)len[i];
+    off += len[i];
+  }
+  hipLaunchKernelGGL(k_chunk_copy, dim3(UP_BLOCKS, CHUNK_COPY_SEGS), dim3(256), 0, c->stream, q);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chunk_first, const int32_t *lm_index, int32_t *feat_status, double *chi2,
+                              double *chi2_thresh, double *dx_seq, double *P_out, double *lm_out, ovgpu_update_stats *stats) {
+  // ---- every check, before anything changes
+  if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
+  if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state was never called");
+  if (c->L <= 0) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_landmarks was never called");
+  if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features must follow ovgpu_set_landmarks");
+  if (n_chunks < 1 || n_chunks > 4096 || !chunk_first) return set_err(OVGPU_ERR_INVALID, "null chunk_first or no chunk");
+  const int F = c->F, n = n_chunks, N = c->N, L = c->L;
+  if (chunk_first[0] != 0 || chunk_first[n] != F) return set_err(OVGPU_ERR_INVALID, "chunk_first must span [0, F]");
+  for (int k = 0; k < n; k++)
+    if (chunk_first[k + 1] < chunk_first[k]) return set_err(OVGPU_ERR_INVALID, "chunk_first not monotone");
+  if (F > 0 && !lm_index) return set_err(OVGPU_ERR_INVALID, "null lm_index");
+  for (int f = 0; f < F; f++)
+    if (lm_index[f] < 0 || lm_index[f] >= L) return set_err(OVGPU_ERR_INVALID, "lm_index out of range");
+  ChunkPlan pl;
+  pl.n = n, pl.F = F;
+  pl.first.assign(chunk_first, chunk_first + n + 1);
+  pl.act_off.assign(n + 1, 0), pl.D.assign(n, 0), pl.order.assign(std::max(F, 1), 0), pl.row_off.assign((size_t)F + n, 0);
+  {
+    int D_fixed = 0;
+    for (const auto &v : c->h_sorted) D_fixed += v.kind != COL_LANDMARK ? v.size : 0;
+    std::vector<uint8_t> on(L);
+    std::vector<int32_t> start;
+    for (int k = 0; k < n; k++) {
+      const int f0 = pl.first[k], Fk = pl.first[k + 1] - f0;
+      std::fill(on.begin(), on.end(), 0);
+      for (int f = f0; f < f0 + Fk; f++) on[lm_index[f]] = 1;
+      int D = D_fixed, n_act = 0; // layout_columns' walk: the set in covariance order
+      for (const auto &v : c->h_sorted)
+        if (v.kind == COL_LANDMARK && on[v.index]) pl.act.push_back(v.index), D += v.size, n_act++;
+      pl.act_off[k + 1] = (int32_t)pl.act.size(), pl.D[k] = D;
+      if (D + 1 > 512)
+        return set_err(OVGPU_ERR_CAPACITY, "chunk " + std::to_string(k) + ": its " + std::to_string(n_act) + " landmarks give " + std::to_string(D) + " Jacobian columns, more than 511");
+      pl.D_max = std::max(pl.D_max, D);
+      // rows (set_row_layout's rule with the landmarks named) and the order of k_system's slots (begin_feature_batch's counting sort), chunk-local
+      int mk = 0;
+      int64_t *ro = pl.row_off.data() + f0 + k;
+      for (int i = 0; i < Fk; i++) {
+        const int m = c->h_offsets[f0 + i + 1] - c->h_offsets[f0 + i], proj = 3 - lm_dof(c->h_lm_rep[lm_index[f0 + i]]);
+        ro[i + 1] = ro[i] + (2 * m > proj ? 2 * m - proj : 0);
+        mk = std::max(mk, m);
+      }
+      pl.rows_max = std::max(pl.rows_max, ro[Fk]), pl.m_max = std::max(pl.m_max, mk);
+      start.assign(mk + 2, 0);
+      for (int i = 0; i < Fk; i++) start[mk - (c->h_offsets[f0 + i + 1] - c->h_offsets[f0 + i]) + 1]++;
+      for (int b = 0; b <= mk; b++) start[b + 1] += start[b];
+      for (int i = 0; i < Fk; i++) pl.order[f0 + start[mk - (c->h_offsets[f0 + i + 1] - c->h_offsets[f0 + i])]++] = i;
+    }
+  }
+  { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }
+  HIPCHK(hipSetDevice(c->device));
+  if (stats) std::memset(stats, 0, sizeof(*stats) * n);
+  hipStream_t s = c->stream;
+  // ---- workspaces for the largest chunk, before the first launch (a buffer that grew between two chunks would be freed under the launches)
+  {
+    const size_t Dm = (size_t)pl.D_max, LDm = Dm + 1, Fm = (size_t)std::max(F, 1), NTm = (LDm + 15) / 16;
+    HIPCHK(c->col_cov.reserve(511));
+    HIPCHK(c->col_kind.reserve(511));
+    HIPCHK(c->col_sub.reserve(511));
+    HIPCHK(c->col_var.reserve(511));
+    HIPCHK(c->Mt.reserve(Dm * N));
+    HIPCHK(c->Aaug.reserve(Dm * (Dm + N + 1)));
+    HIPCHK(c->Yaug.reserve(Dm * (Dm + N + 1)));
+    HIPCHK(c->Yaug2.reserve(Dm * (Dm + N + 1)));
+    {
+      const double *before = c->Lw.p;
+      HIPCHK(c->Lw.reserve(Dm * (Dm + 8)));
+      if (c->Lw.p != before) c->Lw_D = -1; // (its zeroed upper triangle went with the old buffer)
+    }
+    HIPCHK(c->gram_rho.reserve(std::max((size_t)N, Dm)));
+    HIPCHK(c->Hbig.reserve((size_t)std::max<int64_t>(pl.rows_max, 1) * LDm));
+    HIPCHK(c->gram_G.reserve(256 * NTm * NTm));
+    HIPCHK(c->gram_part.reserve((size_t)c->num_cu * (NTm * (NTm + 1) / 2) * 256));
+    HIPCHK(c->pFej.reserve(3 * Fm));
+    HIPCHK(c->feat_lm.reserve(Fm));
+    HIPCHK(c->feat_lmcol.reserve(Fm));
+    HIPCHK(c->feat_lmcov.reserve(Fm));
+    HIPCHK(c->feat_anchor.reserve(Fm));
+    HIPCHK(c->given_status.reserve(Fm));
+    HIPCHK(c->rows_used.reserve(2));
+    HIPCHK(c->chk_offs.reserve((size_t)F + n));
+    HIPCHK(c->chk_rowoff.reserve((size_t)F + n));
+    HIPCHK(c->chk_flags.reserve((size_t)5 * n));
+    HIPCHK(c->chk_dx.reserve((size_t)n * N));
+    HIPCHK(c->chk_save.reserve((size_t)N * N + 7 * (size_t)c->C + 15 * (size_t)c->K + 3 * (size_t)L));
+  }
+  // ---- one upload
+  pl.tab.assign(pl.first.begin(), pl.first.end());
+  pl.o_act = pl.tab.size(), pl.tab.insert(pl.tab.end(), pl.act.begin(), pl.act.end());
+  pl.o_lm = pl.tab.size(), pl.tab.insert(pl.tab.end(), lm_index, lm_index + F);
+  pl.o_order = pl.tab.size(), pl.tab.insert(pl.tab.end(), pl.order.begin(), pl.order.begin() + F);
+  HIPCHK(c->chk_tab.reserve(pl.tab.size()));
+  HIPCHK(upload_begin(c));
+  { const int rcv = upload_var_tab(c); if (rcv != OVGPU_OK) return rcv; }
+  HIPCHK(upload_deferred(c, c->chk_tab.p, pl.tab.data(), sizeof(int32_t) * pl.tab.size()));
+  HIPCHK(upload_deferred(c, c->chk_rowoff.p, pl.row_off.data(), sizeof(int64_t) * pl.row_off.size()));
+  HIPCHK(upload_fence(c, s));
+  hipLaunchKernelGGL(k_chunk_offsets, dim3((F + n + 255) / 256), dim3(256), 0, s, n, F, (const int32_t *)c->chk_tab.p, (const int32_t *)c->meas_offsets.p, c->chk_offs.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
+  HIPCHK(hipMemsetAsync(c->chk_dx.p, 0, sizeof(double) * (size_t)n * N, s));
+  int rc = chunk_state_copy(c, false); // the entry state, for the restore-and-chain path
+  if (rc != OVGPU_OK) return rc;
+  // ---- every chunk, one after the other on the stream
+  BatchView w;
+  w.save(c);
+  c->timing = false; // (no stage events inside the pass: six marker packets per chunk; ovgpu_update_stats::ms_* stay 0)
+  for (int k = 0; k < n && rc == OVGPU_OK; k++) rc = enqueue_chunk(c, pl, w, k);
+  // ---- one read-back
+  std::vector<int32_t> flags((size_t)5 * n, 0);
+  const size_t al = 63;
+  const size_t o_fl = 0, o_st = (sizeof(int32_t) * 5 * n + al) & ~al, o_c2 = (o_st + sizeof(int32_t) * F + al) & ~al, o_th = (o_c2 + sizeof(double) * F + al) & ~al;
+  const size_t o_dx = (o_th + sizeof(double) * F + al) & ~al, o_lm = (o_dx + sizeof(double) * (size_t)n * N + al) & ~al, o_P = (o_lm + sizeof(double) * 3 * L + al) & ~al;
+  const size_t o_end = o_P + sizeof(double) * (size_t)N * N;
+  auto gather = [&]() -> int {
+    HIPCHK(down_reserve(c, o_end));
+    HIPCHK(download_deferred(c, o_fl, c->chk_flags.p, sizeof(int32_t) * 5 * n));
+    if (F > 0) {
+      HIPCHK(download_deferred(c, o_st, w.status, sizeof(int32_t) * F));
+      if (chi2) HIPCHK(download_deferred(c, o_c2, w.chi2, sizeof(double) * F));
+      if (chi2_thresh) HIPCHK(download_deferred(c, o_th, w.chi2_thr, sizeof(double) * F));
+    }
+    if (dx_seq) HIPCHK(download_deferred(c, o_dx, c->chk_dx.p, sizeof(double) * (size_t)n * N));
+    if (lm_out) HIPCHK(download_deferred(c, o_lm, c->lm_val.p, sizeof(double) * 3 * L));
+    if (P_out) HIPCHK(download_deferred(c, o_P, c->P.p, sizeof(double) * (size_t)N * N));
+    HIPCHK(upload_sync(c, s)); // the ONE synchronisation of the call
+    std::memcpy(flags.data(), c->down_arena.p + o_fl, sizeof(int32_t) * 5 * n);
+    return OVGPU_OK;
+  };
+  // on return the active set in force is "all" and the batch is the whole batch as uploaded (the all-landmarks map leaves with the gather's launch)
+  auto leave = [&]() -> int {
+    w.restore(c);
+    c->h_feat_lm.assign(lm_index, lm_index + F);
+    c->active_given = false, c->h_lm_active.clear();
+    const int rcl = layout_columns(c); // (as ovgpu_set_active_landmarks(n < 0): the batch has to be handed over again before another update)
+    c->tri_readable = rcl == OVGPU_OK;
+    return rcl;
+  };
+  if (rc != OVGPU_OK) {
+    (void)leave();
+    (void)upload_sync(c, s);
+    return rc;
+  }
+  if ((rc = leave()) != OVGPU_OK) return rc;
+  if ((rc = gather()) != OVGPU_OK) return rc;
+  int k_done = n; // chunks whose results stand
+  int status = OVGPU_OK;
+  bool any = false;
+  for (int k = 0; k < n; k++) any = any || flags[4 * k] || flags[4 * k + 1] || flags[4 * k + 2];
+  if (c->chunk_fail_inject >= 0 && c->chunk_fail_inject < n) any = true;
+  c->chunk_fail_inject = -1;
+  if (any) {
+    // A chunk's flag word is set: a prior block that failed its pivot test (the single call repeats through the Householder route), a follower of
+    // the single-launch Cholesky that timed out (it repeats with the step-wise kernels), a negative diagonal (the chain stops there).  The chunks
+    // behind it ran on a state the chain would not have produced: the entry state comes back and the chunks run as the chain of single calls
+    // runs them, one synchronisation and update_with_fallbacks each.  Correct, slower and rare; counted.
+    c->chunk_fallbacks++;
+    if ((rc = chunk_state_copy(c, true)) != OVGPU_OK) return rc;
+    if ((rc = launch_build_tables(c)) != OVGPU_OK) return rc;
+    HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
+    HIPCHK(hipMemsetAsync(c->chk_dx.p, 0, sizeof(double) * (size_t)n * N, s));
+    w.save(c);
+    c->timing = false;
+    k_done = 0;
+    for (int k = 0; k < n && status == OVGPU_OK; k++) {
+      int32_t fl[4] = {0, 0, 0, 0};
+      status = update_with_fallbacks(c, nullptr, [&]() {
+        int rc2 = enqueue_chunk(c, pl, w, k);
+        if (rc2 != OVGPU_OK) return rc2;
+        if (hipMemcpyAsync(fl, c->chk_flags.p + 4 * k, sizeof(fl), hipMemcpyDeviceToHost, s) != hipSuccess || upload_sync(c, s) != hipSuccess)
+          return set_err(OVGPU_ERR_HIP, "read-back of a chunk's flag words failed");
+        c->chol_timed_out = fl[2] != 0;
+        if (fl[2]) return set_err(OVGPU_ERR_HIP, "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup; the state was not modified");
+        if (fl[0]) return set_err(OVGPU_ERR_NOT_SPD, "chunk " + std::to_string(k) + ": innovation covariance not SPD");
+        if (fl[1]) return set_err(OVGPU_ERR_NEGATIVE_DIAGONAL, "chunk " + std::to_string(k) + ": negative covariance diagonal after the update");
+        return (int)OVGPU_OK;
+      });
+      if (status == OVGPU_OK || status == OVGPU_ERR_NEGATIVE_DIAGONAL || status == OVGPU_ERR_NOT_SPD) k_done = k + 1;
+      if (stats && pl.first[k + 1] > pl.first[k]) stats[k].status = status;
+    }
+    const std::string msg = g_err;
+    if ((rc = leave()) != OVGPU_OK) return rc;
+    if ((rc = gather()) != OVGPU_OK) return rc;
+    if (status != OVGPU_OK) g_err = msg;
+  }
+  // ---- to the caller
+  {
+    const unsigned char *h = c->down_arena.p;
+    const double qnan = std::nan("");
+    const int32_t *st = reinterpret_cast<const int32_t *>(h + o_st);
+    const int Fd = pl.first[k_done];
+    if (feat_status && Fd > 0) std::memcpy(feat_status, st, sizeof(int32_t) * Fd);
+    if (chi2 && Fd > 0) std::memcpy(chi2, h + o_c2, sizeof(double) * Fd);
+    if (chi2_thresh && Fd > 0) std::memcpy(chi2_thresh, h + o_th, sizeof(double) * Fd);
+    for (int k = 0; k < k_done; k++) {
+      int n_used = 0;
+      int64_t rows = 0;
+      for (int f = pl.first[k]; f < pl.first[k + 1]; f++) {
+        if (st[f] == OVGPU_FEAT_USED) n_used++, rows += pl.row_off[(size_t)f + k + 1] - pl.row_off[(size_t)f + k];
+        if (st[f] != OVGPU_FEAT_USED && st[f] != OVGPU_FEAT_CHI2_REJECTED) { // the gate is only reached by features with rows
+          if (chi2) chi2[f] = qnan;
+          if (chi2_thresh) chi2_thresh[f] = qnan;
+        }
+      }
+      if (stats && pl.first[k + 1] > pl.first[k])
+        stats[k].n_used = n_used, stats[k].n_rows = (int32_t)rows, stats[k].D = pl.D[k], stats[k].n_rows_comp = rows > 0 ? pl.D[k] : 0, stats[k].n_gate_bound = flags[(size_t)4 * n + k];
+    }
+    if (dx_seq) std::memcpy(dx_seq, h + o_dx, sizeof(double) * (size_t)n * N);
+    if (lm_out) std::memcpy(lm_out, h + o_lm, sizeof(double) * 3 * L);
+    if (P_out) std::memcpy(P_out, h + o_P, sizeof(double) * (size_t)N * N);
+  }
+  if (status != OVGPU_OK) return status;
+  return check_tree_error(c);
+}
+
+// ---------------------------------------------------------------------------
 // UpdaterSLAM::delayed_init (UpdaterSLAM.cpp:61-251): a chain of StateHelper::initialize calls, one feature after the
 // other on the stream, no host round trip in between.  The covariance is padded to its final capacity N + 3F up front
 // (the rows / columns of landmarks that do not exist yet are zero, which every kernel of the update treats exactly), the

@@ -124,6 +124,7 @@ void ovgpu_destroy(ovgpu_ctx *c) {
   c->feat_anchor.release(), c->lm_col.release(), c->lm_anchor.release(), c->lm_index.release(), c->Ppad.release(), c->init_ws.release(), c->dx_seq.release();
   c->init_ctr.release(), c->feat_slot.release(), c->prop_w.release(), c->prop_in.release(), c->prop_ids.release();
   c->anc_tab.release(), c->anc_ids.release(), c->anc_phi.release(), c->anc_w.release();
+  c->chk_tab.release(), c->chk_offs.release(), c->chk_flags.release(), c->chk_rowoff.release(), c->chk_dx.release(), c->chk_save.release();
   c->marg_tab.release(), c->lm_anchor_b.release(), c->lm_repd_b.release(), c->clone_qp_b.release(), c->clone_fej_b.release(), c->lm_val_b.release(), c->lm_fej_b.release();
   c->trk_count.release(), c->trk_cam.release(), c->trk_slot_in.release(), c->trk_cam_in.release(), c->trk_sel.release(), c->trk_nvalid.release(), c->trk_flag.release();
   c->trk_time.release(), c->trk_clone_times.release(), c->trk_aux.release(), c->trk_uv.release(), c->trk_uvn.release(), c->trk_uv_in.release(), c->trk_uvn_in.release();
@@ -185,7 +186,7 @@ static int launch_build_tables(ovgpu_ctx *c) {
 // covariance id.  build_columns sorts the resident variables (ovgpu_set_state, ovgpu_set_landmarks and every structural change of the
 // state); layout_columns lays the columns out over that sorted list for the active landmark set (ovgpu_set_active_landmarks: a linear
 // walk, no sort) or, without one, for every resident landmark.
-static int layout_columns(ovgpu_ctx *c, bool defer_flush = false);
+static int layout_columns(ovgpu_ctx *c, bool defer_flush = false, const int32_t *resident_set = nullptr);
 static int build_columns(ovgpu_ctx *c, bool defer_flush = false) {
   std::vector<ovgpu_ctx::HVar> vars = c->h_vars;
   for (int l = 0; l < c->L; l++) vars.push_back({c->h_lm_cov[l], lm_dof(c->h_lm_rep[l]), COL_LANDMARK, l});
@@ -201,7 +202,7 @@ static int build_columns(ovgpu_ctx *c, bool defer_flush = false) {
 // (the uploads are flushed HERE whatever the caller's defer_flush says: the kernel reads them; ovgpu_set_state, the one caller that defers, has no set)
 // the device builds the tables of an active set itself, in one launch behind the two small uploads (k_active_columns, k_slam.h); the host's walk
 // in layout_columns is the mirror that sizes the workspaces and nobody waits for the device
-static int enqueue_active_columns(ovgpu_ctx *c, const std::vector<int32_t> &active_idx, int D) {
+static int upload_var_tab(ovgpu_ctx *c) {
   const int V = (int)c->h_sorted.size();
   if (!c->var_tab_ok) {
     std::vector<int32_t> tab((size_t)4 * std::max(V, 1), 0);
@@ -210,13 +211,23 @@ static int enqueue_active_columns(ovgpu_ctx *c, const std::vector<int32_t> &acti
     HIPCHK(upload_deferred(c, c->var_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
     c->var_tab_ok = true;
   }
-  HIPCHK(c->active_idx.reserve(std::max<size_t>(active_idx.size(), 1)));
-  HIPCHK(upload_deferred(c, c->active_idx.p, active_idx.data(), sizeof(int32_t) * active_idx.size()));
+  return OVGPU_OK;
+}
+// `resident`: the set is on the device already, n_active indices (ovgpu_slam_update_chunked uploads every chunk's set and the variable table in
+// front of its first chunk); otherwise the set is uploaded here, behind the variable table if that is stale
+static int enqueue_active_columns(ovgpu_ctx *c, const std::vector<int32_t> &active_idx, int D, const int32_t *resident = nullptr) {
+  const int V = (int)c->h_sorted.size();
+  if (!resident) {
+    const int rcv = upload_var_tab(c);
+    if (rcv != OVGPU_OK) return rcv;
+    HIPCHK(c->active_idx.reserve(std::max<size_t>(active_idx.size(), 1)));
+    HIPCHK(upload_deferred(c, c->active_idx.p, active_idx.data(), sizeof(int32_t) * active_idx.size()));
+  }
   HIPCHK(upload_fence(c, c->stream));
   HIPCHK(c->lm_col.reserve(std::max(c->L, 1)));
   ActiveColsParams ap;
   ap.V = V, ap.L = c->L, ap.C = c->C, ap.K = c->K, ap.n_active = (int)active_idx.size(), ap.Dcap = D;
-  ap.vars = c->var_tab.p, ap.active_idx = c->active_idx.p;
+  ap.vars = c->var_tab.p, ap.active_idx = resident ? resident : c->active_idx.p;
   ap.clone_col = c->clone_col.p, ap.calib_col = c->calib_col.p, ap.intr_col = c->intr_col.p, ap.lm_col = c->lm_col.p, ap.col_cov = c->col_cov.p;
   ap.col_kind = c->col_kind.p, ap.col_sub = c->col_sub.p, ap.col_var = c->col_var.p;
   hipLaunchKernelGGL(k_active_columns, dim3(1), dim3(64), (size_t)((c->L + 15) & ~15), c->stream, ap);
@@ -224,7 +235,7 @@ static int enqueue_active_columns(ovgpu_ctx *c, const std::vector<int32_t> &acti
   return OVGPU_OK;
 }
 
-static int layout_columns(ovgpu_ctx *c, bool defer_flush) {
+static int layout_columns(ovgpu_ctx *c, bool defer_flush, const int32_t *resident_set) {
   const std::vector<ovgpu_ctx::HVar> &vars = c->h_sorted;
   const int C = c->C, K = c->K, N = c->N;
   const bool act = c->active_given;
@@ -301,7 +312,7 @@ static int layout_columns(ovgpu_ctx *c, bool defer_flush) {
   hipStream_t s = c->stream;
   (void)s;
   if (act) { // tables of an active set: built on the device
-    const int rca = enqueue_active_columns(c, active_idx, D);
+    const int rca = enqueue_active_columns(c, active_idx, D, resident_set); // (resident_set lists the set in this walk's order)
     if (rca != OVGPU_OK) return rca;
     if (!defer_flush) HIPCHK(upload_fence(c, c->stream));
   } else {
@@ -521,7 +532,8 @@ static int enqueue_batch_tables(ovgpu_ctx *c, bool anchors) { return enqueue_bat
 // Row layout of the stacked system for the uploaded tracks, the per-feature kernel's LDS carve and the TSQR leaf layout.
 //   MSCKF / delayed init: 2m - 3 rows per feature after the nullspace projection (UpdaterHelper.cpp:449-450);
 //   SLAM update: all 2m rows (UpdaterSLAM.cpp:381-383).
-static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false) {
+// host_only (ovgpu_slam_update_chunked): sizes, carve and workspaces alone — the row offsets are on the device already and the batch's tables stay
+static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bool host_only = false) {
   const int F = c->F;
   const int udof = lm_uniform_dof(c);
   std::vector<int64_t> row_off(F + 1, 0);
@@ -626,6 +638,7 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false) {
   // ---- stacked system and TSQR accumulators
   const int rct = configure_tsqr(c);
   if (rct != OVGPU_OK) return rct;
+  if (host_only) return OVGPU_OK;
   HIPCHK(c->row_off.reserve(F + 1));
   HIPCHK(upload_deferred(c, c->row_off.p, row_off.data(), sizeof(int64_t) * (F + 1)));
   // everything ovgpu_set_features packed into the arena (offsets, packed codes, pixel coordinates, the slot records and row offsets above)

@@ -22,6 +22,7 @@
 #include "k_tsqr_pw.h"
 #include "k_ekf.h"
 #include "k_slam.h"
+#include "k_slam_chunks.h"
 #include "k_tracks.h"
 #include "k_featy.h"
 #include "k_featy_big.h"

@@ -221,6 +221,33 @@ class UpdaterMSCKF:
         out["stats"] = stats.as_dict()
         return out
 
+    def slam_update_chunked(self, lm_index=None, chunk_first=None):
+        """Every chunk of the frame's SLAM update in one device pass (ovgpu_slam_update_chunked): the uploaded batch is the whole frame's, chunk k is
+        the features chunk_first[k] .. chunk_first[k + 1] (default: one chunk).  Returns the per-feature arrays of the whole batch, dx_seq
+        [n_chunks, N], the final P and landmarks, and one stats dict per chunk.  Afterwards every resident landmark has its columns again."""
+        v = self._views
+        F, N = self.F, self.N
+        lm_index = v.lm_index if lm_index is None else lm_index
+        lm_index = np.ascontiguousarray(lm_index, dtype=np.int32).reshape(-1)
+        first = np.ascontiguousarray([0, F] if chunk_first is None else chunk_first, dtype=np.int32).reshape(-1)
+        if lm_index.shape[0] != F:
+            raise ValueError("lm_index must name one landmark per uploaded feature")
+        if first.shape[0] < 2:
+            raise ValueError("chunk_first needs n_chunks + 1 entries")
+        n = int(first.shape[0]) - 1
+        Lc = C.c_int32(0)
+        capi.check(self.lib.ovgpu_get_landmarks(self._ctx, C.byref(Lc), None, None, None, None, None), "ovgpu_get_landmarks")
+        L = Lc.value
+        out = dict(feat_status=np.zeros(F, np.int32), chi2=np.zeros(F), chi2_thresh=np.zeros(F), dx_seq=np.zeros((n, N)), P=np.zeros((N, N)),
+                   landmarks=np.zeros((L, 3)))
+        stats = (capi.UpdateStats * n)()
+        rc = self.lib.ovgpu_slam_update_chunked(self._ctx, n, _ip(first), _ip(lm_index), _ip(out["feat_status"]), _dp(out["chi2"]),
+                                                _dp(out["chi2_thresh"]), _dp(out["dx_seq"]), _dp(out["P"]), _dp(out["landmarks"]), stats)
+        out["rc"] = rc
+        capi.check(rc, "ovgpu_slam_update_chunked")
+        out["stats"] = [st.as_dict() for st in stats]
+        return out
+
     def slam_compress(self):
         """Mode A of the SLAM update: the compressed (H, r) incl. the landmark columns."""
         v = self._views
