@@ -84,6 +84,8 @@ extern "C" {
 /*      reference in C / C++, hasattr in Python), not by the ABI number.        */
 /*      Likewise ovgpu_slam_update_chunked (every chunk of a frame's SLAM        */
 /*      update in one device pass): a new symbol under the same number.          */
+/*      Likewise ovgpu_msckf_update_lm (the MSCKF update of a state whose        */
+/*      resident landmarks stay current, on the landmark-free state's kernels). */
 /* ------------------------------------------------------------------------- */
 #define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
@@ -395,6 +397,43 @@ int ovgpu_set_triangulation(ovgpu_ctx *ctx, const double *p_FinA, const double *
 int ovgpu_msckf_update(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2,
                        double *chi2_thresh, double *p_FinG, double *dx,
                        double *P_out, ovgpu_update_stats *stats);
+
+/* UpdaterMSCKF::update (VioManager.cpp:525) on a state that carries SLAM landmarks, in the resident
+ * frame loop: ovgpu_msckf_update with the landmarks kept current on the device.  It replaces, for
+ * such a state, the update itself (UpdaterMSCKF.cpp:144-283: an MSCKF feature has no landmark
+ * column), StateHelper::EKFUpdate's walk over the state's variables (StateHelper.cpp:188-196) where
+ * it reaches the landmarks, and Landmark::update (Landmark.h:55-62, Landmark.cpp:130-140) — which a
+ * caller of ovgpu_msckf_update has to do on the host from dx, followed by ovgpu_set_landmarks.
+ * ORDER: ovgpu_set_state, ovgpu_set_landmarks, ovgpu_set_active_landmarks(ctx, NULL, 0) — no
+ * landmark has a Jacobian column —, ovgpu_set_features with the MSCKF batch, this call.
+ *   feat_status, chi2, chi2_thresh, p_FinG, dx, P_out, stats   as ovgpu_msckf_update; dx and P_out
+ *                       cover all N rows, the landmarks' among them
+ *   lm_out      [3*L]   the corrected landmark values (NULL ok); arrives with the same single
+ *                       synchronisation as dx and P_out
+ * The update is UpdaterMSCKF::update over the calibration and clone columns.  Every resident
+ * landmark value is then corrected on the device, in the same stream pass: value += dx[id .. id +
+ * dof), a single-depth landmark's LAST stored value takes dx[id].  FEJ values, anchors and
+ * representations stay.  Afterwards the landmarks are resident and current: a following SLAM call
+ * needs ovgpu_set_active_landmarks and its batch, not ovgpu_set_landmarks.
+ * The correction is predicated on the device exactly as the box-plus of the clones is, through the
+ * fall-backs of ovgpu_msckf_update (Householder route after a prior block that is not positive
+ * definite, step-wise Cholesky after a follower's time-out): an update the device skipped leaves the
+ * landmarks untouched, the repeat corrects them once, and on an error return the landmarks are in
+ * the state the clones are in.
+ * ROUTE: with a global MSCKF representation, no per-feature sigma / multiplier and tracks within
+ * the fused kernels' limits the call runs what a landmark-free state of the same N runs — rows laid
+ * out once, when the batch is handed over under the empty set; the one-kernel-per-feature path; the
+ * Gram-form update; the prior block's factorisation started by ovgpu_set_features on the second
+ * stream — and returns that state's bits.  Otherwise it takes the general per-feature kernel as
+ * ovgpu_msckf_update does, and corrects the landmarks all the same.  ovgpu_msckf_update on the
+ * same context keeps the general kernel.
+ * With L == 0 the call IS ovgpu_msckf_update.  Every check runs before anything changes:
+ * OVGPU_ERR_NO_STATE (no state, no batch); OVGPU_ERR_INVALID when landmarks are resident and the
+ * batch was laid out under a non-empty active set (the message names the calls to make).
+ * Not in every libovgpu.so that reports ABI 10: resolve it by symbol.                          */
+int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, double *chi2_thresh,
+                          double *p_FinG, double *dx, double *P_out, double *lm_out,
+                          ovgpu_update_stats *stats);
 
 /* Mode A (strict drop-in): same pipeline up to and including
  * UpdaterHelper::measurement_compress_inplace (UpdaterHelper.cpp:456-487) and
@@ -1099,6 +1138,7 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             (ovgpu_msckf_compress), the fp32 variant, the Householder route and batches assembled by ovgpu_tracks_to_features
  *                             always stack projected rows.  ("raw_work_const": the region work model's constant; 2: one region, developer experiments)
  *   "last_stack_raw"          (read only) the last pipeline's Gram matrix came from the unprojected stack
+ *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one
  *   "raw_gram_tile_rows"      (read only) rows x tiles summed over the regions of the resident batch: the 16 x 16 products per row k_gram_regions executes
  *   "speculative_prior"       (round 6, default 1) ovgpu_set_features starts the prior block's factorisation on the second stream, next to its own
  *                             uploads; the update joins it.  0: the factorisation starts with the update (round 5)

@@ -220,6 +220,8 @@ def declare(lib):
         "ovgpu_set_triangulation": (C.c_int, [ctxp, c_double_p, c_double_p, c_int32_p, c_int32_p]),
         "ovgpu_msckf_update": (C.c_int, [ctxp, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                          C.POINTER(UpdateStats)]),
+        "ovgpu_msckf_update_lm": (C.c_int, [ctxp, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                            C.POINTER(UpdateStats)]),
         "ovgpu_msckf_compress": (C.c_int, [ctxp, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p,
                                            c_int32_p, c_double_p, c_double_p, C.POINTER(UpdateStats)]),
         "ovgpu_get_state": (C.c_int, [ctxp, c_double_p, c_double_p, c_double_p, c_double_p]),

@@ -164,6 +164,12 @@ struct ovgpu_ctx {
   bool cols_over = false;            // the column set asked for has more than 511 columns: no landmark has a column and the SLAM entry points refuse
   std::string cols_over_msg;
   bool slam_rows = false; // row layout of the uploaded batch: 2m rows per feature (SLAM update) or 2m - 3 (MSCKF, delayed init)
+  // ovgpu_msckf_update_lm: resident landmarks that have NO column (the empty active set) are extra rows of P, as the IMU block is — the column map
+  // is a landmark-free state's and so is every kernel of the MSCKF update
+  bool lm_empty_set = false;      // L > 0 and ovgpu_set_active_landmarks(ctx, NULL, 0) holds (layout_columns)
+  bool lm_fast_ok = false;        // ... and the resident batch was laid out for the fused per-feature kernels under it (set_row_layout)
+  int last_feat_kernel = 0;       // per-feature kernel of the last batch pipeline: 0 the general one (k_system.h), else the fused shape that ran (feat_variant)
+  bool lm_fast_on = false;        // ovgpu_msckf_update_lm is running: the one entry that takes them with landmarks resident (enqueue_system)
   // device-resident FeatureDatabase (ovgpu_tracks_*)
   int trk_max = 0, trk_obs = 0;
   int trk_group_order = OVGPU_GROUPS_REFERENCE; // camera groups of an assembled batch (k_tracks.h, ovgpu_tracks_group_order)

@@ -69,6 +69,8 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = t;
   } else if (n == "stack_is_f32") { // read-only: the last pipeline stored the stack as floats and ran k_gram_f32 (options.gram_fp32)
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
+  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big
+    if (old_value) *old_value = c->last_feat_kernel;
   } else if (n == "chol_timeouts") { // read-only counter: updates repeated with the step-wise Cholesky after a follower timed out
     if (old_value) *old_value = c->chol_timeouts;
   } else {

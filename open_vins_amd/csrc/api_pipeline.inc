@@ -90,6 +90,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   // the one-pass fused kernels on a batch laid out by ovgpu_set_features, float64 stack.  Decided below, once the kernel shape is known.
   p.raw.on = 0;
   c->last_stack_raw = false;
+  if (f_one < 0) c->last_feat_kernel = 0;
   int grid = c->sys_grid;
   if (f_one < 0) HIPCHK(ctrl_zero(c, CTRL_ROWS, c->rows_used.p, 2 * sizeof(int32_t), c->stream));
   if (f_one >= 0) {
@@ -102,7 +103,10 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     grid = 1;
   }
   // the MSCKF fast path: whitened output, global representation, one noise level (k_feat.h)
-  if (p.Lw && c->feat_variant && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
+  // (with landmarks resident — the empty active set, set_row_layout — only for ovgpu_msckf_update_lm: every other entry keeps the general kernel)
+  if (p.Lw && c->feat_variant && (c->L == 0 || (c->lm_fast_on && c->lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
+    if (c->L > 0) p.row_stride = 48; // the fused kernels' records (fs_rows holds M * c->row_stride >= 48 M doubles): a 72-double stride that anchored landmarks or
+                                     // an earlier delayed initialisation left in the context is the general kernel's alone
     HIPCHK(c->feat_counter.reserve(1));
     HIPCHK(ctrl_zero(c, CTRL_COUNTER, c->feat_counter.p, sizeof(int32_t), c->stream));
     p.work_counter = c->feat_counter.p;
@@ -112,6 +116,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     const double *sr = st.rows, *sV = st.V;
     const int32_t *sm = st.minfo;
     if (c->featy_ok) {
+      if (f_one < 0) c->last_feat_kernel = c->feat_variant;
       // the fused form (k_featy.h): rows (clone-major) -> reflectors -> [prior block's factor L joins] -> sweep Y = H L once per feature:
       // projected rows to the stack, gate matrix as Y Y^T + s^2 I on the matrix cores, Cholesky, chi2
       static bool attr_y = false;
@@ -493,6 +498,8 @@ static int enqueue_ekf(ovgpu_ctx *c, const EkfJob &job = EkfJob()) {
   const int n = std::max(c->C, c->K);
   hipLaunchKernelGGL(k_boxplus, dim3((n + 255) / 256), dim3(256), 0, s, c->C, c->K, p.dx, c->clone_cov.p, c->calib_cov.p, c->intr_cov.p,
                      c->clone_qp.p, c->calib_qp.p, c->intr.p, job.pred);
+  if (c->lm_fast_on && c->L > 0) // ovgpu_msckf_update_lm on the Householder route (k_tail.h; p.pred is the box-plus's job.pred, p.pred_not is null)
+    hipLaunchKernelGGL(k_lm_correct, dim3((3 * c->L + 255) / 256), dim3(256), 0, s, p, c->L, (const int32_t *)c->lm_repd.p, (const int32_t *)c->lm_cov.p, c->lm_val.p);
   HIPCHK(hipGetLastError());
   return launch_build_tables(c);
 }
@@ -624,6 +631,8 @@ static int enqueue_ekf_gram(ovgpu_ctx *c, int part, bool side = false) {
     tt.tab_clone = c->tab_clone.p, tt.tab_cam = c->tab_cam.p, tt.tab_cc = c->tab_cc.p;
     const int nb = (tn * tn + 3) / 4;
     hipLaunchKernelGGL(k_tf_tail, dim3(nb + 1), dim3(256), 0, s, p, (const double *)c->Yaug.p, tt, nb);
+    if (c->lm_fast_on && c->L > 0) // ovgpu_msckf_update_lm: the resident landmarks follow dx (k_tail.h)
+      hipLaunchKernelGGL(k_lm_correct, dim3((3 * c->L + 255) / 256), dim3(256), 0, s, p, c->L, (const int32_t *)c->lm_repd.p, (const int32_t *)c->lm_cov.p, c->lm_val.p);
     HIPCHK(hipGetLastError());
     c->last_update_tform = true;
     return OVGPU_OK;
@@ -637,7 +646,9 @@ static int enqueue_speculative_prior(ovgpu_ctx *c) {
   if (!c->speculative_prior || c->prior_pending || !c->have_state || c->poses_only || c->D < 1) return OVGPU_OK;
   if (!(c->stream2 && c->ev_fork && c->ev_join && c->prior_overlap)) return OVGPU_OK;
   if (c->compress_gram != 1 || (c->D + 1 + 15) / 16 > gram::GR_NT_BLK || !c->whiten || !chol_pipe_usable(c, c->D)) return OVGPU_OK;
-  if (c->L != 0 || c->force_tsqr) return OVGPU_OK; // the update will not take the Gram route (need_prior, enqueue_pipeline_body): it would drop the factorisation and wait for it
+  // landmarks with columns: the batch is a SLAM call's, which would drop the factorisation and wait for it (need_prior, enqueue_pipeline_body).  Under the
+  // empty active set the batch is an MSCKF update's (ovgpu_msckf_update_lm, ovgpu_msckf_update): it joins the factorisation as a landmark-free state's does
+  if ((c->L != 0 && !c->lm_empty_set) || c->force_tsqr) return OVGPU_OK;
   const int rc = enqueue_ekf_gram(c, 1, true);
   if (rc != OVGPU_OK) return rc;
   // The update that follows would zero three more views of the control block one by one, each a launch of its own on its critical path (row
@@ -971,26 +982,30 @@ static int check_tree_error(ovgpu_ctx *c) {
   return OVGPU_OK;
 }
 
-static size_t finish_update_bytes(const ovgpu_ctx *c) {
+// with_lm: the resident landmark values land behind P' (ovgpu_msckf_update_lm)
+static size_t finish_update_bytes(const ovgpu_ctx *c, bool with_lm = false) {
   const size_t N = (size_t)c->N;
-  return 64 + ((sizeof(double) * N + 63) & ~(size_t)63) + sizeof(double) * N * N;
+  return 64 + ((sizeof(double) * N + 63) & ~(size_t)63) + ((sizeof(double) * N * N + 63) & ~(size_t)63) + (with_lm ? sizeof(double) * 3 * (size_t)c->L : 0);
 }
-static int finish_update(ovgpu_ctx *c, double *dx, double *P_out, ovgpu_update_stats *stats, const PendingFeatOut *pend = nullptr) {
+static int finish_update(ovgpu_ctx *c, double *dx, double *P_out, ovgpu_update_stats *stats, const PendingFeatOut *pend = nullptr, double *lm_out = nullptr) {
   hipStream_t s = c->stream;
   int32_t flags[4] = {0, 0, 0, 0};
   {
     const size_t base = (pend && pend->active) ? pend->end : 0; // behind the per-feature outputs still in flight
     const size_t N = (size_t)c->N, o_dx = base + 64, o_P = o_dx + ((sizeof(double) * N + 63) & ~(size_t)63);
-    HIPCHK(down_reserve(c, o_P + sizeof(double) * N * N)); // (no-op with `pend`: read_feature_outputs reserved both zones)
+    const size_t o_lm = o_P + ((sizeof(double) * N * N + 63) & ~(size_t)63), n_lm = (lm_out && c->L > 0) ? sizeof(double) * 3 * (size_t)c->L : 0;
+    HIPCHK(down_reserve(c, o_lm + n_lm)); // (no-op with `pend`: read_feature_outputs reserved both zones)
     HIPCHK(download_deferred(c, base, c->flags.p, sizeof(flags)));
     if (dx) HIPCHK(download_deferred(c, o_dx, c->dx.p, sizeof(double) * N));
     if (P_out) HIPCHK(download_deferred(c, o_P, c->P.p, sizeof(double) * N * N));
+    if (n_lm) HIPCHK(download_deferred(c, o_lm, c->lm_val.p, n_lm));
     HIPCHK(upload_sync(c, s)); // (one gather launch for everything deferred, then the synchronisation)
     unsigned char *h = c->down_arena.p;
     if (pend && pend->active) unpack_feature_outputs(c, *pend);
     std::memcpy(flags, h + base, sizeof(flags));
     if (dx) std::memcpy(dx, h + o_dx, sizeof(double) * N);
     if (P_out) std::memcpy(P_out, h + o_P, sizeof(double) * N * N);
+    if (n_lm) std::memcpy(lm_out, h + o_lm, n_lm);
   }
   int status = OVGPU_OK;
   if (flags[0]) status = OVGPU_ERR_NOT_SPD;
@@ -1044,6 +1059,32 @@ int ovgpu_msckf_update(ovgpu_ctx *c, int32_t *feat_status, double *chi2, double 
     if ((rc = read_feature_outputs(c, feat_status, chi2, chi2_thresh, p_FinG, stats, &pend, finish_update_bytes(c))) != OVGPU_OK) return rc;
     return finish_update(c, dx, P_out, stats, &pend);
   });
+}
+
+// UpdaterMSCKF::update on a state whose SLAM landmarks stay resident and current (include/ovgpu.h).  The landmarks have no column under the empty
+// active set, so the batch, the column map and every kernel are a landmark-free state's of the same N (enqueue_system, set_row_layout); k_lm_correct
+// (k_tail.h) follows the tail on the same predicates, and the corrected values come back with dx and P'.
+int ovgpu_msckf_update_lm(ovgpu_ctx *c, int32_t *feat_status, double *chi2, double *chi2_thresh, double *p_FinG, double *dx, double *P_out, double *lm_out,
+                          ovgpu_update_stats *stats) {
+  if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
+  // every check in front of the first launch: a refused call leaves the state, the landmarks and the resident batch as they were
+  if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state was never called");
+  if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features was never called (or the state changed since)");
+  if (c->L > 0 && !c->lm_empty_set)
+    return set_err(OVGPU_ERR_INVALID, "ovgpu_msckf_update_lm: the batch was laid out with landmark columns; call ovgpu_set_active_landmarks(ctx, NULL, 0) after "
+                                      "ovgpu_set_landmarks and hand the MSCKF batch to ovgpu_set_features again");
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const bool with_lm = lm_out != nullptr && c->L > 0;
+  c->lm_fast_on = c->L > 0;
+  const int rc = update_with_fallbacks(c, stats, [&]() {
+    int rc2 = enqueue_pipeline(c, STAGE_LOCAL | STAGE_EKF);
+    if (rc2 != OVGPU_OK) return rc2;
+    PendingFeatOut pend; // one synchronisation for the per-feature outputs, dx / P' and the landmarks
+    if ((rc2 = read_feature_outputs(c, feat_status, chi2, chi2_thresh, p_FinG, stats, &pend, finish_update_bytes(c, with_lm))) != OVGPU_OK) return rc2;
+    return finish_update(c, dx, P_out, stats, &pend, with_lm ? lm_out : nullptr);
+  });
+  c->lm_fast_on = false;
+  return rc;
 }
 
 int ovgpu_msckf_update_async(ovgpu_ctx *c) {

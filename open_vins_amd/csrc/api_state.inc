@@ -247,6 +247,7 @@ static int layout_columns(ovgpu_ctx *c, bool defer_flush, const int32_t *residen
     D_want += on ? v.size : 0, n_act += (on && v.kind == COL_LANDMARK) ? 1 : 0;
   }
   c->cols_over = D_want + 1 > 512;
+  c->lm_empty_set = c->L > 0 && act && n_act == 0; // no landmark has a column: the map below is a landmark-free state's (ovgpu_msckf_update_lm)
   if (c->cols_over)
     c->cols_over_msg = std::string("the active landmark set (") + (act ? std::to_string(n_act) + " landmarks named by ovgpu_set_active_landmarks" : "all " + std::to_string(c->L) + " resident landmarks: no set was named") +
                        ") gives " + std::to_string(D_want) + " Jacobian columns, more than 511: name the batch's landmarks with ovgpu_set_active_landmarks";
@@ -279,7 +280,7 @@ static int layout_columns(ovgpu_ctx *c, bool defer_flush, const int32_t *residen
     for (int i = 0; i < C; i++)
       if (clone_col[i] >= 0) clone_min = std::min(clone_min, clone_col[i]);
     const int NTf = (D + 1 + 15) / 16;
-    if (c->L == 0 && calib_end <= clone_min && NTf >= 6 && NTf <= 15) {
+    if ((c->L == 0 || c->lm_empty_set) && calib_end <= clone_min && NTf >= 6 && NTf <= 15) { // (with landmarks only the fused kernels of ovgpu_msckf_update_lm write this stack)
       const int top = NTf == 15 ? 15 : ((NTf + 1) & ~1); // (k_gram_il has the even counts and 15)
       int n = 0;
       for (int t = 4; t < top && n < RAW_MAXCLS - 1 && !c->raw_one_region; t += 2)
@@ -575,7 +576,9 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bo
   }
   // ---- MSCKF fast path (k_feat.h): gate matrix in registers, several workgroups per CU
   c->feat_variant = 0;
-  if (!slam_rows && !c->no_feat_kernel && c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D && c->L == 0 && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16) {
+  // (resident landmarks under the empty active set have no column: the same batch, the same column map and the same kernels as without them.  The
+  //  eligibility is recorded — lm_fast_ok below — and only ovgpu_msckf_update_lm switches it on: enqueue_system, api_pipeline.inc)
+  if (!slam_rows && !c->no_feat_kernel && c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D && (c->L == 0 || c->lm_empty_set) && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16) {
     // the gate matrix of the one-pass kernels: 2 m + 4 rows (the right-hand sides [r | H_f] are four augmented rows, k_featy.h), upper triangle
     const int nt = (2 * m_max + 15) / 16, nta = (2 * m_max + 4 + 15) / 16, tiles = nta * (nta + 1) / 2;
     // 1: <4 wavefronts, 9 tiles each>; 2: <8, 17> (one workgroup per CU: 256 registers per lane); up to two workgroups per CU
@@ -615,6 +618,7 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bo
       c->feat_variant = 0; // the general kernel (k_system.h)
     }
   }
+  c->lm_fast_ok = c->L > 0 && c->feat_variant != 0 && c->featy_ok;
   if (c->feat_variant) { // row store of the fast path
     const int M = std::max(c->M, 1);
     HIPCHK(c->fs_tq.reserve((size_t)std::max(F, 1) * 8));
@@ -785,7 +789,8 @@ static int end_feature_batch(ovgpu_ctx *c) {
   // rows of the stacked system: SLAM layout when landmarks are resident (the batch is for ovgpu_slam_update), MSCKF otherwise;
   // an entry point that needs the other layout switches it (set_row_layout).  With it the batch's integer tables, the triangulation's
   // anchor measurements among them (a property of the batch: k_batch_layout)
-  const int rcl = set_row_layout(c, c->L > 0, true);
+  // (... and MSCKF again under the empty active set: no landmark has a column, the batch can only be UpdaterMSCKF's or the delayed initialisation's)
+  const int rcl = set_row_layout(c, c->L > 0 && !c->lm_empty_set, true);
   if (rcl != OVGPU_OK) return rcl;
   c->have_feats = true;
   c->given_tri = false;

@@ -2,6 +2,7 @@
 // the pose tables of the next update (StateHelper.cpp:162-196 + the table of UpdaterMSCKF.cpp:97-115).
 #pragma once
 #include "k_ekf.h"
+#include "k_slam.h"
 #include "k_triangulate.h"
 
 namespace ovg {
@@ -31,6 +32,18 @@ __global__ void __launch_bounds__(256) k_tf_tail(EkfParams p, const double *Y1, 
   for (int i = threadIdx.x; i < n2; i += 256) build_tables_item(i, t.C, t.K, t.clone_qp, t.clone_fej, t.calib_qp, t.tab_clone, t.tab_cam, t.tab_cc);
 }
 
+// ovgpu_msckf_update_lm: Landmark::update (Landmark.h:55-62; the single-depth override, Landmark.cpp:130-140, moves the last stored value) for every
+// resident landmark with the correction the update above left in p.dx, read by covariance id — one thread per stored coordinate, consecutive lanes
+// on consecutive addresses.  ONE launch behind the tail (Gram route) or behind k_boxplus (Householder route), predicated on the very words the
+// box-plus is (ekf_skipped): an update the device skipped leaves the landmarks untouched, and the repeat that follows corrects them once.  Not a
+// phase of k_tf_tail's last block: that block is the update's critical path (dx -> box-plus -> pose tables), and every other caller of the tail
+// keeps its code object as it was.
+__global__ void __launch_bounds__(256) k_lm_correct(EkfParams p, int L, const int32_t *__restrict__ lm_rep, const int32_t *__restrict__ lm_cov, double *lm_value) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= 3 * L || ekf_skipped(p)) return;
+  const int l = t / 3, k = t % 3, j0 = 3 - lm_rep_dof(lm_rep[l]);
+  if (k >= j0) lm_value[3 * l + k] += p.dx[lm_cov[l] + k - j0]; // (lm_cov[l] + dof <= N: build_columns)
+}
 
 // ovgpu_reset_state in one launch: the prior copies of the covariance and of the resident poses / calibration come back, and the
 // pose tables are rebuilt FROM the saved values (four device-to-device copies + a table kernel before: five launches of ~5 us,

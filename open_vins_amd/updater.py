@@ -152,6 +152,34 @@ class UpdaterMSCKF:
         out.update(self.get_state(P=False))
         return out
 
+    def update_lm(self, check=True):
+        """UpdaterMSCKF::update with the resident SLAM landmarks kept current on the device (ovgpu_msckf_update_lm).  Call order: set_slam_state
+        (or ovgpu_set_state + ovgpu_set_landmarks), set_active_landmarks([]), set_features with the MSCKF batch, this.  Returns what update()
+        returns and `landmarks` [L, 3], the corrected values."""
+        F, N = self.F, self.N
+        Lc = C.c_int32(0)
+        capi.check(self.lib.ovgpu_get_landmarks(self._ctx, C.byref(Lc), None, None, None, None, None), "ovgpu_get_landmarks")
+        out = dict(feat_status=np.zeros(F, np.int32), chi2=np.zeros(F), chi2_thresh=np.zeros(F), p_FinG=np.zeros((F, 3)),
+                   dx=np.zeros(N), P=np.zeros((N, N)), landmarks=np.zeros((Lc.value, 3)))
+        stats = capi.UpdateStats()
+        rc = self.lib.ovgpu_msckf_update_lm(self._ctx, _ip(out["feat_status"]), _dp(out["chi2"]), _dp(out["chi2_thresh"]), _dp(out["p_FinG"]),
+                                            _dp(out["dx"]), _dp(out["P"]), _dp(out["landmarks"]) if Lc.value else None, C.byref(stats))
+        out["rc"] = rc
+        if check:
+            capi.check(rc, "ovgpu_msckf_update_lm")
+        out["stats"] = stats.as_dict()
+        out["route"] = self.lib.ovgpu_last_update_route(self._ctx)
+        out.update(self.get_state(P=False))
+        return out
+
+    def set_slam_state(self, prob):
+        """State and landmarks of a synth.make_slam_problem snapshot without a batch: what a resident loop holds between frames."""
+        v = capi.Views(prob)
+        self._views = v
+        self.N, self.Cn, self.K = v.state.N, v.state.C, v.state.K
+        capi.check(self.lib.ovgpu_set_state(self._ctx, C.byref(v.state)), "ovgpu_set_state")
+        capi.check(self.lib.ovgpu_set_landmarks(self._ctx, C.byref(v.landmarks)), "ovgpu_set_landmarks")
+
     def compress(self):
         """Mode A: returns the compressed (H, r) for the stock StateHelper::EKFUpdate."""
         F = self.F
