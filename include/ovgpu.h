@@ -1139,6 +1139,10 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             always stack projected rows.  ("raw_work_const": the region work model's constant; 2: one region, developer experiments)
  *   "last_stack_raw"          (read only) the last pipeline's Gram matrix came from the unprojected stack
  *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one
+ *   "anchored_fast"           (default 1) batches of an anchored feat_rep_msckf take the fused per-feature kernels: 48-double records with
+ *                             H_f = A dl at the p_FinG the anchor gives and no anchor blocks, which the nullspace projection annihilates
+ *                             (k_featy.h: k_feat_rows_anchored) — the same update to rounding; 0: the general kernel with its 72-double
+ *                             records, as before; takes effect with the next ovgpu_set_features
  *   "raw_gram_tile_rows"      (read only) rows x tiles summed over the regions of the resident batch: the 16 x 16 products per row k_gram_regions executes
  *   "speculative_prior"       (round 6, default 1) ovgpu_set_features starts the prior block's factorisation on the second stream, next to its own
  *                             uploads; the update joins it.  0: the factorisation starts with the update (round 5)

@@ -169,6 +169,7 @@ struct ovgpu_ctx {
   bool lm_empty_set = false;      // L > 0 and ovgpu_set_active_landmarks(ctx, NULL, 0) holds (layout_columns)
   bool lm_fast_ok = false;        // ... and the resident batch was laid out for the fused per-feature kernels under it (set_row_layout)
   int last_feat_kernel = 0;       // per-feature kernel of the last batch pipeline: 0 the general one (k_system.h), else the fused shape that ran (feat_variant)
+  bool anchored_fast = true;      // ovgpu_debug_option "anchored_fast": batches of an anchored feat_rep_msckf are laid out for the fused per-feature kernels too (set_row_layout)
   bool lm_fast_on = false;        // ovgpu_msckf_update_lm is running: the one entry that takes them with landmarks resident (enqueue_system)
   // device-resident FeatureDatabase (ovgpu_tracks_*)
   int trk_max = 0, trk_obs = 0;

@@ -29,6 +29,9 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "raw_stack") { // 0: the Gram route stacks the projected rows (rounds 2-5) instead of the unprojected ones in regions; takes effect with the next ovgpu_set_features
     if (old_value) *old_value = c->raw_enable ? 1 : 0;
     if (value >= 0) c->raw_enable = value != 0, c->raw_one_region = value == 2;
+  } else if (n == "anchored_fast") { // 0: batches of an anchored feat_rep_msckf keep the general kernel (the routing before k_feat_rows_anchored); takes effect with the next ovgpu_set_features
+    if (old_value) *old_value = c->anchored_fast ? 1 : 0;
+    if (value >= 0) c->anchored_fast = value != 0;
   } else if (n == "gram_blocks_only") {
     if (old_value) *old_value = c->gram_blocks_only ? 1 : 0;
     if (value >= 0) c->gram_blocks_only = value != 0;

@@ -102,11 +102,11 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     p.init_dof_less = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 2 : 0;
     grid = 1;
   }
-  // the MSCKF fast path: whitened output, global representation, one noise level (k_feat.h)
+  // the MSCKF fast path: whitened output, one noise level (k_feat.h); a global representation, or an anchored one on its own record kernel
   // (with landmarks resident — the empty active set, set_row_layout — only for ovgpu_msckf_update_lm: every other entry keeps the general kernel)
   if (p.Lw && c->feat_variant && (c->L == 0 || (c->lm_fast_on && c->lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
-    if (c->L > 0) p.row_stride = 48; // the fused kernels' records (fs_rows holds M * c->row_stride >= 48 M doubles): a 72-double stride that anchored landmarks or
-                                     // an earlier delayed initialisation left in the context is the general kernel's alone
+    p.row_stride = 48; // the fused kernels' records (fs_rows holds M * c->row_stride >= 48 M doubles): a 72-double stride — an anchored feat_rep_msckf, anchored
+                       // landmarks, an earlier delayed initialisation — is the general kernel's alone
     HIPCHK(c->feat_counter.reserve(1));
     HIPCHK(ctrl_zero(c, CTRL_COUNTER, c->feat_counter.p, sizeof(int32_t), c->stream));
     p.work_counter = c->feat_counter.p;
@@ -132,7 +132,8 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
         p.Hbig32 = c->Hbig32.p, p.LDF = c->stack_ldf;
         c->stack_is_f32 = true;
       }
-      hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((c->M + 255) / 256), dim3(256), 0, c->stream, p, st, c->M);
+      if (p.opt.feat_rep >= OVGPU_REP_ANCHORED_3D) hipLaunchKernelGGL(feat::k_feat_rows_anchored, dim3((c->M + 255) / 256), dim3(256), 0, c->stream, p, st, c->M);
+      else hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((c->M + 255) / 256), dim3(256), 0, c->stream, p, st, c->M);
       const bool big = c->feat_variant == 3 || c->featy_big;
       const int cb = featy_block_cols(c, p.Hbig32 != nullptr);
       if (c->raw_enable && c->raw_tables_ok && !c->raw_veto && !big && !p.Hbig32 && cb == feat::FY_CB) {

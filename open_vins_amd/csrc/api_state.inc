@@ -576,9 +576,11 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bo
   }
   // ---- MSCKF fast path (k_feat.h): gate matrix in registers, several workgroups per CU
   c->feat_variant = 0;
+  // (an anchored feat_rep_msckf takes it as well — k_feat_rows_anchored, k_featy.h: 48-double records whatever c->row_stride says, which stays the
+  //  general kernel's; ovgpu_debug_option "anchored_fast" = 0 keeps such batches on the general kernel)
   // (resident landmarks under the empty active set have no column: the same batch, the same column map and the same kernels as without them.  The
   //  eligibility is recorded — lm_fast_ok below — and only ovgpu_msckf_update_lm switches it on: enqueue_system, api_pipeline.inc)
-  if (!slam_rows && !c->no_feat_kernel && c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D && (c->L == 0 || c->lm_empty_set) && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16) {
+  if (!slam_rows && !c->no_feat_kernel && (c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D || c->anchored_fast) && (c->L == 0 || c->lm_empty_set) && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16) {
     // the gate matrix of the one-pass kernels: 2 m + 4 rows (the right-hand sides [r | H_f] are four augmented rows, k_featy.h), upper triangle
     const int nt = (2 * m_max + 15) / 16, nta = (2 * m_max + 4 + 15) / 16, tiles = nta * (nta + 1) / 2;
     // 1: <4 wavefronts, 9 tiles each>; 2: <8, 17> (one workgroup per CU: 256 registers per lane); up to two workgroups per CU

@@ -98,6 +98,30 @@ __global__ void __launch_bounds__(256) k_feat_rows_sorted(SysParams p, FeatStore
   else dl[0] = 1, dl[1] = 0, dl[2] = 0, dl[3] = 0, dl[4] = 1, dl[5] = 0, dl[6] = 0, dl[7] = 0, dl[8] = 1;
   sys_measurement_rows(p, gm, p_FinG, p_FinG, false, hq, st.minfo + (size_t)8 * pos, st.rows + (size_t)pos * p.row_stride);
 }
+
+// k_feat_rows_anchored: the same records for the ANCHORED representations (UpdaterHelper.cpp:84-189; the single depth arrives as the MSCKF
+// inverse depth, UpdaterMSCKF.cpp:180-183).  For an anchored feature H_f = A dl and the anchor blocks are A H_anc, A H_calib with the same
+// A = dz / dp_FinG row by row (UpdaterHelper.cpp:374-421); dl is 3 x 3 and invertible, so the left nullspace of H_f is A's, the projection
+// annihilates both anchor blocks and they leave the projected gate matrix as well: the update is the global one evaluated at the p_FinG the
+// anchor gives.  So the records stay 48 doubles — neither H_anc nor H_calib is formed — and everything behind them is
+// the global batch's.  H_f keeps dl (not A alone): the reflectors of k_feat_vt stay on the reference's columns when dl is badly conditioned.
+//   p_FinG   through the anchor's CURRENT clone pose and extrinsics from p_FinA (:268-280), as k_system does: a caller's p_FinG that
+//            disagrees with p_FinA loses.  With do_fej this "best" point is the linearisation point too (:282-287), the global feature's
+//   dl       anchored_rep_jacobian (k_system.h), at the anchor's first estimates under do_fej (:93-100)
+__global__ void __launch_bounds__(256) k_feat_rows_anchored(SysParams p, FeatStore st, int M) {
+  const int gm = blockIdx.x * 256 + threadIdx.x;
+  if (gm >= M) return;
+  const int f = st.meas_feat[gm];
+  if (p.status[f] != OVGPU_FEAT_USED) return;
+  const int pos = st.pos[gm];
+  const int ac = p.meas_cc[p.anchor_meas[f]]; // the anchor of the triangulation (k_triangulate / ovgpu_set_triangulation)
+  const double *tca = p.tab_cam + 12 * (ac >> 10), *tcl = p.tab_clone + 24 * (ac & 1023);
+  const V3 p_FinA = load_v3(p.p_FinA + 3 * f);
+  const V3 p_FinG = mulT(load_m3(tcl), mulT(load_m3(tca), p_FinA - load_v3(tca + 9))) + load_v3(tcl + 9); // UpdaterHelper.cpp:274
+  double hq[21], Ha[18], Hc[18]; // (H_anc, H_calib: computed by the shared routine, never read — dead code here)
+  anchored_rep_jacobian(p.opt.feat_rep, p.opt.do_fej, tca, tcl, p_FinA, hq + 12, Ha, Hc);
+  sys_measurement_rows(p, gm, p_FinG, p_FinG, false, hq, st.minfo + (size_t)8 * pos, st.rows + (size_t)pos * p.row_stride);
+}
 #endif // OVG_TU_FEATY
 
 // ---------------------------------------------------------------------------------------------------
