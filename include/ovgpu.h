@@ -86,6 +86,9 @@ extern "C" {
 /*      update in one device pass): a new symbol under the same number.          */
 /*      Likewise ovgpu_msckf_update_lm (the MSCKF update of a state whose        */
 /*      resident landmarks stay current, on the landmark-free state's kernels). */
+/*      Likewise ovgpu_slam_delayed_init_fused (the delayed initialisation with  */
+/*      every candidate's step as five launches; ovgpu_slam_delayed_init keeps   */
+/*      its kernels and its bits).                                               */
 /* ------------------------------------------------------------------------- */
 #define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
@@ -650,6 +653,27 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_stat
                             double *dx_seq, int32_t *N_out, double *P_out,
                             ovgpu_update_stats *stats);
 
+/* ovgpu_slam_delayed_init with every candidate's step fused: same inputs, outputs, ordering rules (triangulation once at entry,
+ * candidate f linearised at the state candidates 0 .. f-1 left, StateHelper::initialize's gate, growth by 3 or 1 per accepted
+ * candidate, a rejected candidate leaves the state bit for bit untouched), checks (all before anything changes) and error codes.
+ * Per candidate the chain of about eleven launches and two clears becomes five launches and no clear (csrc/k_init_fused.h): the
+ * system and its gate; ONE product [G ; A2_x] P(cols, :) on the matrix cores that serves initialize_invertible and EKFUpdate
+ * both; the innovation covariance next to the appended columns; its Cholesky factorisation with the carried columns; one tail
+ * (covariance with its new rows / columns, dx, box-plus, landmarks, the new landmark, counters, pose tables).  No host
+ * synchronisation inside the chain.  The results agree with ovgpu_slam_delayed_init's to rounding (the products are summed in
+ * another order), not bit for bit.
+ * Bound of the fused step: tracks of m <= 64 measurements (2m - 3 <= 125 projected rows).  A longer candidate takes
+ * ovgpu_slam_delayed_init's step where it stands in the chain and the chain goes on; so does every candidate when
+ * ovgpu_options::no_single_launch_cholesky is set or ovgpu_debug_option "delayed_init_fused" is 0 (then the outputs are
+ * ovgpu_slam_delayed_init's bit for bit).  "delayed_init_fused_steps" / "delayed_init_chain_steps" count the candidates of this
+ * entry by the step they took.  A time-out of the factorisation's bounded waits is reported as OVGPU_ERR_HIP, as there.
+ * Callers find the entry by symbol (ABI 10).                                                                      */
+int ovgpu_slam_delayed_init_fused(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_status, double *chi2,
+                                  double *chi2_thresh, int32_t *lm_cov_id, double *lm_value,
+                                  double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone,
+                                  double *dx_seq, int32_t *N_out, double *P_out,
+                                  ovgpu_update_stats *stats);
+
 /* Mode A of UpdaterSLAM::delayed_init (UpdaterSLAM.cpp:61-251): the chain of ovgpu_slam_delayed_init run
  * SPECULATIVELY, every feature's system exported in the form the stock StateHelper::initialize
  * (StateHelper.cpp:393-481) takes, so that an unpatched reference applies them itself.  Inputs as
@@ -1122,6 +1146,9 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *   "chol_timeouts"           (read only) number of updates repeated that way
  *   "slam_chunked_fallbacks"  number of ovgpu_slam_update_chunked passes that put the entry state back and ran the chunks one by one
  *                             (a value >= 0 sets the counter)
+ *   "delayed_init_fused"      (default 1) 0: ovgpu_slam_delayed_init_fused runs ovgpu_slam_delayed_init's step for every candidate
+ *   "delayed_init_fused_steps" / "delayed_init_chain_steps"  number of candidates of ovgpu_slam_delayed_init_fused that took the fused step /
+ *                             the chain's step (a track beyond the fused step's bound, or the switch above; a value >= 0 sets the counter)
  *   "slam_chunked_fail_chunk" k >= 0: the next ovgpu_slam_update_chunked treats chunk k's flag word as failed after its pass and takes
  *                             that path (one-shot; tests)
  *   "layout_every_update"     1: the integer tables ovgpu_set_features derives once per batch (anchor measurements, clone-major

@@ -262,6 +262,8 @@ def declare(lib):
         "ovgpu_get_landmarks": (C.c_int, [ctxp, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p]),
         "ovgpu_slam_delayed_init": (C.c_int, [ctxp, C.c_int32, c_int32_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p, c_int32_p,
                                               c_int32_p, c_double_p, c_int32_p, c_double_p, C.POINTER(UpdateStats)]),
+        "ovgpu_slam_delayed_init_fused": (C.c_int, [ctxp, C.c_int32, c_int32_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p, c_int32_p,
+                                                    c_int32_p, c_double_p, c_int32_p, c_double_p, C.POINTER(UpdateStats)]),
         "ovgpu_slam_init_systems_len": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(InitSizes)]),
         "ovgpu_slam_init_systems": (C.c_int, [ctxp, C.c_int32, C.c_int32, C.POINTER(InitSizes), C.POINTER(InitSystem), c_int32_p, c_int32_p, c_double_p,
                                               c_double_p, c_double_p, C.POINTER(UpdateStats)]),

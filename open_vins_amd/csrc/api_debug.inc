@@ -11,6 +11,15 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "slam_chunked_fallbacks") { // reads the count of restore-and-chain passes; a value >= 0 sets it
     if (old_value) *old_value = c->chunk_fallbacks;
     if (value >= 0) c->chunk_fallbacks = value;
+  } else if (n == "delayed_init_fused") { // 0: ovgpu_slam_delayed_init_fused runs the chain's step (enqueue_init_feature) for every candidate
+    if (old_value) *old_value = c->init_fused_on ? 1 : 0;
+    if (value >= 0) c->init_fused_on = value != 0;
+  } else if (n == "delayed_init_fused_steps") { // reads the count of candidates that took the fused step; a value >= 0 sets it
+    if (old_value) *old_value = c->init_fused_steps;
+    if (value >= 0) c->init_fused_steps = value;
+  } else if (n == "delayed_init_chain_steps") { // ... and of those ovgpu_slam_delayed_init_fused ran as the chain runs them
+    if (old_value) *old_value = c->init_chain_steps;
+    if (value >= 0) c->init_chain_steps = value;
   } else if (n == "gram_interleaved") {
     if (old_value) *old_value = c->gram_il ? 1 : 0;
     if (value >= 0) c->gram_il = value != 0;

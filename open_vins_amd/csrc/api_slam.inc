@@ -530,9 +530,50 @@ static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap
   return OVGPU_OK;
 }
 
-int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
-                            double *lm_value, double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone, double *dx_seq, int32_t *N_out,
-                            double *P_out, ovgpu_update_stats *stats) {
+// One candidate as the fused step (k_init_fused.h): five launches, no memset.  The caller has checked initf_holds(c, m).
+static bool initf_holds(const ovgpu_ctx *c, int m) { return m >= 2 && m <= INITF_M_MAX && chol_pipe_usable(c, 2 * m - 3); }
+static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, double *dx) {
+  hipStream_t s = c->stream;
+  const int m = c->h_offsets[f + 1] - c->h_offsets[f], r = 2 * m - 3;
+  int rc = enqueue_system(c, f, rep);
+  if (rc != OVGPU_OK) return rc;
+  c->last_update_tform = false;
+  InitFusedParams p;
+  p.N = Nmax, p.D = c->D, p.LD = c->LD, p.r = r, p.LA = r + Nmax + 1, p.rep = rep, p.f = f, p.sz = lm_dof(rep);
+  p.col_cov = c->col_cov.p, p.init_out = c->init_ws.p, p.stack = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, p.P = c->P.p;
+  p.A = c->Aaug.p, p.Y = c->Yaug.p, p.T = c->init_ws.p + (size_t)3 * c->LD + 16, p.PLL = p.T + (size_t)3 * Nmax;
+  p.sigma2 = c->dopt.sigma_pix_sq, p.ctr = c->init_ctr.p, p.dx = dx, p.flags = c->flags.p;
+  p.C = c->C, p.K = c->K, p.clone_cov = c->clone_cov.p, p.calib_cov = c->calib_cov.p, p.intr_cov = c->intr_cov.p;
+  p.clone_qp = c->clone_qp.p, p.calib_qp = c->calib_qp.p, p.intr = c->intr.p, p.clone_fej = c->clone_fej.p;
+  p.tab_clone = c->tab_clone.p, p.tab_cam = c->tab_cam.p, p.tab_cc = c->tab_cc.p;
+  p.p_FinG = c->pG.p, p.p_FinA = c->pA.p, p.meas_cc = c->meas_cc.p, p.anchor_meas = c->anchor.p, p.lm = landmark_store(c), p.feat_slot = c->feat_slot.p;
+  const int slot = (c->chol_slot++) & 1;
+  p.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot;
+  c->ctrl_clean &= ~(slot ? CTRL_PROG1 : CTRL_PROG0), c->ctrl_pre &= ~(slot ? CTRL_PROG1 : CTRL_PROG0); // (the step words are k_initf_s's to clear, and dirty afterwards)
+  const int tn = (Nmax + 15) / 16, tw = (r + 3 + 15) / 16, tm = (r + 15) / 16;
+  hipLaunchKernelGGL(k_initf_w, dim3((tw * tn + 3) / 4), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_initf_s, dim3((tm * tw + 3) / 4 + 1), dim3(256), 0, s, p);
+  chol::CholParams q;
+  q.D = r, q.LA = p.LA, q.A = p.A, q.Y = c->Yaug.p, q.Lt = nullptr, q.flags = c->flags.p, q.diag0 = nullptr, q.pivot_tol = 1e-13, q.pred = c->init_ctr.p + 2;
+  q.prog = p.prog, q.uinv = c->chol_uinv.p + (size_t)slot * 16 * 256, q.err = c->flags.p + 2, q.dbg = c->dbg_cycles.p;
+  q.spin_limit = c->chol_spin_limit, q.n_arrive = chol::chol_tile_waves(tm), q.src = chol::CH_SRC_MATRIX, q.N = Nmax, q.pred_not = nullptr;
+  c->last_uinv = q.uinv;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)chol::k_chol_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol::chol_lds_bytes());
+    attr = true;
+  }
+  const int carried = (p.LA - r + 15) / 16;
+  hipLaunchKernelGGL(chol::k_chol_fused, dim3(1 + (carried + chol::CH_FC - 1) / chol::CH_FC), dim3(64 * (chol::CH_FW + 1)), chol::chol_lds_bytes(), s, q);
+  hipLaunchKernelGGL(k_initf_tail, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+// ovgpu_slam_delayed_init (fused = false) and ovgpu_slam_delayed_init_fused: one body, the step per candidate differs
+static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
+                             double *lm_value, double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone, double *dx_seq, int32_t *N_out,
+                             double *P_out, ovgpu_update_stats *stats) {
   if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
   { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }  // the covariance changes: a prior-block factorisation started for a sharded update is stale
   if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state was never called");
@@ -564,10 +605,14 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   int rc = reserve_landmarks(c, L0 + F, L0);
   if (rc != OVGPU_OK) return rc;
   HIPCHK(c->Ppad.reserve((size_t)Nmax * Nmax));
-  HIPCHK(c->init_ws.reserve((size_t)3 * c->LD + 16));
-  HIPCHK(c->init_ctr.reserve(4));
+  HIPCHK(c->init_ws.reserve((size_t)3 * c->LD + 16 + (size_t)3 * Nmax + 16)); // (behind the system's three rows and R1: k_init_fused.h's T and P_LL)
+  HIPCHK(c->init_ctr.reserve(8));
   HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
   HIPCHK(c->dx_seq.reserve((size_t)std::max(F, 1) * Nmax));
+  if (fused) {
+    HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
+    HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
+  }
   HIPCHK(c->Mt.reserve((size_t)std::max(r_max, c->D) * Nmax));
   HIPCHK(c->Aaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
   HIPCHK(c->Yaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
@@ -586,7 +631,7 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
     std::swap(c->P, c->Ppad);
     c->N = Nmax;
   }
-  const int32_t ctr0[4] = {N0, L0, 0, 0};
+  const int32_t ctr0[8] = {N0, L0, 0, 0, 0, 0, 0, 0}; // ([4]: the fused tail's arrival count)
   HIPCHK(upload(c->init_ctr.p, ctr0, sizeof(ctr0), s));
   HIPCHK(upload_sync(c, s)); // ctr0 is a stack variable
   HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
@@ -595,8 +640,15 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   const size_t init_lds = ((size_t)3 * c->LD + (size_t)3 * Nmax + 16) * sizeof(double);
   // ---- 4. one feature after the other (UpdaterSLAM.cpp:147-239)
   for (int f = 0; f < F && rc == OVGPU_OK; f++) {
-    if (c->h_offsets[f + 1] - c->h_offsets[f] < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
+    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+    if (m < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
+    if (fused && c->init_fused_on && initf_holds(c, m)) {
+      rc = enqueue_init_feature_fused(c, f, rep_of(f), Nmax, c->dx_seq.p + (size_t)f * Nmax);
+      c->init_fused_steps++;
+      continue;
+    }
     rc = enqueue_init_feature(c, f, rep_of(f), Nmax, L0 + F, init_lds, c->dx_seq.p + (size_t)f * Nmax, nullptr);
+    if (fused) c->init_chain_steps++; // (a track beyond the fused step's bound, or "delayed_init_fused" = 0)
   }
   // ---- results
   int32_t ctr[4] = {N0, L0, 0, 0};
@@ -680,6 +732,20 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   if (stats) stats->status = status;
   if (status != OVGPU_OK) return set_err(status, status == OVGPU_ERR_NOT_SPD ? "innovation covariance not SPD" : "negative covariance diagonal after the update");
   return OVGPU_OK;
+}
+
+int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
+                            double *lm_value, double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone, double *dx_seq, int32_t *N_out,
+                            double *P_out, ovgpu_update_stats *stats) {
+  return delayed_init_impl(c, false, feat_rep, feat_status, chi2, chi2_thresh, lm_cov_id, lm_value, lm_fej, anchor_cam, anchor_clone, dx_seq, N_out, P_out, stats);
+}
+
+// The same call with every candidate the fused step holds (k_init_fused.h: m <= INITF_M_MAX) run as five launches; the others take
+// enqueue_init_feature where they stand in the chain.
+int ovgpu_slam_delayed_init_fused(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
+                                  double *lm_value, double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone, double *dx_seq, int32_t *N_out,
+                                  double *P_out, ovgpu_update_stats *stats) {
+  return delayed_init_impl(c, true, feat_rep, feat_status, chi2, chi2_thresh, lm_cov_id, lm_value, lm_fej, anchor_cam, anchor_clone, dx_seq, N_out, P_out, stats);
 }
 
 

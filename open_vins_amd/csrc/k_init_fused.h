@@ -1,0 +1,251 @@
+// k_init_fused.h — one candidate of UpdaterSLAM::delayed_init (UpdaterSLAM.cpp:147-239: StateHelper::initialize = initialize_invertible
+// followed by EKFUpdate, StateHelper.cpp:393-577) as a chain of FIVE launches without a memset (ovgpu_slam_delayed_init_fused):
+//
+//   k_system_t (init mode, k_system.h)   A1 = Q1^T [H_x | res] with R1 (init_out), A2 = Q2^T [H_x | res] (the stack's 2m - 3 rows), the gate flag
+//   k_initf_w                            W = [G ; A2_x] P(cols, :),  G = R1^-1 A1           (3 + 2m - 3) x N, on the matrix cores
+//   k_initf_s                            [S | -W2(:, cols) G^T | res2],  S = W2(:, cols) A2_x^T + sigma^2 I;  P_LL;  the Cholesky's step words
+//   k_chol_fused (k_chol.h)              S = U^T U carried through [W2 | new columns | res2]  ->  Z, y
+//   k_initf_tail                         P <- P_aug - Z^T Z, dx = Z^T y, box-plus, landmarks, the new landmark, counters, pose tables
+//
+// The algebra.  initialize_invertible appends the columns P(:, new) = -P(:, cols) G^T and P_LL = G P_DD G^T + sigma^2 R1^-1 R1^-T; the
+// update that follows has H_f = 0 on the new variable, so its P_aug H^T is [W2^T ; -G W2(:, cols)^T]: BOTH need only G P(cols, :) and
+// A2_x P(cols, :), i.e. ONE product of (2m) x D by D x N, and the appended columns need not be in memory before the update — the tail
+// reads them from T = G P(cols, :) while it writes P_aug - Z^T Z.  The chain of single launches (k_init_invertible, k_ekf_mt, k_ekf_s, two
+// clears, k_chol_fused, k_ekf_dx, k_ekf_pupdate, k_boxplus, k_build_tables, k_landmark_update) formed G P(cols, :) serially over D on one
+// workgroup and the second product in a kernel of its own.
+//
+// Per-feature noise (ovgpu_set_feature_options): k_system_t scales A1, R1 and A2 by sigma / sigma_f, so sigma^2 below is the context's one
+// value and sigma^2 R1^-1 R1^-T is sigma_f^2 (R1 / scale)^-1 (..)^-T.
+//
+// Everything is predicated on the gate flag ctr[2]: a rejected candidate writes nothing.  No workgroup waits for another one in the three kernels
+// of this file: the tail's counters are advanced by the workgroup that finishes LAST (an atomic count of arrivals, reset by that workgroup).
+// The only waits of the step are k_chol_fused's bounded ones.
+//
+// Bound: 2m - 3 + 3 <= 128 rows of W (eight 16-row tiles), m <= INITF_M_MAX = 64; a longer track takes the chain of single launches.
+#pragma once
+#include "k_ekf.h"
+#include "k_slam.h"
+#include "k_triangulate.h"
+
+namespace ovg {
+
+constexpr int INITF_M_MAX = 64;
+
+struct InitFusedParams {
+  int N;                    // leading dimension of P (the padded capacity) = carried covariance columns
+  int D, LD;                // Jacobian columns, row stride of the system rows (residual in column D)
+  int r, LA;                // 2m - 3 projected rows; LA = r + N + 1 columns of the factorisation's work matrix
+  int rep, f, sz;           // representation, feature, dof of the new landmark (3; 1: only the third row of the 3-row system initialises it)
+  const int32_t *col_cov;   // [D]
+  const double *init_out;   // [3 LD + 9]: A1, R1
+  const double *stack;      // [r x LD]: A2
+  double *P;                // [N x N]
+  double *A;                // [r x LA] = [S | W2 (new columns at id ..) | res2]
+  const double *Y;          // [r x LA] the factorisation's result [U | Z | y]
+  double *T;                // [3 x N] G P(cols, :)
+  double *PLL;              // [9] G P_DD G^T + sigma^2 R1^-1 R1^-T
+  double sigma2;
+  int32_t *ctr;             // [0] covariance dimension, [1] landmark count, [2] this candidate passed the gate, [4] arrivals of the tail's workgroups
+  int32_t *prog;            // [16] k_chol_fused's step words (cleared by k_initf_s)
+  double *dx;               // [N] row f of dx_seq
+  int32_t *flags;           // [1] = 1: a negative diagonal of P after the update
+  // the tail
+  int C, K;
+  const int32_t *clone_cov, *calib_cov, *intr_cov;
+  double *clone_qp, *calib_qp, *intr;
+  const double *clone_fej;
+  double *tab_clone, *tab_cam, *tab_cc;
+  const double *p_FinG, *p_FinA;
+  const uint16_t *meas_cc;
+  const int32_t *anchor_meas;
+  LandmarkStore lm;
+  int32_t *feat_slot;
+};
+
+// H_L^-1 of the upper-triangular 3 x 3 R1 (StateHelper.cpp:548) and a column of G = H_L^-1 [H_R | res]
+struct InitHLinv {
+  double i00, i01, i02, i11, i12, i22;
+};
+__device__ __forceinline__ InitHLinv initf_hlinv(const double *R1) {
+  const double u00 = R1[0], u01 = R1[1], u02 = R1[2], u11 = R1[4], u12 = R1[5], u22 = R1[8];
+  InitHLinv h;
+  h.i00 = 1.0 / u00, h.i11 = 1.0 / u11, h.i22 = 1.0 / u22;
+  h.i01 = -u01 * h.i00 * h.i11, h.i12 = -u12 * h.i11 * h.i22, h.i02 = (u01 * u12 - u02 * u11) * h.i00 * h.i11 * h.i22;
+  return h;
+}
+__device__ __forceinline__ double initf_g(const InitHLinv &h, const double *top, int LD, int j, int c) {
+  const double a = top[c], b = top[LD + c], d = top[2 * LD + c];
+  return j == 0 ? h.i00 * a + h.i01 * b + h.i02 * d : (j == 1 ? h.i11 * b + h.i12 * d : h.i22 * d);
+}
+
+// W = [G ; A2_x] P(cols, :): one wavefront per 16 x 16 tile, W's rows tiled by 16 (G's three rows and A2's in one operand), the N columns
+// across workgroups, P's rows gathered by col_cov.  Rows 0..2 -> T, rows 3.. -> the carried columns of A.
+__global__ void __launch_bounds__(256) k_initf_w(InitFusedParams p) {
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int tn = (p.N + 15) / 16, tm = (p.r + 3 + 15) / 16;
+  if (tile >= tn * tm || p.ctr[2] == 0) return;
+  const int r0 = (tile / tn) * 16, c0 = (tile % tn) * 16;
+  const InitHLinv h = initf_hlinv(p.init_out + (size_t)3 * p.LD);
+  auto fa = [&](int i, int k) {
+    const int row = r0 + i;
+    if (row < 3) return initf_g(h, p.init_out, p.LD, row, k);
+    return row < p.r + 3 ? p.stack[(size_t)(row - 3) * p.LD + k] : 0.0;
+  };
+  auto fb = [&](int k, int j) { const int c = c0 + j; return (c < p.N) ? p.P[(size_t)p.col_cov[k] * p.N + c] : 0.0; };
+  const double4_t acc = mfma_tile(fa, fb, p.D, lane);
+  const int col = c0 + (lane & 15);
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int row = r0 + (lane >> 4) + 4 * q;
+    if (col >= p.N || row >= p.r + 3) continue;
+    if (row < 3) p.T[(size_t)row * p.N + col] = acc[q];
+    else p.A[(size_t)(row - 3) * p.LA + p.r + col] = acc[q];
+  }
+}
+
+// [S | new columns] = W2(:, cols) [A2_x ; G]^T (+ sigma^2 I on S): one wavefront per tile, the three rows of G ride behind A2's in the second
+// operand.  The LAST workgroup: P_LL (wavefront 0), the residual column, the factorisation's step words.
+__global__ void __launch_bounds__(256) k_initf_s(InitFusedParams p) {
+  if (p.ctr[2] == 0) return;
+  const int lane = threadIdx.x & 63;
+  const int r = p.r, LD = p.LD, LA = p.LA, N = p.N, D = p.D;
+  const InitHLinv h = initf_hlinv(p.init_out + (size_t)3 * LD);
+  const int id = p.ctr[0], j0 = 3 - p.sz;
+  if (blockIdx.x + 1 == gridDim.x) {
+    for (int row = threadIdx.x; row < r; row += 256) p.A[(size_t)row * LA + r + N] = p.stack[(size_t)row * LD + D];
+    if (threadIdx.x < 16) p.prog[threadIdx.x] = 0;
+    if (threadIdx.x < 64) {
+      double s[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+      for (int c = lane; c < D; c += 64) {
+        const int cc = p.col_cov[c];
+        double g[3], t[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) g[j] = initf_g(h, p.init_out, LD, j, c), t[j] = p.T[(size_t)j * N + cc];
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+#pragma unroll
+          for (int k = 0; k < 3; k++) s[j][k] = fma(t[j], g[k], s[j][k]);
+      }
+#pragma unroll
+      for (int j = 0; j < 3; j++)
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+          for (int off = 32; off > 0; off >>= 1) s[j][k] += __shfl_xor(s[j][k], off, 64);
+      if (lane == 0) {
+        const double inv[3][3] = {{h.i00, h.i01, h.i02}, {0.0, h.i11, h.i12}, {0.0, 0.0, h.i22}};
+        for (int j = 0; j < 3; j++)
+          for (int k = 0; k < 3; k++) {
+            double w = 0.0;
+            for (int q = 0; q < 3; q++) w = fma(inv[j][q], inv[k][q], w); // sigma^2 H_L^-1 H_L^-T (:549, R = sigma^2 I)
+            p.PLL[3 * j + k] = fma(p.sigma2, w, s[j][k]);
+          }
+      }
+    }
+    return;
+  }
+  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int tm = (r + 15) / 16, tc = (r + 3 + 15) / 16;
+  if (tile >= tm * tc) return;
+  const int r0 = (tile / tc) * 16, c0 = (tile % tc) * 16;
+  auto fa = [&](int i, int k) { const int row = r0 + i; return (row < r) ? p.A[(size_t)row * LA + r + p.col_cov[k]] : 0.0; };
+  auto fb = [&](int k, int j) {
+    const int c = c0 + j;
+    if (c < r) return p.stack[(size_t)c * LD + k];
+    return c < r + 3 ? initf_g(h, p.init_out, LD, c - r, k) : 0.0;
+  };
+  const double4_t acc = mfma_tile(fa, fb, D, lane);
+  const int col = c0 + (lane & 15);
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int row = r0 + (lane >> 4) + 4 * q;
+    if (row >= r) continue;
+    if (col < r) p.A[(size_t)row * LA + col] = acc[q] + (row == col ? p.sigma2 : 0.0);
+    else if (col >= r + j0 && col < r + 3) p.A[(size_t)row * LA + r + id + (col - r - j0)] = -acc[q]; // (id + sz <= N: the capacity counts every candidate)
+  }
+}
+
+// The tail.  Workgroups 0 .. n - 2: one wavefront per 16 x 16 tile of P <- P_aug - Z^T Z over the current dimension id + sz, the appended rows /
+// columns taken from T and P_LL (symmetric by construction: Z^T Z is, -T is mirrored, P_LL is averaged with its transpose).  The last workgroup:
+// dx = Z^T y, Landmark::update of the resident landmarks, the new landmark, box-plus of clones / calibration / intrinsics, the pose tables.  The
+// workgroup that arrives last advances the dimension and the landmark count.
+__global__ void __launch_bounds__(256) k_initf_tail(InitFusedParams p) {
+  if (p.ctr[2] == 0) return; // (every workgroup reads the same word: all of them leave, nobody counts)
+  const int lane = threadIdx.x & 63, tid = threadIdx.x;
+  const int r = p.r, LA = p.LA, N = p.N;
+  const int id = p.ctr[0], slot = p.ctr[1], j0 = 3 - p.sz, n1 = id + p.sz;
+  const double *Z = p.Y + r;
+  if (blockIdx.x + 1 < gridDim.x) {
+    const int tile = blockIdx.x * 4 + (tid >> 6);
+    const int tn = (N + 15) / 16;
+    const int r0 = (tile / tn) * 16, c0 = (tile % tn) * 16;
+    if (tile < tn * tn && r0 < n1 && c0 < n1) {
+      auto fa = [&](int i, int k) { const int row = r0 + i; return (row < n1) ? Z[(size_t)k * LA + row] : 0.0; };
+      auto fb = [&](int k, int j) { const int c = c0 + j; return (c < n1) ? Z[(size_t)k * LA + c] : 0.0; };
+      const double4_t acc = mfma_tile(fa, fb, r, lane);
+      const int col = c0 + (lane & 15);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int row = r0 + (lane >> 4) + 4 * q;
+        if (row >= n1 || col >= n1) continue;
+        double base;
+        if (row < id && col < id) base = p.P[(size_t)row * N + col];
+        else if (row >= id && col >= id) base = 0.5 * (p.PLL[3 * (row - id + j0) + col - id + j0] + p.PLL[3 * (col - id + j0) + row - id + j0]); // :558
+        else if (row >= id) base = -p.T[(size_t)(row - id + j0) * N + col]; // :556-557
+        else base = -p.T[(size_t)(col - id + j0) * N + row];
+        const double v = base - acc[q];
+        p.P[(size_t)row * N + col] = v;
+        if (row == col && v < 0.0) p.flags[1] = 1; // StateHelper.cpp:172-182
+      }
+    }
+  } else {
+    const double *y = p.Y + r + N;
+    for (int i = tid; i < N; i += 256) {
+      double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      if (i < n1) {
+        int k = 0;
+        for (; k + 4 <= r; k += 4) {
+          s0 = fma(Z[(size_t)k * LA + i], y[(size_t)k * LA], s0);
+          s1 = fma(Z[(size_t)(k + 1) * LA + i], y[(size_t)(k + 1) * LA], s1);
+          s2 = fma(Z[(size_t)(k + 2) * LA + i], y[(size_t)(k + 2) * LA], s2);
+          s3 = fma(Z[(size_t)(k + 3) * LA + i], y[(size_t)(k + 3) * LA], s3);
+        }
+        for (; k < r; k++) s0 = fma(Z[(size_t)k * LA + i], y[(size_t)k * LA], s0);
+      }
+      p.dx[i] = (s0 + s1) + (s2 + s3);
+    }
+    __syncthreads(); // dx complete (this workgroup wrote all of it)
+    for (int t = tid; t < 3 * slot; t += 256) { // Landmark::update of the resident landmarks, through P alone (k_landmark_update's rule)
+      const int l = t / 3, k = t % 3, l0 = 3 - lm_rep_dof(p.lm.rep[l]);
+      if (k >= l0) p.lm.value[3 * l + k] += p.dx[p.lm.cov[l] + k - l0];
+    }
+    if (tid < 3) { // the new landmark: UpdaterSLAM.cpp:213-221, new_variable->update(H_L^-1 res) (:569), then the update's own correction
+      const bool relative = p.rep >= OVGPU_REP_ANCHORED_3D;
+      const double *x = (relative ? p.p_FinA : p.p_FinG) + 3 * p.f;
+      double v[3];
+      lm_from_xyz(p.rep, V3{x[0], x[1], x[2]}, v);
+      const int j = tid;
+      const InitHLinv h = initf_hlinv(p.init_out + (size_t)3 * p.LD);
+      p.lm.fej[3 * slot + j] = v[j];
+      p.lm.value[3 * slot + j] = j >= j0 ? (v[j] + initf_g(h, p.init_out, p.LD, j, p.D)) + p.dx[id + j - j0] : v[j];
+      if (j == 0) {
+        p.lm.cov[slot] = id, p.lm.col[slot] = -1, p.lm.rep[slot] = p.rep;
+        p.lm.anchor[slot] = relative ? (int32_t)p.meas_cc[p.anchor_meas[p.f]] : -1;
+        p.feat_slot[p.f] = slot;
+      }
+    }
+    const int nb = max(p.C, p.K);
+    for (int t = tid; t < nb; t += 256) boxplus_item(t, p.C, p.K, p.dx, p.clone_cov, p.calib_cov, p.intr_cov, p.clone_qp, p.calib_qp, p.intr);
+    __syncthreads(); // the poses the tables are built from
+    const int nt = max(p.K * p.C, nb);
+    for (int t = tid; t < nt; t += 256) build_tables_item(t, p.C, p.K, p.clone_qp, p.clone_fej, p.calib_qp, p.tab_clone, p.tab_cam, p.tab_cc);
+  }
+  // every workgroup has read the counters by now; the one that arrives last advances them (nobody waits)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    if (atomicAdd(p.ctr + 4, 1) == (int)gridDim.x - 1) p.ctr[0] = n1, p.ctr[1] = slot + 1, p.ctr[4] = 0;
+  }
+}
+
+} // namespace ovg

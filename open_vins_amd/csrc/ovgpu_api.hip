@@ -39,6 +39,7 @@
 #include "k_triangulate.h"
 #include "k_tail.h"
 #include "k_retri.h"
+#include "k_init_fused.h"
 #include "ovgpu_types.h"
 
 // The fused per-feature kernels live in the second translation unit (ovgpu_featy_tu.hip: its own scheduler strategy); here they are

@@ -1,6 +1,6 @@
 // Mode-B replacement for the body of ov_msckf::UpdaterSLAM::delayed_init (ov_msckf/src/update/UpdaterSLAM.cpp:61-251,
 // rpng/open_vins v2.7): triangulation, the per-feature StateHelper::initialize chain and every EKF update of it run on the GPU
-// (ovgpu_slam_delayed_init); the host writes the posterior back.
+// (ovgpu_slam_delayed_init_fused where the library exports it, ovgpu_slam_delayed_init otherwise); the host writes the posterior back.
 //
 // Unlike the mode-A shims this one has to WRITE State::_Cov and State::_variables, which are private with `friend class
 // StateHelper` (State.h:182-192): it needs the one line of ovgpu_state_access.h added to the reference.  Without that patch keep
@@ -18,6 +18,10 @@
 #else
 #include "ovgpu_shim_common.h"
 #include "ovgpu_state_access.h"
+
+// ovgpu_slam_delayed_init_fused (every candidate's step as five launches) is newer than the ABI number it shares with its library (10).  A weak
+// reference keeps the drop-in loadable next to a library that does not export it: the chain of single launches runs then, as before.
+#pragma weak ovgpu_slam_delayed_init_fused
 
 using namespace ov_core;
 using namespace ov_type;
@@ -76,8 +80,9 @@ void UpdaterSLAM::delayed_init(std::shared_ptr<State> state, std::vector<std::sh
   std::vector<int32_t> status(F), new_cov(F), acam(F), aclone(F), tri_anchor(F);
   std::vector<double> new_val(3 * (size_t)F), new_fej(3 * (size_t)F), dx_seq((size_t)F * Nmax), Pout((size_t)Nmax * Nmax), pA(3 * (size_t)F), pG(3 * (size_t)F);
   int32_t N1 = 0;
-  cx.check(ovgpu_slam_delayed_init(ctx, (int32_t)rep, status.data(), nullptr, nullptr, new_cov.data(), new_val.data(), new_fej.data(), acam.data(),
-                                   aclone.data(), dx_seq.data(), &N1, Pout.data(), nullptr),
+  const auto entry = ovgpu_slam_delayed_init_fused ? ovgpu_slam_delayed_init_fused : ovgpu_slam_delayed_init;
+  cx.check(entry(ctx, (int32_t)rep, status.data(), nullptr, nullptr, new_cov.data(), new_val.data(), new_fej.data(), acam.data(), aclone.data(),
+                 dx_seq.data(), &N1, Pout.data(), nullptr),
            "ovgpu_slam_delayed_init");
   cx.check(ovgpu_get_triangulation(ctx, pA.data(), pG.data(), tri_anchor.data()), "ovgpu_get_triangulation");
 

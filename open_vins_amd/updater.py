@@ -293,10 +293,11 @@ class UpdaterMSCKF:
         return out
 
     # ---- UpdaterSLAM::delayed_init (UpdaterSLAM.cpp:61-251) -------------
-    def delayed_init(self, feat_rep=0, feat_rep_each=None):
+    def delayed_init(self, feat_rep=0, feat_rep_each=None, fused=False):
         """Runs the delayed initialisation on the resident state and tracks (set_problem / set_slam_problem first;
         set_triangulation optionally replaces the triangulation stage).  The state grows by 3 (1: single depth) per accepted
-        feature.  feat_rep_each [F]: the representation per feature (UpdaterSLAM.cpp:160-166: feat_rep_aruco for ArUco corners)."""
+        feature.  feat_rep_each [F]: the representation per feature (UpdaterSLAM.cpp:160-166: feat_rep_aruco for ArUco corners).
+        fused: through ovgpu_slam_delayed_init_fused (five launches per candidate); same dictionary."""
         F, N = self.F, self.N
         reps = np.full(F, int(feat_rep), np.int32)
         if feat_rep_each is not None:
@@ -309,11 +310,12 @@ class UpdaterMSCKF:
         Pbuf = np.zeros(Nmax * Nmax)
         N_out = C.c_int32(0)
         stats = capi.UpdateStats()
-        rc = self.lib.ovgpu_slam_delayed_init(self._ctx, int(feat_rep), _ip(out["feat_status"]), _dp(out["chi2"]), _dp(out["chi2_thresh"]),
-                                              _ip(out["lm_cov_id"]), _dp(out["lm_value"]), _dp(out["lm_fej"]), _ip(out["anchor_cam"]),
-                                              _ip(out["anchor_clone"]), _dp(out["dx_seq"]), C.byref(N_out), _dp(Pbuf), C.byref(stats))
+        name = "ovgpu_slam_delayed_init_fused" if fused else "ovgpu_slam_delayed_init"
+        rc = getattr(self.lib, name)(self._ctx, int(feat_rep), _ip(out["feat_status"]), _dp(out["chi2"]), _dp(out["chi2_thresh"]),
+                                     _ip(out["lm_cov_id"]), _dp(out["lm_value"]), _dp(out["lm_fej"]), _ip(out["anchor_cam"]),
+                                     _ip(out["anchor_clone"]), _dp(out["dx_seq"]), C.byref(N_out), _dp(Pbuf), C.byref(stats))
         out["rc"] = rc
-        capi.check(rc, "ovgpu_slam_delayed_init")
+        capi.check(rc, name)
         n = N_out.value
         out["N"] = n
         out["P"] = Pbuf[: n * n].reshape(n, n).copy()
