@@ -508,37 +508,43 @@ static int enqueue_ekf(ovgpu_ctx *c, const EkfJob &job = EkfJob()) {
 // EKF update straight from the Gram matrix in c->gram_G (k_ekf.h, "whitened by the prior"): two Cholesky-with-carry passes
 // through k_ekf_chol_step — P_DD carrying P(D, :), then T = I + U1 G U1^T / sigma^2 carrying [B | U1 g / sigma^2]
 static bool chol_pipe_usable(const ovgpu_ctx *c, int D) { return !c->no_chol_pipe && D <= 16 * chol::CH_TMAX && D >= 1; }
+// chol::k_chol_fused on `s` with the progress words and inverse-diagonal tiles of `slot` (two factorisations may be in flight on the two
+// streams); the caller has set q.D, q.LA, q.flags, what is factored and its predicates, and has seen to the slot's progress words.
+// ONE launch (round 5): block 0 factors, the others carry the columns next to it (k_chol.h).  Until round 4 the carried columns were a
+// kernel of their own that had to run NEXT TO the factor kernel, i.e. on a helper stream behind an event, with a second event to join
+// it: each hand-over cost the stream ~6-13 us whichever side carried it (profiles/r05_c_timeline_*: 13 us between k_gram_reduce and
+// the second factorisation, 14 us behind k_tf_tail).
+static int chol_next_slot(ovgpu_ctx *c) { return (c->chol_slot++) & 1; }
+static int launch_chol_fused(ovgpu_ctx *c, chol::CholParams &q, int slot, hipStream_t s) {
+  q.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot, q.uinv = c->chol_uinv.p + (size_t)slot * 16 * 256, q.err = q.flags + 2, q.dbg = c->dbg_cycles.p;
+  q.spin_limit = c->chol_spin_limit, q.n_arrive = chol::chol_tile_waves((q.D + 15) / 16);
+  c->last_uinv = q.uinv;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)chol::k_chol_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol::chol_lds_bytes());
+    attr = true;
+  }
+  const int carried = (q.LA - q.D + 15) / 16;
+  hipLaunchKernelGGL(chol::k_chol_fused, dim3(1 + (carried + chol::CH_FC - 1) / chol::CH_FC), dim3(64 * (chol::CH_FW + 1)), chol::chol_lds_bytes(), s, q);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
 static int enqueue_chol_carry(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, double *Lt, const CholSource &from) {
   if (chol_pipe_usable(c, p.D)) {
     // one launch: the factor workgroup's chain stays inside a compute unit, the carried columns follow through flags (k_chol.h)
     HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
     HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
-    const int slot = (c->chol_slot++) & 1; // two factorisations may be in flight on the two streams
+    const int slot = chol_next_slot(c);
     chol::CholParams q;
     q.D = p.D, q.LA = p.LA, q.A = p.A, q.Y = p.Y, q.Lt = Lt, q.flags = p.flags, q.diag0 = p.diag0, q.pivot_tol = p.pivot_tol, q.pred = p.pred;
-    q.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot, q.uinv = c->chol_uinv.p + (size_t)slot * 16 * 256, q.err = p.flags + 2, q.dbg = c->dbg_cycles.p;
-    q.spin_limit = c->chol_spin_limit;
-    q.n_arrive = chol::chol_tile_waves((p.D + 15) / 16);
     q.src = from.src, q.N = p.N, q.pred_not = p.pred_not;
     if (from.src != chol::CH_SRC_MATRIX) {
       const TformParams &t = *from.t;
       q.col_cov = t.col_cov, q.P = t.P, q.G = t.G, q.LG = t.LG, q.inv_sigma2 = t.inv_sigma2, q.Y1 = t.Y1;
     }
-    c->last_uinv = q.uinv;
-    HIPCHK(ctrl_zero(c, slot ? CTRL_PROG1 : CTRL_PROG0, q.prog, 16 * sizeof(int32_t), s));
-    const int carried = (p.LA - p.D + 15) / 16;
-    // ONE launch (round 5): block 0 factors, the others carry the columns next to it (k_chol.h).  Until round 4 the carried columns were a
-    // kernel of their own that had to run NEXT TO the factor kernel, i.e. on a helper stream behind an event, with a second event to join
-    // it: each hand-over cost the stream ~6-13 us whichever side carried it (profiles/r05_c_timeline_*: 13 us between k_gram_reduce and
-    // the second factorisation, 14 us behind k_tf_tail).
-    static bool attr_f2 = false;
-    if (!attr_f2) {
-      (void)hipFuncSetAttribute((const void *)chol::k_chol_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol::chol_lds_bytes());
-      attr_f2 = true;
-    }
-    hipLaunchKernelGGL(chol::k_chol_fused, dim3(1 + (carried + chol::CH_FC - 1) / chol::CH_FC), dim3(64 * (chol::CH_FW + 1)), chol::chol_lds_bytes(), s, q);
-    HIPCHK(hipGetLastError());
-    return OVGPU_OK;
+    HIPCHK(ctrl_zero(c, slot ? CTRL_PROG1 : CTRL_PROG0, c->chol_prog.p + CHOL_PROG_STRIDE * slot, 16 * sizeof(int32_t), s));
+    return launch_chol_fused(c, q, slot, s);
   }
   if (from.src != chol::CH_SRC_MATRIX) return set_err(OVGPU_ERR_INVALID, "the step-wise factorisation needs its work matrix assembled");
   const int TM = (p.D + 15) / 16, TL = (p.LA + 15) / 16;
@@ -983,6 +989,24 @@ static int check_tree_error(ovgpu_ctx *c) {
   return OVGPU_OK;
 }
 
+// The four flag words of an update (or of a chain of them) as the call's result: a follower's time-out comes first (c->chol_timed_out,
+// OVGPU_ERR_HIP; stats->status is left alone), then a pivot that failed, then a negative diagonal.  The texts are the call site's own.
+struct FlagText {
+  std::string timed_out, not_spd, neg_diag;
+};
+#define CHOL_TIMED_OUT "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup"
+#define CHOL_STEPWISE_HINT " (options.no_single_launch_cholesky = 1 selects the step-wise kernels)"
+static const FlagText UPDATE_FLAG_TEXT{CHOL_TIMED_OUT "; the state was not modified" CHOL_STEPWISE_HINT, "innovation covariance not SPD",
+                                       "negative covariance diagonal after the update"};
+static int decode_update_flags(ovgpu_ctx *c, const int32_t fl[4], ovgpu_update_stats *stats, const FlagText &where) {
+  c->chol_timed_out = fl[2] != 0;
+  if (fl[2]) return set_err(OVGPU_ERR_HIP, where.timed_out);
+  const int status = fl[0] ? OVGPU_ERR_NOT_SPD : (fl[1] ? OVGPU_ERR_NEGATIVE_DIAGONAL : OVGPU_OK);
+  if (stats) stats->status = status;
+  if (status != OVGPU_OK) return set_err(status, fl[0] ? where.not_spd : where.neg_diag);
+  return OVGPU_OK;
+}
+
 // with_lm: the resident landmark values land behind P' (ovgpu_msckf_update_lm)
 static size_t finish_update_bytes(const ovgpu_ctx *c, bool with_lm = false) {
   const size_t N = (size_t)c->N;
@@ -1008,15 +1032,10 @@ static int finish_update(ovgpu_ctx *c, double *dx, double *P_out, ovgpu_update_s
     if (P_out) std::memcpy(P_out, h + o_P, sizeof(double) * N * N);
     if (n_lm) std::memcpy(lm_out, h + o_lm, n_lm);
   }
-  int status = OVGPU_OK;
-  if (flags[0]) status = OVGPU_ERR_NOT_SPD;
-  else if (flags[1]) status = OVGPU_ERR_NEGATIVE_DIAGONAL;
-  c->chol_timed_out = flags[2] != 0;
-  if (flags[2]) return set_err(OVGPU_ERR_HIP, "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup; the state was not modified (options.no_single_launch_cholesky = 1 selects the step-wise kernels)");
-  if (stats) stats->status = status;
+  const int status = decode_update_flags(c, flags, stats, UPDATE_FLAG_TEXT);
+  if (c->chol_timed_out) return status;
   fill_times(c, stats);
-  if (status != OVGPU_OK) return set_err(status, status == OVGPU_ERR_NOT_SPD ? "innovation covariance not SPD" : "negative covariance diagonal after the update");
-  return check_tree_error(c);
+  return status != OVGPU_OK ? status : check_tree_error(c);
 }
 
 // Runs `attempt` (enqueue -> read back -> finish_update) and repeats it when the failure is one that left the resident state untouched:

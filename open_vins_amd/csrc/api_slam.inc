@@ -1,4 +1,7 @@
 // api_slam.inc — part of ovgpu_api.hip (ONE translation unit, included in order; not a stand-alone header): UpdaterSLAM: landmarks, ovgpu_slam_update / compress, ovgpu_slam_delayed_init, anchor changes, per-feature options.
+// Shared host steps: enqueue_slam_step (one SLAM update on the stream: the single call and every chunk), state_segs / state_snapshot (the moving
+// state set aside and put back: the chunked call and mode A), InitChain / begin_init_chain (the set-up of both delayed-initialisation entries).
+// From api_state.inc: copy_reset_baseline, cov_resize; from api_pipeline.inc: launch_chol_fused, decode_update_flags.
 // ---------------------------------------------------------------------------
 // UpdaterSLAM::update (UpdaterSLAM.cpp:253-479), GLOBAL_3D landmarks
 // ---------------------------------------------------------------------------
@@ -34,7 +37,7 @@ int ovgpu_set_landmarks(ovgpu_ctx *c, const ovgpu_landmarks_view *lm) {
     if (reps[l] < OVGPU_REP_ANCHORED_3D) continue;
     if (lm->anchor_cam[l] < 0 || lm->anchor_cam[l] >= c->K || lm->anchor_clone[l] < 0 || lm->anchor_clone[l] >= c->C)
       return set_err(OVGPU_ERR_INVALID, "landmark anchor refers to an unknown clone / camera");
-    anc[l] = (lm->anchor_cam[l] << 10) | lm->anchor_clone[l];
+    anc[l] = anchor_pack(lm->anchor_cam[l], lm->anchor_clone[l]);
   }
   HIPCHK(hipSetDevice(c->device));
   c->L = lm->L;
@@ -89,8 +92,8 @@ int ovgpu_get_landmarks(ovgpu_ctx *c, int32_t *L_out, double *value, double *fej
   }
   HIPCHK(upload_sync(c, s));
   for (int l = 0; l < L; l++) {
-    if (anchor_cam) anchor_cam[l] = anc[l] >= 0 ? anc[l] >> 10 : -1;
-    if (anchor_clone) anchor_clone[l] = anc[l] >= 0 ? (anc[l] & 1023) : -1;
+    if (anchor_cam) anchor_cam[l] = ovg::anchor_cam(anc[l]);
+    if (anchor_clone) anchor_clone[l] = ovg::anchor_clone(anc[l]);
   }
   return OVGPU_OK;
 }
@@ -102,9 +105,27 @@ int ovgpu_get_landmark_reps(ovgpu_ctx *c, int32_t *L_out, int32_t *feat_rep) {
   return OVGPU_OK;
 }
 
-// per-feature landmark data of a SLAM batch, gathered on the device from the resident landmarks; the triangulation stage
-// is replaced by the state's landmark estimates
-static int slam_prepare(ovgpu_ctx *c, const int32_t *lm_index, ovgpu_update_stats *stats) {
+// One SLAM update on the stream for the F features whose landmarks lm_index_dev names: their per-feature landmark data gathered from the
+// resident landmarks, the system and the EKF update, the resident landmarks' share of dx.  No upload, no wait.
+static int enqueue_slam_gather(ovgpu_ctx *c, int F, const int32_t *lm_index_dev) {
+  if (F <= 0) return OVGPU_OK;
+  hipLaunchKernelGGL(k_slam_gather, dim3((F + 255) / 256), dim3(256), 0, c->stream, F, lm_index_dev, (const int32_t *)c->meas_offsets.p, landmark_store(c), c->pG.p,
+                     c->pA.p, c->pFej.p, c->feat_lm.p, c->feat_lmcol.p, c->feat_lmcov.p, c->feat_anchor.p, c->given_status.p);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+static int enqueue_slam_step(ovgpu_ctx *c, int F, const int32_t *lm_index_dev) {
+  int rc = enqueue_slam_gather(c, F, lm_index_dev);
+  if (rc != OVGPU_OK || (rc = enqueue_pipeline(c, STAGE_LOCAL | STAGE_EKF, true)) != OVGPU_OK) return rc;
+  hipLaunchKernelGGL(k_landmark_update, dim3((3 * c->L + 255) / 256), dim3(256), 0, c->stream, c->L, (const int32_t *)nullptr, (const int32_t *)c->lm_repd.p, c->dx.p,
+                     c->lm_cov.p, c->lm_val.p, (const int32_t *)nullptr);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+// per-feature landmark data of a SLAM batch, gathered on the device from the resident landmarks (`gather`; ovgpu_slam_update leaves it to
+// enqueue_slam_step); the triangulation stage is replaced by the state's landmark estimates
+static int slam_prepare(ovgpu_ctx *c, const int32_t *lm_index, ovgpu_update_stats *stats, bool gather = true) {
   if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
   if (c->L <= 0) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_landmarks was never called");
   if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features must follow ovgpu_set_landmarks");
@@ -134,9 +155,8 @@ static int slam_prepare(ovgpu_ctx *c, const int32_t *lm_index, ovgpu_update_stat
   if (F > 0) {
     HIPCHK(upload(c->lm_index.p, lm_index, sizeof(int32_t) * F, s));
     HIPCHK(upload_sync(c, s));
-    hipLaunchKernelGGL(k_slam_gather, dim3((F + 255) / 256), dim3(256), 0, s, F, c->lm_index.p, c->meas_offsets.p, landmark_store(c), c->pG.p,
-                       c->pA.p, c->pFej.p, c->feat_lm.p, c->feat_lmcol.p, c->feat_lmcov.p, c->feat_anchor.p, c->given_status.p);
-    HIPCHK(hipGetLastError());
+    const int rcg = gather ? enqueue_slam_gather(c, F, c->lm_index.p) : (int)OVGPU_OK;
+    if (rcg != OVGPU_OK) return rcg;
   }
   c->given_tri = true; // positions come from the state: no triangulation stage
   return OVGPU_OK;
@@ -144,15 +164,12 @@ static int slam_prepare(ovgpu_ctx *c, const int32_t *lm_index, ovgpu_update_stat
 
 int ovgpu_slam_update(ovgpu_ctx *c, const int32_t *lm_index, int32_t *feat_status, double *chi2, double *chi2_thresh, double *dx, double *P_out,
                       double *lm_out, ovgpu_update_stats *stats) {
-  int rc = slam_prepare(c, lm_index, stats);
+  int rc = slam_prepare(c, lm_index, stats, false);
   if (rc != OVGPU_OK) return rc;
   hipStream_t s = c->stream;
   return update_with_fallbacks(c, stats, [&]() {
-    int rc2 = enqueue_pipeline(c, STAGE_LOCAL | STAGE_EKF, true);
+    int rc2 = enqueue_slam_step(c, c->F, c->lm_index.p); // (a repeat gathers again: the failed attempt left the landmarks as they were)
     if (rc2 != OVGPU_OK) return rc2;
-    hipLaunchKernelGGL(k_landmark_update, dim3((3 * c->L + 255) / 256), dim3(256), 0, s, c->L, (const int32_t *)nullptr, (const int32_t *)c->lm_repd.p, c->dx.p,
-                       c->lm_cov.p, c->lm_val.p, (const int32_t *)nullptr);
-    HIPCHK(hipGetLastError());
     PendingFeatOut pend; // one synchronisation for the per-feature outputs, the landmarks and dx / P'
     if ((rc2 = read_feature_outputs(c, feat_status, chi2, chi2_thresh, nullptr, stats, &pend, finish_update_bytes(c))) != OVGPU_OK) return rc2;
     if (lm_out) HIPCHK(hipMemcpyAsync(lm_out, c->lm_val.p, sizeof(double) * 3 * c->L, hipMemcpyDeviceToHost, s));
@@ -249,12 +266,7 @@ static int enqueue_chunk(ovgpu_ctx *c, const ChunkPlan &pl, const BatchView &w, 
     if (c->h_row_off[i] != pl.row_off[(size_t)f0 + k + i]) return set_err(OVGPU_ERR_INVALID, "internal: a chunk's row layout differs from the plan's");
   c->have_feats = true, c->given_tri = true;
   // ---- the single call's launches
-  hipLaunchKernelGGL(k_slam_gather, dim3((Fk + 255) / 256), dim3(256), 0, s, Fk, (const int32_t *)(c->chk_tab.p + pl.o_lm + f0), (const int32_t *)c->meas_offsets.p,
-                     landmark_store(c), c->pG.p, c->pA.p, c->pFej.p, c->feat_lm.p, c->feat_lmcol.p, c->feat_lmcov.p, c->feat_anchor.p, c->given_status.p);
-  HIPCHK(hipGetLastError());
-  if ((rc = enqueue_pipeline(c, STAGE_LOCAL | STAGE_EKF, true)) != OVGPU_OK) return rc;
-  hipLaunchKernelGGL(k_landmark_update, dim3((3 * c->L + 255) / 256), dim3(256), 0, s, c->L, (const int32_t *)nullptr, (const int32_t *)c->lm_repd.p, c->dx.p,
-                     c->lm_cov.p, c->lm_val.p, (const int32_t *)nullptr);
+  if ((rc = enqueue_slam_step(c, Fk, c->chk_tab.p + pl.o_lm + f0)) != OVGPU_OK) return rc;
   ChunkCollect cc;
   cc.N = c->N, cc.dx = c->dx.p, cc.flags = c->flags.p, cc.gate = c->rows_used.p + 1;
   cc.dx_row = c->chk_dx.p + (size_t)k * c->N, cc.flags_out = c->chk_flags.p + 4 * k, cc.gate_out = c->chk_flags.p + 4 * pl.n + k;
@@ -263,17 +275,26 @@ static int enqueue_chunk(ovgpu_ctx *c, const ChunkPlan &pl, const BatchView &w, 
   return OVGPU_OK;
 }
 
-static int chunk_state_copy(ovgpu_ctx *c, bool put_back) {
-  const int C = c->C, K = c->K, L = c->L;
-  const size_t N = (size_t)c->N;
-  double *sv = c->chk_save.p;
-  double *live[CHUNK_COPY_SEGS] = {c->P.p, c->clone_qp.p, c->calib_qp.p, c->intr.p, c->lm_val.p};
-  const size_t len[CHUNK_COPY_SEGS] = {N * N, (size_t)7 * C, (size_t)7 * K, (size_t)8 * K, (size_t)3 * L};
+// The part of the resident state that an update moves, as k_chunk_copy's segments: P (with_P; mode A of the delayed initialisation keeps P in
+// Ppad instead) | clone_qp | calib_qp | intr | lm_val.  The one place that knows this layout.
+struct StateSegs {
+  double *live[CHUNK_COPY_SEGS];
+  size_t len[CHUNK_COPY_SEGS], total;
+};
+static StateSegs state_segs(const ovgpu_ctx *c, bool with_P) {
+  const size_t N = (size_t)c->N, C = (size_t)c->C, K = (size_t)c->K, L = (size_t)c->L;
+  StateSegs g{{c->P.p, c->clone_qp.p, c->calib_qp.p, c->intr.p, c->lm_val.p}, {with_P ? N * N : 0, 7 * C, 7 * K, 8 * K, 3 * L}, 0};
+  for (size_t n : g.len) g.total += n;
+  return g;
+}
+// those segments set aside in `save` (state_segs(..).total doubles) or, put_back, brought back from it: one launch
+static int state_snapshot(ovgpu_ctx *c, double *save, bool with_P, bool put_back) {
+  const StateSegs g = state_segs(c, with_P);
   ChunkCopy q;
   size_t off = 0;
   for (int i = 0; i < CHUNK_COPY_SEGS; i++) {
-    q.dst[i] = put_back ? live[i] : sv + off, q.src[i] = put_back ? sv + off : live[i], q.n[i] = (uint32_t)len[i];
-    off += len[i];
+    q.dst[i] = put_back ? g.live[i] : save + off, q.src[i] = put_back ? save + off : g.live[i], q.n[i] = (uint32_t)g.len[i];
+    off += g.len[i];
   }
   hipLaunchKernelGGL(k_chunk_copy, dim3(UP_BLOCKS, CHUNK_COPY_SEGS), dim3(256), 0, c->stream, q);
   HIPCHK(hipGetLastError());
@@ -365,7 +386,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     HIPCHK(c->chk_rowoff.reserve((size_t)F + n));
     HIPCHK(c->chk_flags.reserve((size_t)5 * n));
     HIPCHK(c->chk_dx.reserve((size_t)n * N));
-    HIPCHK(c->chk_save.reserve((size_t)N * N + 7 * (size_t)c->C + 15 * (size_t)c->K + 3 * (size_t)L));
+    HIPCHK(c->chk_save.reserve(state_segs(c, true).total));
   }
   // ---- one upload
   pl.tab.assign(pl.first.begin(), pl.first.end());
@@ -382,7 +403,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
   HIPCHK(hipMemsetAsync(c->chk_dx.p, 0, sizeof(double) * (size_t)n * N, s));
-  int rc = chunk_state_copy(c, false); // the entry state, for the restore-and-chain path
+  int rc = state_snapshot(c, c->chk_save.p, true, false); // the entry state, for the restore-and-chain path
   if (rc != OVGPU_OK) return rc;
   // ---- every chunk, one after the other on the stream
   BatchView w;
@@ -438,7 +459,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     // behind it ran on a state the chain would not have produced: the entry state comes back and the chunks run as the chain of single calls
     // runs them, one synchronisation and update_with_fallbacks each.  Correct, slower and rare; counted.
     c->chunk_fallbacks++;
-    if ((rc = chunk_state_copy(c, true)) != OVGPU_OK) return rc;
+    if ((rc = state_snapshot(c, c->chk_save.p, true, true)) != OVGPU_OK) return rc;
     if ((rc = launch_build_tables(c)) != OVGPU_OK) return rc;
     HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
     HIPCHK(hipMemsetAsync(c->chk_dx.p, 0, sizeof(double) * (size_t)n * N, s));
@@ -452,11 +473,8 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
         if (rc2 != OVGPU_OK) return rc2;
         if (hipMemcpyAsync(fl, c->chk_flags.p + 4 * k, sizeof(fl), hipMemcpyDeviceToHost, s) != hipSuccess || upload_sync(c, s) != hipSuccess)
           return set_err(OVGPU_ERR_HIP, "read-back of a chunk's flag words failed");
-        c->chol_timed_out = fl[2] != 0;
-        if (fl[2]) return set_err(OVGPU_ERR_HIP, "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup; the state was not modified");
-        if (fl[0]) return set_err(OVGPU_ERR_NOT_SPD, "chunk " + std::to_string(k) + ": innovation covariance not SPD");
-        if (fl[1]) return set_err(OVGPU_ERR_NEGATIVE_DIAGONAL, "chunk " + std::to_string(k) + ": negative covariance diagonal after the update");
-        return (int)OVGPU_OK;
+        const std::string chunk = "chunk " + std::to_string(k) + ": ";
+        return decode_update_flags(c, fl, nullptr, {CHOL_TIMED_OUT "; the state was not modified", chunk + "innovation covariance not SPD", chunk + "negative covariance diagonal after the update"});
       });
       if (status == OVGPU_OK || status == OVGPU_ERR_NEGATIVE_DIAGONAL || status == OVGPU_ERR_NOT_SPD) k_done = k + 1;
       if (stats && pl.first[k + 1] > pl.first[k]) stats[k].status = status;
@@ -547,7 +565,7 @@ static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, do
   p.clone_qp = c->clone_qp.p, p.calib_qp = c->calib_qp.p, p.intr = c->intr.p, p.clone_fej = c->clone_fej.p;
   p.tab_clone = c->tab_clone.p, p.tab_cam = c->tab_cam.p, p.tab_cc = c->tab_cc.p;
   p.p_FinG = c->pG.p, p.p_FinA = c->pA.p, p.meas_cc = c->meas_cc.p, p.anchor_meas = c->anchor.p, p.lm = landmark_store(c), p.feat_slot = c->feat_slot.p;
-  const int slot = (c->chol_slot++) & 1;
+  const int slot = chol_next_slot(c);
   p.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot;
   c->ctrl_clean &= ~(slot ? CTRL_PROG1 : CTRL_PROG0), c->ctrl_pre &= ~(slot ? CTRL_PROG1 : CTRL_PROG0); // (the step words are k_initf_s's to clear, and dirty afterwards)
   const int tn = (Nmax + 15) / 16, tw = (r + 3 + 15) / 16, tm = (r + 15) / 16;
@@ -555,18 +573,82 @@ static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, do
   hipLaunchKernelGGL(k_initf_s, dim3((tm * tw + 3) / 4 + 1), dim3(256), 0, s, p);
   chol::CholParams q;
   q.D = r, q.LA = p.LA, q.A = p.A, q.Y = c->Yaug.p, q.Lt = nullptr, q.flags = c->flags.p, q.diag0 = nullptr, q.pivot_tol = 1e-13, q.pred = c->init_ctr.p + 2;
-  q.prog = p.prog, q.uinv = c->chol_uinv.p + (size_t)slot * 16 * 256, q.err = c->flags.p + 2, q.dbg = c->dbg_cycles.p;
-  q.spin_limit = c->chol_spin_limit, q.n_arrive = chol::chol_tile_waves(tm), q.src = chol::CH_SRC_MATRIX, q.N = Nmax, q.pred_not = nullptr;
-  c->last_uinv = q.uinv;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)chol::k_chol_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol::chol_lds_bytes());
-    attr = true;
-  }
-  const int carried = (p.LA - r + 15) / 16;
-  hipLaunchKernelGGL(chol::k_chol_fused, dim3(1 + (carried + chol::CH_FC - 1) / chol::CH_FC), dim3(64 * (chol::CH_FW + 1)), chol::chol_lds_bytes(), s, q);
+  q.src = chol::CH_SRC_MATRIX, q.N = Nmax, q.pred_not = nullptr;
+  if ((rc = launch_chol_fused(c, q, slot, s)) != OVGPU_OK) return rc;
   hipLaunchKernelGGL(k_initf_tail, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p);
   HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
+// the representation feature f is initialised in: the call's, or ovgpu_set_feature_reps' (UpdaterSLAM.cpp:160-166: feat_rep_aruco for an
+// ArUco corner, feat_rep_slam otherwise); the resident landmarks keep their own
+static int feat_rep_of(const ovgpu_ctx *c, int32_t feat_rep, int f) { return ((int)c->h_feat_rep.size() == c->F && c->F > 0) ? (int)c->h_feat_rep[f] : (int)feat_rep; }
+
+// What the chain's set-up leaves for the per-feature steps of both delayed-initialisation entries
+struct InitChain {
+  int N0 = 0, L0 = 0, Nmax = 0, r_max = 1; // dimension and landmarks at entry, the padded capacity, the most rows of one EKF update
+  size_t init_lds = 0;                     // k_init_invertible's dynamic LDS
+  std::vector<int32_t> rep;                // feat_rep_of every feature
+  // mode A (ovgpu_slam_init_systems) sets these before the call; null otherwise
+  double *save = nullptr;                  // the moving state is set aside here ahead of the triangulation (state_snapshot)
+  const std::vector<int32_t> *up_src = nullptr; // a second upload under the set-up's one synchronisation ...
+  int32_t *up_dst = nullptr;                    // ... and where it goes
+};
+
+// The chain's set-up for the features [first, F): the 48 / 72 row layout, the workspaces, the triangulation (or the caller's), P padded to the
+// capacity N0 + the candidates' dof (the rows / columns of landmarks that do not exist yet are zero), the device counters, the cleared flags.
+static int begin_init_chain(ovgpu_ctx *c, int32_t feat_rep, int first, bool fused, InitChain &ch) {
+  const int F = c->F;
+  hipStream_t s = c->stream;
+  ch.N0 = ch.Nmax = c->N, ch.L0 = c->L, ch.r_max = 1;
+  ch.rep.assign(std::max(F, 1), feat_rep);
+  for (int f = 0; f < F; f++) ch.rep[f] = feat_rep_of(c, feat_rep, f);
+  bool new_anchored = false;
+  for (int f = first; f < F; f++) {
+    ch.Nmax += lm_dof(ch.rep[f]), new_anchored = new_anchored || ch.rep[f] >= OVGPU_REP_ANCHORED_3D;
+    ch.r_max = std::max(ch.r_max, 2 * (c->h_offsets[f + 1] - c->h_offsets[f]) - 3);
+  }
+  // the per-feature kernel needs the anchor blocks in its row store for an anchored representation
+  const int want_stride = (new_anchored || c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D || lm_any_anchored(c)) ? 72 : 48;
+  if (c->slam_rows || want_stride != c->row_stride) {
+    c->row_stride = want_stride;
+    const int rcl = set_row_layout(c, false);
+    if (rcl != OVGPU_OK) return rcl;
+  }
+  // ---- workspaces.  One size for every entry, the largest any of them needs: init_ws holds k_init_fused.h's T and P_LL behind the system's
+  // three rows and R1, init_ctr the fused tail's arrival count in [4], dx_seq a row per feature (mode A uses the first).
+  const size_t Nmax = (size_t)ch.Nmax, rD = (size_t)std::max(ch.r_max, c->D);
+  int rc = reserve_landmarks(c, ch.L0 + F, ch.L0);
+  if (rc != OVGPU_OK) return rc;
+  HIPCHK(c->Ppad.reserve(Nmax * Nmax));
+  HIPCHK(c->init_ws.reserve((size_t)3 * c->LD + 16 + 3 * Nmax + 16));
+  HIPCHK(c->init_ctr.reserve(8));
+  HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
+  HIPCHK(c->dx_seq.reserve((size_t)std::max(F, 1) * Nmax));
+  if (fused) {
+    HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
+    HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
+  }
+  HIPCHK(c->Mt.reserve(rD * Nmax));
+  HIPCHK(c->Aaug.reserve(rD * (rD + Nmax + 1)));
+  HIPCHK(c->Yaug.reserve(rD * (rD + Nmax + 1)));
+  HIPCHK(c->dx.reserve(Nmax));
+  if (ch.save && (rc = state_snapshot(c, ch.save, false, false)) != OVGPU_OK) return rc;
+  // ---- triangulate every feature against the clone poses at entry (UpdaterSLAM.cpp:121-144), or take the caller's (ovgpu_set_triangulation)
+  if (!c->given_tri) {
+    if ((rc = enqueue_triangulate(c)) != OVGPU_OK) return rc;
+  } else if (F > 0) {
+    HIPCHK(hipMemcpyAsync(c->status.p, c->given_status.p, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
+  }
+  if ((rc = cov_resize(c, ch.N0, ch.Nmax, ch.N0)) != OVGPU_OK) return rc; // (the entry's P waits in Ppad)
+  const int32_t ctr0[8] = {ch.N0, ch.L0, 0, 0, 0, 0, 0, 0};
+  HIPCHK(upload(c->init_ctr.p, ctr0, sizeof(ctr0), s));
+  if (ch.up_src && !ch.up_src->empty()) HIPCHK(upload(ch.up_dst, ch.up_src->data(), sizeof(int32_t) * ch.up_src->size(), s));
+  HIPCHK(upload_sync(c, s)); // ctr0 is a stack variable
+  HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
+  if (!ch.save) HIPCHK(hipMemsetAsync(c->dx_seq.p, 0, sizeof(double) * (size_t)std::max(F, 1) * Nmax, s)); // (mode A hands no dx out)
+  HIPCHK(hipMemsetAsync(c->feat_slot.p, 0xFF, sizeof(int32_t) * std::max(F, 1), s));
+  ch.init_lds = ((size_t)3 * c->LD + 3 * Nmax + 16) * sizeof(double);
   return OVGPU_OK;
 }
 
@@ -583,71 +665,21 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   if (c->cols_over) return set_err(OVGPU_ERR_CAPACITY, c->cols_over_msg);
   HIPCHK(hipSetDevice(c->device));
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  // the representation each feature is initialised in: the call's, or ovgpu_set_feature_reps' (UpdaterSLAM.cpp:160-166: feat_rep_aruco for an
-  // ArUco corner, feat_rep_slam otherwise); the resident landmarks keep their own
-  const int F = c->F, N0 = c->N, L0 = c->L;
-  const bool per_feature = (int)c->h_feat_rep.size() == F && F > 0;
-  auto rep_of = [&](int f) { return per_feature ? (int)c->h_feat_rep[f] : (int)feat_rep; };
-  int Nmax = N0;
-  bool new_anchored = false;
-  for (int f = 0; f < F; f++) Nmax += lm_dof(rep_of(f)), new_anchored = new_anchored || rep_of(f) >= OVGPU_REP_ANCHORED_3D;
-  hipStream_t s = c->stream;
-  // the per-feature kernel needs the anchor blocks in its row store for an anchored representation
-  const int want_stride = (new_anchored || c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D || lm_any_anchored(c)) ? 72 : 48;
-  if (c->slam_rows || want_stride != c->row_stride) {
-    c->row_stride = want_stride;
-    const int rcl = set_row_layout(c, false);
-    if (rcl != OVGPU_OK) return rcl;
-  }
-  int r_max = 1;
-  for (int f = 0; f < F; f++) r_max = std::max(r_max, 2 * (c->h_offsets[f + 1] - c->h_offsets[f]) - 3);
-  // ---- workspaces
-  int rc = reserve_landmarks(c, L0 + F, L0);
+  InitChain ch;
+  int rc = begin_init_chain(c, feat_rep, 0, fused, ch);
   if (rc != OVGPU_OK) return rc;
-  HIPCHK(c->Ppad.reserve((size_t)Nmax * Nmax));
-  HIPCHK(c->init_ws.reserve((size_t)3 * c->LD + 16 + (size_t)3 * Nmax + 16)); // (behind the system's three rows and R1: k_init_fused.h's T and P_LL)
-  HIPCHK(c->init_ctr.reserve(8));
-  HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
-  HIPCHK(c->dx_seq.reserve((size_t)std::max(F, 1) * Nmax));
-  if (fused) {
-    HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
-    HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
-  }
-  HIPCHK(c->Mt.reserve((size_t)std::max(r_max, c->D) * Nmax));
-  HIPCHK(c->Aaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
-  HIPCHK(c->Yaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
-  HIPCHK(c->dx.reserve(Nmax));
-  // ---- 3. triangulate every feature against the clone poses at entry (UpdaterSLAM.cpp:121-144)
-  if (!c->given_tri) {
-    if ((rc = enqueue_triangulate(c)) != OVGPU_OK) return rc;
-  } else if (F > 0) {
-    HIPCHK(hipMemcpyAsync(c->status.p, c->given_status.p, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
-  }
-  // ---- covariance -> padded capacity
-  {
-    dim3 g((Nmax + 255) / 256, Nmax);
-    hipLaunchKernelGGL(k_cov_copy, g, dim3(256), 0, s, N0, Nmax, c->P.p, N0, c->Ppad.p, Nmax);
-    HIPCHK(hipGetLastError());
-    std::swap(c->P, c->Ppad);
-    c->N = Nmax;
-  }
-  const int32_t ctr0[8] = {N0, L0, 0, 0, 0, 0, 0, 0}; // ([4]: the fused tail's arrival count)
-  HIPCHK(upload(c->init_ctr.p, ctr0, sizeof(ctr0), s));
-  HIPCHK(upload_sync(c, s)); // ctr0 is a stack variable
-  HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
-  HIPCHK(hipMemsetAsync(c->dx_seq.p, 0, sizeof(double) * (size_t)std::max(F, 1) * Nmax, s));
-  HIPCHK(hipMemsetAsync(c->feat_slot.p, 0xFF, sizeof(int32_t) * std::max(F, 1), s));
-  const size_t init_lds = ((size_t)3 * c->LD + (size_t)3 * Nmax + 16) * sizeof(double);
+  const int F = c->F, N0 = ch.N0, L0 = ch.L0, Nmax = ch.Nmax;
+  hipStream_t s = c->stream;
   // ---- 4. one feature after the other (UpdaterSLAM.cpp:147-239)
   for (int f = 0; f < F && rc == OVGPU_OK; f++) {
     const int m = c->h_offsets[f + 1] - c->h_offsets[f];
     if (m < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
     if (fused && c->init_fused_on && initf_holds(c, m)) {
-      rc = enqueue_init_feature_fused(c, f, rep_of(f), Nmax, c->dx_seq.p + (size_t)f * Nmax);
+      rc = enqueue_init_feature_fused(c, f, ch.rep[f], Nmax, c->dx_seq.p + (size_t)f * Nmax);
       c->init_fused_steps++;
       continue;
     }
-    rc = enqueue_init_feature(c, f, rep_of(f), Nmax, L0 + F, init_lds, c->dx_seq.p + (size_t)f * Nmax, nullptr);
+    rc = enqueue_init_feature(c, f, ch.rep[f], Nmax, L0 + F, ch.init_lds, c->dx_seq.p + (size_t)f * Nmax, nullptr);
     if (fused) c->init_chain_steps++; // (a track beyond the fused step's bound, or "delayed_init_fused" = 0)
   }
   // ---- results
@@ -663,17 +695,8 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   const int N1 = ctr[0], L1 = ctr[1];
   // covariance back to its own leading dimension; it is the new baseline of ovgpu_reset_state as well
   {
-    HIPCHK(c->Ppad.reserve((size_t)N1 * N1));
-    dim3 g((N1 + 255) / 256, N1);
-    hipLaunchKernelGGL(k_cov_copy, g, dim3(256), 0, s, N1, N1, c->P.p, Nmax, c->Ppad.p, N1);
-    HIPCHK(hipGetLastError());
-    std::swap(c->P, c->Ppad);
-    c->N = N1;
-    HIPCHK(c->P0.reserve((size_t)N1 * N1));
-    HIPCHK(hipMemcpyAsync(c->P0.p, c->P.p, sizeof(double) * N1 * N1, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->clone_qp0.p, c->clone_qp.p, sizeof(double) * 7 * c->C, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->calib_qp0.p, c->calib_qp.p, sizeof(double) * 7 * c->K, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->intr0.p, c->intr.p, sizeof(double) * 8 * c->K, hipMemcpyDeviceToDevice, s));
+    int rcb = cov_resize(c, N1, N1, Nmax);
+    if (rcb != OVGPU_OK || (rcb = copy_reset_baseline(c)) != OVGPU_OK) return rcb;
   }
   if (rc != OVGPU_OK) return rc;
   std::vector<double> val(3 * (size_t)std::max(L1, 1)), fej(3 * (size_t)std::max(L1, 1));
@@ -707,8 +730,8 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
     // Feature for every representation, and UpdaterSLAM.cpp:214 takes Landmark::_unique_camera_id from it)
     const int tri_anchor = (f < (int)tri_am.size() && tri_am[f] >= 0 && tri_am[f] < (int)tri_cc.size()) ? (int)tri_cc[tri_am[f]] : -1;
     const int a = (l >= 0 && anc[l] >= 0) ? anc[l] : tri_anchor;
-    if (anchor_cam) anchor_cam[f] = a >= 0 ? a >> 10 : -1;
-    if (anchor_clone) anchor_clone[f] = a >= 0 ? (a & 1023) : -1;
+    if (anchor_cam) anchor_cam[f] = ovg::anchor_cam(a);
+    if (anchor_clone) anchor_clone[f] = ovg::anchor_clone(a);
   }
   if (N_out) *N_out = N1;
   if (stats) stats->n_used = L1 - L0, stats->D = c->D;
@@ -716,7 +739,7 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   c->L = L1;
   c->h_lm_rep.resize(L1, feat_rep);
   for (int f = 0; f < F; f++)
-    if (slot[f] >= L0 && slot[f] < L1) c->h_lm_rep[slot[f]] = rep_of(f);
+    if (slot[f] >= L0 && slot[f] < L1) c->h_lm_rep[slot[f]] = ch.rep[f];
   c->h_lm_cov.assign(cov.begin(), cov.begin() + L1);
   c->h_lm_anchor.assign(anc.begin(), anc.begin() + L1);
   c->dx.release(), c->Mt.release(), c->Aaug.release(), c->Yaug.release(); // sized by the old N below
@@ -724,14 +747,7 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   rc = build_columns(c);
   if (rc != OVGPU_OK) return rc;
   c->tri_readable = true; // include/ovgpu.h: ovgpu_get_triangulation reads the triangulation of THIS call (the shim's delayed_init needs it for the Feature side effects)
-  int status = OVGPU_OK;
-  if (flags[0]) status = OVGPU_ERR_NOT_SPD;
-  else if (flags[1]) status = OVGPU_ERR_NEGATIVE_DIAGONAL;
-  c->chol_timed_out = flags[2] != 0;
-  if (flags[2]) return set_err(OVGPU_ERR_HIP, "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup; the state was not modified (options.no_single_launch_cholesky = 1 selects the step-wise kernels)");
-  if (stats) stats->status = status;
-  if (status != OVGPU_OK) return set_err(status, status == OVGPU_ERR_NOT_SPD ? "innovation covariance not SPD" : "negative covariance diagonal after the update");
-  return OVGPU_OK;
+  return decode_update_flags(c, flags, stats, UPDATE_FLAG_TEXT);
 }
 
 int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
@@ -774,7 +790,6 @@ static int init_sys_layout(ovgpu_ctx *c, int32_t feat_rep, int first, InitSysLay
   std::vector<uint16_t> cc(std::max(M, 1));
   if (M > 0) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(upload_sync(c, c->stream));
-  const bool per_feature = (int)c->h_feat_rep.size() == F && F > 0;
   std::vector<int32_t> col_of(std::max(c->N, 1), -1);
   for (int j = 0; j < c->D; j++) col_of[c->h_col_cov[j]] = j;
   lo = InitSysLayout();
@@ -786,11 +801,11 @@ static int init_sys_layout(ovgpu_ctx *c, int32_t feat_rep, int first, InitSysLay
     lo.var_off[f] = lo.tot.n_vars, lo.hx_off[f] = lo.tot.n_hx, lo.hf_off[f] = lo.tot.n_hf, lo.res_off[f] = lo.tot.n_res, lo.col_off[f] = (int64_t)lo.cols.size();
     const int m = c->h_offsets[f + 1] - c->h_offsets[f];
     if (f < first || m < 2) continue;
-    const bool single = (per_feature ? (int)c->h_feat_rep[f] : (int)feat_rep) == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE;
+    const bool single = feat_rep_of(c, feat_rep, f) == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE;
     vars.clear();
     std::fill(seen_clone.begin(), seen_clone.end(), 0), std::fill(seen_cam.begin(), seen_cam.end(), 0);
     for (int i = c->h_offsets[f]; i < c->h_offsets[f + 1]; i++) {
-      const int cam = cc[i] >> 10, cl = cc[i] & 1023;
+      const int cam = anchor_cam(cc[i]), cl = anchor_clone(cc[i]);
       if (!seen_clone[cl]) seen_clone[cl] = 1, vars.push_back({c->h_clone_cov[cl], 6});
       if (!seen_cam[cam]) {
         seen_cam[cam] = 1;
@@ -828,83 +843,35 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
   InitSysLayout lo;
   int rc = init_sys_layout(c, feat_rep, first_feature, lo);
   if (rc != OVGPU_OK) return rc;
-  const int F = c->F, N0 = c->N, L0 = c->L, C = c->C, K = c->K, first = first_feature;
+  const int F = c->F, first = first_feature;
   if (F > 0 && !sys) return set_err(OVGPU_ERR_INVALID, "null sys");
   if ((lo.tot.n_vars > 0 && (!var_id || !var_size)) || (lo.tot.n_hx > 0 && !H_x) || (lo.tot.n_hf > 0 && (!H_f || !res)))
     return set_err(OVGPU_ERR_INVALID, "null output arrays");
   if (cap->n_vars < lo.tot.n_vars || cap->n_hx < lo.tot.n_hx || cap->n_hf < lo.tot.n_hf || cap->n_res < lo.tot.n_res)
     return set_err(OVGPU_ERR_CAPACITY, "output capacities below ovgpu_slam_init_systems_len");
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  const bool per_feature = (int)c->h_feat_rep.size() == F && F > 0;
-  auto rep_of = [&](int f) { return per_feature ? (int)c->h_feat_rep[f] : (int)feat_rep; };
-  int Nmax = N0, r_max = 1;
-  bool new_anchored = false;
-  for (int f = first; f < F; f++) {
-    Nmax += lm_dof(rep_of(f)), new_anchored = new_anchored || rep_of(f) >= OVGPU_REP_ANCHORED_3D;
-    r_max = std::max(r_max, 2 * (c->h_offsets[f + 1] - c->h_offsets[f]) - 3);
-  }
   hipStream_t s = c->stream;
   // the row layout of the delayed initialisation (as ovgpu_slam_delayed_init); the batch's own is put back at the end
   const int stride0 = c->row_stride;
   const bool slam_rows0 = c->slam_rows;
-  const int want_stride = (new_anchored || c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D || lm_any_anchored(c)) ? 72 : 48;
-  if (c->slam_rows || want_stride != c->row_stride) {
-    c->row_stride = want_stride;
-    if ((rc = set_row_layout(c, false)) != OVGPU_OK) return rc;
-  }
-  // ---- workspaces
-  if ((rc = reserve_landmarks(c, L0 + F, L0)) != OVGPU_OK) return rc;
+  // ---- what the chain moves, kept aside: clones, calibration, intrinsics, the resident landmarks' values (P waits in Ppad)
   const size_t n_out = (size_t)(lo.tot.n_hx + lo.tot.n_hf + lo.tot.n_res);
-  const size_t n_save = (size_t)7 * C + 7 * K + 8 * K + 3 * L0;
-  HIPCHK(c->Ppad.reserve((size_t)Nmax * Nmax));
-  HIPCHK(c->init_ws.reserve((size_t)3 * c->LD + 16));
-  HIPCHK(c->init_ctr.reserve(4));
-  HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
-  HIPCHK(c->dx_seq.reserve(Nmax));
-  HIPCHK(c->Mt.reserve((size_t)std::max(r_max, c->D) * Nmax));
-  HIPCHK(c->Aaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
-  HIPCHK(c->Yaug.reserve((size_t)std::max(r_max, c->D) * (std::max(r_max, c->D) + Nmax + 1)));
-  HIPCHK(c->dx.reserve(Nmax));
   HIPCHK(c->isx_arena.reserve(std::max<size_t>(n_out, 1)));
   HIPCHK(c->isx_cols.reserve(std::max<size_t>(lo.cols.size(), 1)));
-  HIPCHK(c->isx_save.reserve(n_save));
-  // ---- what the chain moves, kept aside: clones, calibration, intrinsics, the resident landmarks' values
-  double *sv = c->isx_save.p;
-  HIPCHK(hipMemcpyAsync(sv, c->clone_qp.p, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(sv + 7 * C, c->calib_qp.p, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(sv + 7 * C + 7 * K, c->intr.p, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
-  if (L0 > 0) HIPCHK(hipMemcpyAsync(sv + 7 * C + 15 * K, c->lm_val.p, sizeof(double) * 3 * L0, hipMemcpyDeviceToDevice, s));
-  // ---- the triangulation at entry (UpdaterSLAM.cpp:121-144), or the caller's (ovgpu_set_triangulation: a restart)
-  if (!c->given_tri) {
-    if ((rc = enqueue_triangulate(c)) != OVGPU_OK) return rc;
-  } else if (F > 0) {
-    HIPCHK(hipMemcpyAsync(c->status.p, c->given_status.p, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
-  }
-  // ---- the chain works on a padded copy of P; the resident one waits in Ppad
-  {
-    dim3 g((Nmax + 255) / 256, Nmax);
-    hipLaunchKernelGGL(k_cov_copy, g, dim3(256), 0, s, N0, Nmax, c->P.p, N0, c->Ppad.p, Nmax);
-    HIPCHK(hipGetLastError());
-    std::swap(c->P, c->Ppad);
-    c->N = Nmax;
-  }
-  const int32_t ctr0[4] = {N0, L0, 0, 0};
-  HIPCHK(upload(c->init_ctr.p, ctr0, sizeof(ctr0), s));
-  if (!lo.cols.empty()) HIPCHK(upload(c->isx_cols.p, lo.cols.data(), sizeof(int32_t) * lo.cols.size(), s));
-  HIPCHK(upload_sync(c, s)); // (host sources on the stack)
-  HIPCHK(hipMemsetAsync(c->flags.p, 0, 4 * sizeof(int32_t), s));
-  HIPCHK(hipMemsetAsync(c->feat_slot.p, 0xFF, sizeof(int32_t) * std::max(F, 1), s));
-  const size_t init_lds = ((size_t)3 * c->LD + (size_t)3 * Nmax + 16) * sizeof(double);
+  HIPCHK(c->isx_save.reserve(state_segs(c, false).total));
+  InitChain ch;
+  ch.save = c->isx_save.p, ch.up_src = &lo.cols, ch.up_dst = c->isx_cols.p;
+  if ((rc = begin_init_chain(c, feat_rep, first, false, ch)) != OVGPU_OK) return rc;
   double *a_hx = c->isx_arena.p, *a_hf = a_hx + lo.tot.n_hx, *a_res = a_hf + lo.tot.n_hf;
   c->init_export = true;
   for (int f = first; f < F && rc == OVGPU_OK; f++) {
     if (lo.rows[f] == 0) continue; // fewer than two measurements: OVGPU_FEAT_TOO_FEW_MEAS
     InitExportParams ep;
-    ep.LD = c->LD, ep.D = c->D, ep.h = lo.h[f], ep.rows = lo.rows[f], ep.single = rep_of(f) == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE, ep.f = f;
+    ep.LD = c->LD, ep.D = c->D, ep.h = lo.h[f], ep.rows = lo.rows[f], ep.single = ch.rep[f] == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE, ep.f = f;
     ep.init_out = c->init_ws.p, ep.stack = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, ep.cols = c->isx_cols.p + lo.col_off[f];
     ep.feat_sigma = c->have_feat_sigma ? c->feat_sigma.p : nullptr, ep.sigma = std::sqrt(c->dopt.sigma_pix_sq);
     ep.Hx = a_hx + lo.hx_off[f], ep.Hf = a_hf + lo.hf_off[f], ep.res = a_res + lo.res_off[f];
-    rc = enqueue_init_feature(c, f, rep_of(f), Nmax, L0 + F, init_lds, c->dx_seq.p, &ep);
+    rc = enqueue_init_feature(c, f, ch.rep[f], ch.Nmax, ch.L0 + F, ch.init_lds, c->dx_seq.p, &ep);
   }
   c->init_export = false;
   // ---- results: one gather, one synchronisation
@@ -927,12 +894,12 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
     if (lo.tot.n_res > 0) HIPCHK(hipMemcpyAsync(res, a_res, sizeof(double) * lo.tot.n_res, hipMemcpyDeviceToHost, s));
   }
   // ---- the resident state as it was: P back from Ppad, the saved values, the pose tables, the batch's row layout
-  std::swap(c->P, c->Ppad);
-  c->N = N0;
-  HIPCHK(hipMemcpyAsync(c->clone_qp.p, sv, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->calib_qp.p, sv + 7 * C, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->intr.p, sv + 7 * C + 7 * K, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
-  if (L0 > 0) HIPCHK(hipMemcpyAsync(c->lm_val.p, sv + 7 * C + 15 * K, sizeof(double) * 3 * L0, hipMemcpyDeviceToDevice, s));
+  std::swap(c->P, c->Ppad); // (undoes begin_init_chain's cov_resize: no copy, the entry's P was never written)
+  c->N = ch.N0;
+  {
+    const int rcs = state_snapshot(c, c->isx_save.p, false, true);
+    if (rc == OVGPU_OK) rc = rcs;
+  }
   {
     const int rct = launch_build_tables(c);
     if (rc == OVGPU_OK) rc = rct;
@@ -953,7 +920,7 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
   for (int f = 0; f < F; f++) {
     ovgpu_init_system &o = sys[f];
     std::memset(&o, 0, sizeof(o));
-    o.feat_rep = rep_of(f);
+    o.feat_rep = ch.rep[f];
     o.var_off = lo.var_off[f], o.hx_off = lo.hx_off[f], o.hf_off = lo.hf_off[f], o.res_off = lo.res_off[f];
     o.chi2 = o.chi2_thresh = qnan;
     o.anchor_cam = o.anchor_clone = -1;
@@ -969,19 +936,12 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
       o.chi2 = x2[f], o.chi2_thresh = thr[f];
     }
     n_acc += slot[f] >= 0;
-    if (am[f] >= 0 && am[f] < c->M) o.anchor_cam = cc[am[f]] >> 10, o.anchor_clone = cc[am[f]] & 1023;
+    if (am[f] >= 0 && am[f] < c->M) o.anchor_cam = anchor_cam(cc[am[f]]), o.anchor_clone = anchor_clone(cc[am[f]]);
     const double *p = (o.feat_rep >= OVGPU_REP_ANCHORED_3D ? pA.data() : pG.data()) + 3 * f;
     for (int i = 0; i < 3; i++) o.p_seed[i] = p[i];
   }
   if (stats) stats->n_used = n_acc, stats->D = c->D;
-  int status = OVGPU_OK;
-  if (flags[0]) status = OVGPU_ERR_NOT_SPD;
-  else if (flags[1]) status = OVGPU_ERR_NEGATIVE_DIAGONAL;
-  c->chol_timed_out = flags[2] != 0;
-  if (flags[2]) return set_err(OVGPU_ERR_HIP, "single-launch Cholesky: a follower workgroup timed out waiting for the factor workgroup (options.no_single_launch_cholesky = 1 selects the step-wise kernels)");
-  if (stats) stats->status = status;
-  if (status != OVGPU_OK) return set_err(status, status == OVGPU_ERR_NOT_SPD ? "innovation covariance not SPD in the chain" : "negative covariance diagonal in the chain");
-  return OVGPU_OK;
+  return decode_update_flags(c, flags, stats, {CHOL_TIMED_OUT CHOL_STEPWISE_HINT, "innovation covariance not SPD in the chain", "negative covariance diagonal in the chain"});
 }
 
 // ---------------------------------------------------------------------------
@@ -1009,13 +969,7 @@ static int rebuild_variables(ovgpu_ctx *c) {
   HIPCHK(c->dx.reserve(N));
   int rc = build_columns(c); // synchronises
   if (rc != OVGPU_OK) return rc;
-  // the state as it is now is what ovgpu_reset_state goes back to
-  HIPCHK(c->P0.reserve((size_t)N * N));
-  HIPCHK(c->clone_qp0.reserve(7 * (size_t)C));
-  HIPCHK(hipMemcpyAsync(c->P0.p, c->P.p, sizeof(double) * N * N, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->clone_qp0.p, c->clone_qp.p, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->calib_qp0.p, c->calib_qp.p, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->intr0.p, c->intr.p, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
+  if ((rc = copy_reset_baseline(c)) != OVGPU_OK) return rc;
   return launch_build_tables(c);
 }
 
@@ -1023,7 +977,7 @@ static int rebuild_variables(ovgpu_ctx *c) {
 static int enqueue_anchor_change(ovgpu_ctx *c, int l, int new_cam, int new_clone) {
   { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }
   const int32_t old = c->h_lm_anchor[l];
-  const int old_cam = old >> 10;
+  const int old_cam = anchor_cam(old);
   const int lsz = lm_dof(c->h_lm_rep[l]);
   int n_old = 6 + 6 + lsz;
   if (c->h_calib_cov[old_cam] >= 0) n_old += 6;
@@ -1046,7 +1000,7 @@ static int enqueue_anchor_change(ovgpu_ctx *c, int l, int new_cam, int new_clone
                        c->flags.p, pass);
   }
   HIPCHK(hipGetLastError());
-  c->h_lm_anchor[l] = (new_cam << 10) | new_clone;
+  c->h_lm_anchor[l] = anchor_pack(new_cam, new_clone);
   return OVGPU_OK;
 }
 
@@ -1079,8 +1033,8 @@ int ovgpu_slam_change_anchors(ovgpu_ctx *c, int32_t marg_clone, int32_t new_clon
   int n = 0;
   for (int l = 0; l < c->L; l++) {
     const int32_t a = c->h_lm_anchor[l];
-    if (a < 0 || (a & 1023) != marg_clone) continue;
-    if ((rc = enqueue_anchor_change(c, l, a >> 10, new_clone)) != OVGPU_OK) return rc; // same camera (:499-500)
+    if (anchor_clone(a) != marg_clone) continue;
+    if ((rc = enqueue_anchor_change(c, l, anchor_cam(a), new_clone)) != OVGPU_OK) return rc; // same camera (:499-500)
     n++;
   }
   if (n_changed) *n_changed = n;
@@ -1112,8 +1066,8 @@ static int anchor_batch_plan(ovgpu_ctx *c, int marg_clone, int new_clone, Anchor
   pl = AnchorBatchPlan();
   for (int l = 0; l < c->L; l++) {
     const int32_t a = c->h_lm_anchor[l];
-    if (a < 0 || (a & 1023) != marg_clone) continue;
-    const int cam = a >> 10, lsz = lm_dof(c->h_lm_rep[l]); // same camera (:499-500): its extrinsics appear once in phi_order_OLD
+    if (anchor_clone(a) != marg_clone) continue;
+    const int cam = anchor_cam(a), lsz = lm_dof(c->h_lm_rep[l]); // same camera (:499-500): its extrinsics appear once in phi_order_OLD
     const int est = c->h_calib_cov[cam] >= 0 ? 1 : 0;
     const int n_old = 6 + 6 * est + 6 + lsz;
     const int32_t e[8] = {l, cam, new_clone, lsz, n_old, (int32_t)pl.n_phi, (int32_t)pl.n_ids, c->h_lm_cov[l]};
@@ -1172,7 +1126,7 @@ int ovgpu_slam_change_anchors_batched(ovgpu_ctx *c, int32_t marg_clone, int32_t 
     hipLaunchKernelGGL(k_cov_propagate_multi, dim3((nt + 255) / 256), dim3(256), 0, s, pp, pass);
   }
   HIPCHK(hipGetLastError());
-  for (int b = 0; b < pl.n; b++) c->h_lm_anchor[pl.tab[8 * b]] = (pl.tab[8 * b + 1] << 10) | new_clone;
+  for (int b = 0; b < pl.n; b++) c->h_lm_anchor[pl.tab[8 * b]] = anchor_pack(pl.tab[8 * b + 1], new_clone);
   if (n_changed) *n_changed = pl.n;
   return OVGPU_OK;
 }

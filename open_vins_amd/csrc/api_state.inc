@@ -182,6 +182,29 @@ static int launch_build_tables(ovgpu_ctx *c) {
   return OVGPU_OK;
 }
 
+// the resident state as it is now becomes what ovgpu_reset_state goes back to (P0 sized for the current N)
+static int copy_reset_baseline(ovgpu_ctx *c) {
+  const size_t N = (size_t)c->N, C = (size_t)c->C, K = (size_t)c->K;
+  hipStream_t s = c->stream;
+  HIPCHK(c->P0.reserve(N * N));
+  HIPCHK(c->clone_qp0.reserve(7 * C));
+  HIPCHK(hipMemcpyAsync(c->P0.p, c->P.p, sizeof(double) * N * N, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->clone_qp0.p, c->clone_qp.p, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->calib_qp0.p, c->calib_qp.p, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->intr0.p, c->intr.p, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
+  return OVGPU_OK;
+}
+
+// the covariance at dimension N_to: its leading n_copy x n_copy block (leading dimension ld_from) into Ppad, zero beyond, and Ppad becomes P
+static int cov_resize(ovgpu_ctx *c, int n_copy, int N_to, int ld_from) {
+  HIPCHK(c->Ppad.reserve((size_t)N_to * N_to));
+  hipLaunchKernelGGL(k_cov_copy, dim3((N_to + 255) / 256, N_to), dim3(256), 0, c->stream, n_copy, N_to, c->P.p, ld_from, c->Ppad.p, N_to);
+  HIPCHK(hipGetLastError());
+  std::swap(c->P, c->Ppad);
+  c->N = N_to;
+  return OVGPU_OK;
+}
+
 // Canonical column order of the stacked Jacobian: calibrated camera variables, clones and (SLAM) landmarks sorted by
 // covariance id.  build_columns sorts the resident variables (ovgpu_set_state, ovgpu_set_landmarks and every structural change of the
 // state); layout_columns lays the columns out over that sorted list for the active landmark set (ovgpu_set_active_landmarks: a linear
@@ -424,13 +447,9 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
   HIPCHK(upload_deferred(c, c->intr_cov.p, intr_cov.data(), sizeof(int32_t) * K));
   // the caller's buffers may change when this returns: the bytes sit in the page-locked arena (a synchronisation only for what bypassed it)
   HIPCHK(upload_fence(c, s));
-  if (!twins) { // (an array bypassed the arena, or the launch was split: the copies of rounds 4-5)
-    HIPCHK(hipMemcpyAsync(c->P0.p, c->P.p, sizeof(double) * N * N, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->clone_qp0.p, c->clone_qp.p, sizeof(double) * 7 * C, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->calib_qp0.p, c->calib_qp.p, sizeof(double) * 7 * K, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->intr0.p, c->intr.p, sizeof(double) * 8 * K, hipMemcpyDeviceToDevice, s));
-  }
-  int rc = launch_build_tables(c);
+  int rc = OVGPU_OK;
+  if (!twins && (rc = copy_reset_baseline(c)) != OVGPU_OK) return rc; // (an array bypassed the arena, or the launch was split: the copies of rounds 4-5)
+  rc = launch_build_tables(c);
   if (rc != OVGPU_OK) return rc;
   c->have_state = true, c->poses_only = false;
   c->have_feats = false; // workspaces depend on D
@@ -663,7 +682,7 @@ static int raw_stack_layout(ovgpu_ctx *c, const uint16_t *cc) {
   int64_t run[RAW_MAXCLS + 1] = {0};
   for (int f = 0; f < F; f++) {
     int cnt[RAW_MAXCLS] = {0};
-    for (int i = c->h_offsets[f]; i < c->h_offsets[f + 1]; i++) cnt[c->h_cls_of_clone[cc[i] & 1023]]++;
+    for (int i = c->h_offsets[f]; i < c->h_offsets[f + 1]; i++) cnt[c->h_cls_of_clone[anchor_clone(cc[i])]]++;
     int below = 0;
     for (int k = 0; k < n; k++) {
       fb[(size_t)f * RAW_MAXCLS + k] = (int32_t)(run[k] - 2 * below);
@@ -831,7 +850,7 @@ int ovgpu_set_features(ovgpu_ctx *c, const ovgpu_features_view *fv) {
     for (int i = 0; i < M; i++) {
       const uint32_t cl = (uint32_t)ci[i], cam = (uint32_t)ki[i]; // (a negative index is a huge unsigned one)
       bad |= (uint32_t)(cl >= nC) | (uint32_t)(cam >= nK);
-      cc[i] = (uint16_t)((cam << 10) | cl);
+      cc[i] = (uint16_t)anchor_pack(cam, cl);
     }
     if (bad) return set_err(OVGPU_ERR_INVALID, "measurement refers to an unknown clone / camera");
   }

@@ -60,7 +60,7 @@ int ovgpu_state_marginalize(ovgpu_ctx *c, int32_t cov_id, int32_t size) {
     // a landmark anchored in the clone that goes away must have been re-anchored before (UpdaterSLAM::change_anchors runs before
     // StateHelper::marginalize_old_clone, VioManager.cpp:585-590); checked before anything is modified
     for (int l = 0; l < c->L; l++)
-      if (l != drop_lm && c->h_lm_anchor[l] >= 0 && (c->h_lm_anchor[l] & 1023) == drop_clone)
+      if (l != drop_lm && anchor_clone(c->h_lm_anchor[l]) == drop_clone)
         return set_err(OVGPU_ERR_INVALID, "a resident landmark is anchored in the marginalised clone (ovgpu_slam_change_anchors first)");
   }
   // ---- nothing was modified so far; from here on the call goes through
@@ -107,8 +107,8 @@ int ovgpu_state_marginalize(ovgpu_ctx *c, int32_t cov_id, int32_t size) {
     std::vector<int32_t> &anc = c->h_lm_anchor;
     for (auto &a : anc) {
       if (a < 0) continue;
-      const int cam = a >> 10, cl = a & 1023;
-      a = (cam << 10) | (cl > drop_clone ? cl - 1 : cl);
+      const int cl = anchor_clone(a);
+      a = anchor_pack(anchor_cam(a), cl > drop_clone ? cl - 1 : cl);
     }
     HIPCHK(hipMemcpy(c->lm_anchor.p, anc.data(), sizeof(int32_t) * c->L, hipMemcpyHostToDevice));
   }
@@ -164,7 +164,7 @@ int ovgpu_state_marginalize_batched(ovgpu_ctx *c, int32_t n, const int32_t *cov_
   }
   if (Cn < C) // a landmark anchored in a clone that leaves must leave with it, or have been re-anchored before (UpdaterSLAM::change_anchors, VioManager.cpp:585-590)
     for (int l = 0; l < L; l++)
-      if (lm_keep[l] && c->h_lm_anchor[l] >= 0 && !clone_keep[c->h_lm_anchor[l] & 1023])
+      if (lm_keep[l] && c->h_lm_anchor[l] >= 0 && !clone_keep[anchor_clone(c->h_lm_anchor[l])])
         return set_err(OVGPU_ERR_INVALID, "a resident landmark is anchored in the marginalised clone (ovgpu_slam_change_anchors first)");
   int gone = 0;
   for (int b = 0; b < n; b++) tab[2 * b] = blk[b].first, tab[2 * b + 1] = blk[b].second, gone += blk[b].second;
@@ -220,7 +220,7 @@ int ovgpu_state_marginalize_batched(ovgpu_ctx *c, int32_t n, const int32_t *cov_
     if (!lm_keep[l]) continue;
     const int32_t a = c->h_lm_anchor[l];
     c->h_lm_rep[w] = c->h_lm_rep[l], c->h_lm_cov[w] = shifted(c->h_lm_cov[l]);
-    c->h_lm_anchor[w] = a >= 0 ? ((a >> 10) << 10) | clone_new[a & 1023] : a;
+    c->h_lm_anchor[w] = a >= 0 ? anchor_pack(anchor_cam(a), clone_new[anchor_clone(a)]) : a;
     if (act) c->h_lm_active[w] = c->h_lm_active[l];
     w++;
   }
@@ -242,11 +242,9 @@ int ovgpu_state_augment_clone(ovgpu_ctx *c, int32_t src_cov_id, const double *q_
   hipStream_t s = c->stream;
   const int N = c->N, Nn = N + 6, C = c->C;
   // ---- covariance: grow, copy the pose's rows / columns to the end (StateHelper.cpp:348-372)
-  HIPCHK(c->Ppad.reserve((size_t)Nn * Nn));
   {
-    dim3 g((Nn + 255) / 256, Nn);
-    hipLaunchKernelGGL(k_cov_copy, g, dim3(256), 0, s, N, Nn, c->P.p, N, c->Ppad.p, Nn);
-    std::swap(c->P, c->Ppad);
+    const int rcr = cov_resize(c, N, Nn, N);
+    if (rcr != OVGPU_OK) return rcr;
     hipLaunchKernelGGL(k_cov_clone, dim3((N + 36 + 255) / 256), dim3(256), 0, s, Nn, N, (int)src_cov_id, N, 6, c->P.p);
     HIPCHK(hipGetLastError());
   }
@@ -258,7 +256,6 @@ int ovgpu_state_augment_clone(ovgpu_ctx *c, int32_t src_cov_id, const double *q_
     hipLaunchKernelGGL(k_cov_dt, dim3((Nn + 255) / 256), dim3(256), 0, s, Nn, N, (int)dt_cov_id, c->prop_in.p, c->P.p, 1);
     HIPCHK(hipGetLastError());
   }
-  c->N = Nn;
   // ---- the clone joins the resident ones (State::_clones_IMU[timestamp] = pose, :597)
   HIPCHK(c->clone_qp.grow(7 * (size_t)(C + 1), 7 * (size_t)C));
   HIPCHK(c->clone_fej.grow(7 * (size_t)(C + 1), 7 * (size_t)C));
@@ -737,8 +734,8 @@ int ovgpu_get_features(ovgpu_ctx *c, int32_t *F_out, int32_t *M_out, int32_t *me
   if (want_cc) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, s));
   HIPCHK(upload_sync(c, s));
   for (int i = 0; want_cc && i < M; i++) {
-    if (clone_idx) clone_idx[i] = cc[i] & 1023;
-    if (cam_idx) cam_idx[i] = cc[i] >> 10;
+    if (clone_idx) clone_idx[i] = anchor_clone(cc[i]);
+    if (cam_idx) cam_idx[i] = anchor_cam(cc[i]);
   }
   return OVGPU_OK;
 }

@@ -16,9 +16,12 @@ struct DevOptions {
   int gate_always_factor; // options.gate_always_factor: no residual bound in the MSCKF gate (k_featy.h)
 };
 
-// packed (camera, clone) code of one measurement: cam << 10 | clone
+// packed (camera, clone) code of one measurement or of a landmark's anchor: cam << 10 | clone; -1: none
 static constexpr int OVG_MAX_CLONES = 1024;
 static constexpr int OVG_MAX_CAMS = 64;
+constexpr int32_t anchor_pack(int cam, int clone) { return (cam << 10) | clone; }
+constexpr int anchor_cam(int32_t a) { return a >= 0 ? a >> 10 : -1; }
+constexpr int anchor_clone(int32_t a) { return a >= 0 ? (a & 1023) : -1; }
 
 struct TriParams {
   int F, C, K;

@@ -352,7 +352,7 @@ def make_problem(cfg=2, rep=0, *, C=None, K=None, F=None, track="full", fisheye=
         v = rng_f.uniform(0, IMG_H, batch).astype(np.float32).astype(np.float64)
         depth = rng_f.uniform(5.0, 7.0, batch)
         lo = rng_f.integers(0, C, batch)
-        ln = rng_f.integers(5, C + 1, batch)
+        ln = rng_f.integers(min(5, C), C + 1, batch)  # (windows of fewer than five clones: the whole window)
         noise = rng_f.normal(0, 1.0, (batch, K, C, 2))
         camk = intr_true[k].T  # [8,batch]
         xn, yn = undistort(camk, u, v)

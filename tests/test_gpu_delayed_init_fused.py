@@ -269,6 +269,31 @@ def test_every_candidate_rejected_leaves_the_state_bit_for_bit(Updater, oracle):
     assert np.array_equal(post_c["clone_q_p"], prob.clone_q_p) and np.array_equal(post_c["calib_q_p"], prob.calib_q_p)
 
 
+# --------------------------------------------------------------------------- the reset baseline after the covariance shrank to its own dimension
+@pytest.mark.parametrize("fused", [False, True])
+def test_reset_state_returns_to_what_the_call_left(Updater, oracle, fused):
+    """Four clones, one camera, one resident landmark; three candidates of three measurements, the middle one a planted outlier (tracks 2, 3, 6 of
+    the window: the ones that triangulate over so short a baseline).  The chain runs at the padded dimension N + 9 and leaves N + 6: after
+    ovgpu_reset_state the covariance, at that dimension and its own leading dimension, the clones, the calibration and the intrinsics read back
+    bit for bit as the call returned and left them."""
+    window = synth.make_problem(2, C=4, K=1, F=12, seed=32, min_obs=3)
+    tracks = ts.make_outlier(ts.exact_length(window, 3, patterns=("stride",)).subset([2, 3, 6]), 1)
+    case = Case(_tracks_from(synth.make_slam_problem(2, L=1, C=4, K=1, seed=32, min_obs=3), tracks), capi.REP_GLOBAL_3D, slam=True)
+    tri, ref = _oracle(oracle, case)
+    assert list(ref["feat_status"]) == [capi.FEAT_USED, capi.FEAT_CHI2_REJECTED, capi.FEAT_USED]
+    up, out, post, lm, _ = _run(Updater, case, tri, fused)
+    try:
+        assert np.array_equal(out["feat_status"], ref["feat_status"]) and out["N"] == case.prob.N + 6 and len(lm["cov_id"]) == 3
+        assert post["P"].shape == (out["N"], out["N"]) and np.array_equal(post["P"], out["P"])
+        assert np.abs(post["clone_q_p"] - case.prob.clone_q_p).max() > 0  # the chain moved the state
+        up.reset_state()
+        back = up.get_state(P=True)
+        for k in post:
+            assert back[k].shape == post[k].shape and np.array_equal(back[k], post[k]), k
+    finally:
+        up.close()
+
+
 # --------------------------------------------------------------------------- calibration and FEJ flags
 @pytest.mark.parametrize("do_fej,K,pose,intr", [(0, 2, 1, 1), (1, 1, 0, 0), (0, 1, 1, 0), (1, 2, 0, 1)])
 def test_calibration_and_fej_flags(Updater, oracle, do_fej, K, pose, intr):

@@ -350,6 +350,42 @@ def test_no_side_effects_on_landmarks(Updater):
     up.close()
 
 
+def test_no_side_effects_before_a_delayed_init_with_an_anchored_landmark(Updater):
+    """Four clones, two cameras, two resident landmarks (one anchored: the 72-double row store; every landmark active: the batch's SLAM row layout
+    is what the call has to put back), three candidates (tracks 0, 6, 7 of the window: the ones that triangulate over so short a baseline), a
+    restart from the second.  The state and the landmarks read back bit for bit, and the delayed initialisation that follows equals, bit for
+    bit, the one on a context that never made the call."""
+    kw = dict(C=4, K=2, min_obs=3)
+    lm_reps = np.array([capi.REP_GLOBAL_3D, capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH], np.int32)
+    prob = synth.make_slam_problem(2, L=2, lm_rep=lm_reps, seed=71, **kw)
+    tracks = synth.make_problem(2, F=16, seed=71, shard=1, **kw).subset([0, 6, 7])
+    for k in ("meas_offsets", "uv", "uvn", "clone_idx", "cam_idx"):
+        setattr(prob, k, getattr(tracks, k))
+    opts = capi.default_options(chi2_multipler=1.0)
+    a, b = Updater(opts), Updater(opts)
+    a.set_slam_problem(prob)
+    b.set_slam_problem(prob)
+    lm0, st0 = a.get_landmarks(), a.get_state(P=True)
+    sys_ = a.init_systems(capi.REP_ANCHORED_3D, first_feature=1)
+    assert sys_[0]["status"] == -1 and sum(s["status"] == capi.FEAT_USED and s["H_x"] is not None for s in sys_[1:]) >= 1
+    lm1, st1 = a.get_landmarks(), a.get_state(P=True)
+    for k in lm0:
+        assert np.array_equal(lm0[k], lm1[k]), k
+    for k in st0:
+        assert np.array_equal(st0[k], st1[k]), k
+    oa, ob = a.delayed_init(capi.REP_ANCHORED_3D), b.delayed_init(capi.REP_ANCHORED_3D)
+    assert (ob["lm_cov_id"] >= 0).sum() >= 2 and oa["N"] == ob["N"] > prob.N
+    for k in ("feat_status", "chi2", "chi2_thresh", "lm_cov_id", "lm_value", "lm_fej", "anchor_cam", "anchor_clone", "dx_seq", "P"):
+        assert np.array_equal(oa[k], ob[k]), k
+    la, lb, sa, sb = a.get_landmarks(), b.get_landmarks(), a.get_state(P=True), b.get_state(P=True)
+    for k in la:
+        assert np.array_equal(la[k], lb[k]), k
+    for k in sa:
+        assert np.array_equal(sa[k], sb[k]), k
+    a.close()
+    b.close()
+
+
 def test_edge_cases(Updater):
     """No features; tracks with fewer than two measurements (no system); a batch the gate rejects completely."""
     opts = capi.default_options(chi2_multipler=1.0)
