@@ -187,7 +187,7 @@ typedef struct {
   int32_t no_fast_feature_kernel; /* 1: always the general per-feature       */
                              /* kernel (k_system) instead of the MSCKF fast  */
                              /* path (k_feat: gate matrix in registers)      */
-  int32_t no_single_launch_cholesky; /* 1: the Cholesky-with-carry factorisations run as one launch per 16 rows */
+  int32_t no_single_launch_cholesky; /* 1: the Cholesky-with-carry factorisations run as one launch per 16 rows (0: one launch up to 256 columns, four up to 512) */
                              /* (k_ekf_chol_step) instead of the pipelined single launch (k_chol.h)           */
   double prior_pivot_tol;    /* Gram route: a pivot of the prior block's      */
                              /* Cholesky factorisation below this fraction of */
@@ -1144,6 +1144,13 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             are switched off on the device, the state stays untouched and the synchronous update calls repeat
  *                             the update with the step-wise kernels
  *   "chol_timeouts"           (read only) number of updates repeated that way
+ *   "chol_wide"               (default 1) a Cholesky-with-carry factorisation of 257 .. 512 columns runs as two panels of the single-launch
+ *                             kernel around a Schur step, four launches (k_chol_wide.h), in every update entry point, with no lower bound on
+ *                             the second panel's width (measured faster from 257 columns on); 0: one launch per 16 rows up
+ *                             there (the same result to rounding).  ovgpu_options::no_single_launch_cholesky = 1 and the repeat after a
+ *                             follower's time-out select the step-wise kernels at every column count
+ *   "chol_wide_factorisations" number of factorisations ENQUEUED on the two-panel path, counted on the host: one that a predicate switches off on the
+ *                             device counts too (a value >= 0 sets the counter)
  *   "slam_chunked_fallbacks"  number of ovgpu_slam_update_chunked passes that put the entry state back and ran the chunks one by one
  *                             (a value >= 0 sets the counter)
  *   "delayed_init_fused"      (default 1) 0: ovgpu_slam_delayed_init_fused runs ovgpu_slam_delayed_init's step for every candidate

@@ -308,6 +308,9 @@ struct ovgpu_ctx {
   unsigned ctrl_clean = 0;
   unsigned ctrl_pre = 0;       // views zeroed AHEAD of the pipeline call that will use them (enqueue_speculative_prior) and not touched since: ctrl_zero skips them once
   DevBuf<double> chol_uinv;    // [2][16][256]
+  DevBuf<double> chol_wide_A, chol_wide_Y; // [D - 256][LA - 256] each: the compact Schur complement and its factorisation (k_chol_wide.h: the second panel beyond 256 columns)
+  bool chol_wide = true;          // ovgpu_debug_option "chol_wide": 0 = the step-wise kernels beyond 256 columns (1: two panels of k_chol_fused, measured faster on every leg: DESIGN.md §7)
+  int64_t chol_wide_count = 0;    // ovgpu_debug_option "chol_wide_factorisations": factorisations enqueued on the two-panel path
   PinBuf<double> h_tri;        // mode A: the compressed system on its way to the caller ([D x LD] + one word of flags per double behind it)
   int chol_slot = 0;
   bool no_chol_pipe = false;   // options.no_single_launch_cholesky

@@ -83,6 +83,12 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
   } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big
     if (old_value) *old_value = c->last_feat_kernel;
+  } else if (n == "chol_wide") { // 0: beyond 256 columns the Cholesky-with-carry runs as one launch of k_ekf_chol_step per 16 rows instead of two panels of k_chol_fused (k_chol_wide.h)
+    if (old_value) *old_value = c->chol_wide ? 1 : 0;
+    if (value >= 0) c->chol_wide = value != 0;
+  } else if (n == "chol_wide_factorisations") { // reads the count of factorisations enqueued on the two-panel path; a value >= 0 sets it
+    if (old_value) *old_value = c->chol_wide_count;
+    if (value >= 0) c->chol_wide_count = value;
   } else if (n == "chol_timeouts") { // read-only counter: updates repeated with the step-wise Cholesky after a follower timed out
     if (old_value) *old_value = c->chol_timeouts;
   } else {

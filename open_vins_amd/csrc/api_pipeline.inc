@@ -530,6 +530,42 @@ static int launch_chol_fused(ovgpu_ctx *c, chol::CholParams &q, int slot, hipStr
   return OVGPU_OK;
 }
 
+// Beyond 256 columns, up to 512: two panels of k_chol_fused around a Schur step, four launches (k_chol_wide.h).  The work matrix is assembled
+// (CH_SRC_MATRIX: reading at the source stays tied to one panel), so is only ONE factorisation in flight — the speculative prior stays off up here —
+// and the panels take the two sets of step words and inverse tiles.  options.no_single_launch_cholesky and the repeat after a time-out
+// (c->no_chol_pipe) select the step-wise kernels here exactly as they do below 256 columns.
+static bool chol_wide_usable(const ovgpu_ctx *c, int D) { return !c->no_chol_pipe && c->chol_wide && D > chol::CW_D1 && D <= 2 * chol::CW_D1; }
+static int enqueue_chol_wide(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, double *Lt) {
+  const int D2 = p.D - chol::CW_D1, LA2 = p.LA - chol::CW_D1;
+  HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
+  HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
+  HIPCHK(c->chol_wide_A.reserve((size_t)D2 * LA2));
+  HIPCHK(c->chol_wide_Y.reserve((size_t)D2 * LA2));
+  HIPCHK(ctrl_zero(c, CTRL_PROG0, c->chol_prog.p, 16 * sizeof(int32_t), s));
+  HIPCHK(ctrl_zero(c, CTRL_PROG1, c->chol_prog.p + CHOL_PROG_STRIDE, 16 * sizeof(int32_t), s));
+  int32_t *go = c->ctrl.p + 4; // a spare word of the control block, written by k_chol_schur before anybody reads it
+  chol::CholParams q;
+  q.D = chol::CW_D1, q.LA = p.LA, q.A = p.A, q.Y = p.Y, q.Lt = nullptr, q.flags = p.flags, q.diag0 = p.diag0, q.pivot_tol = p.pivot_tol, q.pred = p.pred;
+  q.src = chol::CH_SRC_MATRIX, q.pred_not = p.pred_not; // (q.N stays 0: only the read-at-source forms use it)
+  int rc = launch_chol_fused(c, q, 0, s);
+  if (rc != OVGPU_OK) return rc;
+  chol::CholWideParams w;
+  w.D = p.D, w.LA = p.LA, w.A = p.A, w.Y = p.Y, w.Ac = c->chol_wide_A.p, w.Yc = c->chol_wide_Y.p, w.Lt = Lt, w.flags = p.flags, w.go = go;
+  w.pred = const_cast<int32_t *>(p.pred), w.pred_not = p.pred_not;
+  const int TR = (D2 + 15) / 16, TC = (LA2 + 15) / 16;
+  const int tiles = TR * TC - TR * (TR - 1) / 2; // on or right of the diagonal tile
+  hipLaunchKernelGGL(chol::k_chol_schur, dim3((tiles + 3) / 4), dim3(256), 0, s, w);
+  // the second panel judges every pivot against its own original diagonal entry, like the first
+  q.D = D2, q.LA = LA2, q.A = c->chol_wide_A.p, q.Y = c->chol_wide_Y.p, q.diag0 = p.diag0 ? p.diag0 + chol::CW_D1 : nullptr, q.pred = go, q.pred_not = nullptr;
+  if ((rc = launch_chol_fused(c, q, 1, s)) != OVGPU_OK) return rc;
+  const int64_t elems = (int64_t)D2 * LA2 + (Lt ? (int64_t)p.D * p.D : 0);
+  hipLaunchKernelGGL(chol::k_chol_place, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, w);
+  HIPCHK(hipGetLastError());
+  c->last_uinv = nullptr; // (the inverse tiles are two panels' own: k_unwhiten_blk is a kernel for up to 256 columns)
+  c->chol_wide_count++;
+  return OVGPU_OK;
+}
+
 static int enqueue_chol_carry(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, double *Lt, const CholSource &from) {
   if (chol_pipe_usable(c, p.D)) {
     // one launch: the factor workgroup's chain stays inside a compute unit, the carried columns follow through flags (k_chol.h)
@@ -547,6 +583,7 @@ static int enqueue_chol_carry(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, d
     return launch_chol_fused(c, q, slot, s);
   }
   if (from.src != chol::CH_SRC_MATRIX) return set_err(OVGPU_ERR_INVALID, "the step-wise factorisation needs its work matrix assembled");
+  if (chol_wide_usable(c, p.D)) return enqueue_chol_wide(c, p, s, Lt);
   const int TM = (p.D + 15) / 16, TL = (p.LA + 15) / 16;
   for (int kb = 0; kb < p.D; kb += 16) {
     const int tb = kb / 16;

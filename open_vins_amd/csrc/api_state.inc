@@ -133,6 +133,7 @@ void ovgpu_destroy(ovgpu_ctx *c) {
   c->ctrl.release();
   c->gram_part.release(), c->gram_G.release(), c->gram_rho.release(), c->Yaug2.release(), c->gram_dropped.release(), c->Lw.release(), c->dbg_cycles.release();
   c->chol_uinv.release();
+  c->chol_wide_A.release(), c->chol_wide_Y.release();
   c->h_tri.release();
   c->fs_slots.release(), c->fs_minfo.release(), c->fs_meas_feat.release(), c->fs_pos.release(), c->fs_rows.release(), c->fs_V.release(), c->fs_z.release(), c->fs_w.release(), c->fs_tq.release(), c->fs_inst.release(), c->featyb_ws.release();
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);

@@ -36,6 +36,7 @@
 #include "k_system.h"
 #include "k_feat.h"
 #include "k_chol.h"
+#include "k_chol_wide.h"
 #include "k_triangulate.h"
 #include "k_tail.h"
 #include "k_retri.h"
