@@ -1151,6 +1151,13 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             follower's time-out select the step-wise kernels at every column count
  *   "chol_wide_factorisations" number of factorisations ENQUEUED on the two-panel path, counted on the host: one that a predicate switches off on the
  *                             device counts too (a value >= 0 sets the counter)
+ *   "tsqr_leaves" / "tsqr_rows_per_node" / "tsqr_last_leaf_kernel" / "tsqr_last_tree" / "tsqr_last_qh"  (read only) what the last Householder
+ *                             compression launched, stand-alone (ovgpu_measurement_compress, ovgpu_ekf_update) or on the update route: the number
+ *                             of leaves W; the rows per leaf; the leaf kernel (0 the panel-wave kernel of k_tsqr_pw.h, 1 k_qr_node of k_tsqr.h,
+ *                             2 k_qr_append; -1 before the first compression); the merge (0 none: one leaf, 1 the single-launch tree next to the
+ *                             leaves, 2 the single-launch tree behind them, 3 one launch per level); the merge kernels' quads per register array
+ *                             (16, 28 or 32; 0 for k_qr_append and where nothing was merged).  A merge without leaves (ovgpu_msckf_merge_update)
+ *                             sets the last two only
  *   "slam_chunked_fallbacks"  number of ovgpu_slam_update_chunked passes that put the entry state back and ran the chunks one by one
  *                             (a value >= 0 sets the counter)
  *   "delayed_init_fused"      (default 1) 0: ovgpu_slam_delayed_init_fused runs ovgpu_slam_delayed_init's step for every candidate

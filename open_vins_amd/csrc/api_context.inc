@@ -232,6 +232,13 @@ struct ovgpu_ctx {
   DevBuf<int32_t> flags;
   int W = 1;
   int64_t rows_per_node = 128;
+  // read-only ovgpu_debug_option names "tsqr_leaves", "tsqr_rows_per_node", "tsqr_last_leaf_kernel", "tsqr_last_tree", "tsqr_last_qh": what the last
+  // Householder compression (stand-alone or on the update route) launched, kept on the host by enqueue_compress / enqueue_merge_tree
+  int tsqr_last_W = 0;            // leaves
+  int64_t tsqr_last_rpn = 0;      // rows per leaf
+  int tsqr_last_leaf = -1;        // 0 pw::k_qr_node (k_tsqr_pw.h), 1 k_qr_node<.., false> (k_tsqr.h), 2 k_qr_append (k_compress.h); -1: none yet
+  int tsqr_last_tree = 0;         // 0 no merge, 1 k_qr_tree next to the leaves, 2 k_qr_tree behind them, 3 one launch per level
+  int tsqr_last_qh = 0;           // quads per register array of the merge kernels (16 / 28 / 32); 0: k_qr_append, or no merge
   DevBuf<QrTreeNode> tree_nodes, tree_nodes2; // merge trees of the pipelined launch, cached per leaf count (two: the local
                                               // compression and the cross-GPU merge alternate in the sharded update)
   int tree_G2 = 0;

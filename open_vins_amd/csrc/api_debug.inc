@@ -89,6 +89,16 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "chol_wide_factorisations") { // reads the count of factorisations enqueued on the two-panel path; a value >= 0 sets it
     if (old_value) *old_value = c->chol_wide_count;
     if (value >= 0) c->chol_wide_count = value;
+  } else if (n == "tsqr_leaves") { // read-only, this and the four below: what the last Householder compression launched (enqueue_compress / enqueue_merge_tree)
+    if (old_value) *old_value = c->tsqr_last_W;
+  } else if (n == "tsqr_rows_per_node") {
+    if (old_value) *old_value = c->tsqr_last_rpn;
+  } else if (n == "tsqr_last_leaf_kernel") { // 0 pw::k_qr_node, 1 k_qr_node<.., false>, 2 k_qr_append; -1: no compression yet
+    if (old_value) *old_value = c->tsqr_last_leaf;
+  } else if (n == "tsqr_last_tree") { // 0 no merge, 1 k_qr_tree next to the leaves, 2 k_qr_tree behind them, 3 one launch per level
+    if (old_value) *old_value = c->tsqr_last_tree;
+  } else if (n == "tsqr_last_qh") { // 16 / 28 / 32: quads per register array of the merge kernels; 0: k_qr_append, or no merge
+    if (old_value) *old_value = c->tsqr_last_qh;
   } else if (n == "chol_timeouts") { // read-only counter: updates repeated with the step-wise Cholesky after a follower timed out
     if (old_value) *old_value = c->chol_timeouts;
   } else {

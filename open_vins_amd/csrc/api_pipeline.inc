@@ -204,7 +204,9 @@ static int enqueue_merge_tree(ovgpu_ctx *c, int G, bool leaves_live = false, hip
   const int NT = (LD + 15) / 16;
   if (G <= 1) return OVGPU_OK;
   hipStream_t ts = on ? on : c->stream;
+  c->tsqr_last_qh = NT <= 8 ? 16 : (NT <= 14 ? 28 : (NT <= 16 ? 32 : 0));
   if (c->tree_pipelined && NT <= 16 && G - 1 <= c->num_cu) {
+    c->tsqr_last_tree = leaves_live ? 1 : 2;
     // ---- one launch for the whole tree, software-pipelined across the levels (k_qr_tree)
     DevBuf<QrTreeNode> *slot = nullptr;
     if (c->tree_G == G && c->tree_nodes_overlap == leaves_live) slot = &c->tree_nodes;
@@ -244,6 +246,7 @@ static int enqueue_merge_tree(ovgpu_ctx *c, int G, bool leaves_live = false, hip
     if (NT <= 14) return launch_qr_tree<28>(c, n_nodes, q, ts);
     return launch_qr_tree<32>(c, n_nodes, q, ts);
   }
+  c->tsqr_last_tree = 3;
   for (int stride = 1; stride < G; stride <<= 1) {
     const int pairs = (G - stride + 2 * stride - 1) / (2 * stride); // i = 0, 2s, 4s, ... with i + s < G
     if (pairs <= 0) break;
@@ -412,6 +415,8 @@ static int enqueue_compress(ovgpu_ctx *c) {
   const int D = c->D, LD = c->LD;
   const int NT = (LD + 15) / 16;
   const int W = c->W;
+  c->tsqr_last_W = W, c->tsqr_last_rpn = c->rows_per_node, c->tsqr_last_tree = 0, c->tsqr_last_qh = 0;
+  c->tsqr_last_leaf = NT <= 15 ? 0 : (NT == 16 ? 1 : 2);
   if (NT <= 16) {
     QrNodeParams q;
     q.D = D, q.LD = LD, q.NT = NT;

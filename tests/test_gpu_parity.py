@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from open_vins_amd import capi, synth
+import tsqr_shapes as ts
 from parity_util import assert_chi2, oracle_with_the_same_gate_verdicts
 
 pytestmark = pytest.mark.gpu
@@ -850,6 +851,11 @@ def test_standalone_measurement_compress(Updater, oracle, shape):
     G = Ho.T @ Ho
     assert np.linalg.norm(Hc.T @ Hc - G) / np.linalg.norm(G) < 1e-12
     assert np.linalg.norm(Hc.T @ rc - Ho.T @ ro) / np.linalg.norm(Ho.T @ ro) < 1e-11
+    # ... and entry by entry on the column-normalised Gram matrix, against LAPACK's own error (tests/tsqr_shapes.py): the norms above are
+    # dominated by the largest columns
+    Gl, n = ts.gram_ref(H, r)
+    e_ref = ts.metric(*ts.lapack_compress(H, r), Gl, n)
+    assert ts.metric(Hc, rc, Gl, n) <= ts.bound(e_ref)
 
 
 def test_standalone_ekf_update(Updater, oracle):
