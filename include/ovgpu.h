@@ -1195,6 +1195,8 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             workgroups or fewer where that allows, so that the prior's factorisation finds free compute units
  *   "featy_big"               1 / 2: the block-row form of the per-feature kernel (k_featy_big.h) on batches the one-pass kernel holds
  *   "gram_interleaved"        0: k_gram instead of k_gram_il (staging not interleaved with the matrix instructions)
+ *   "gram_read_ahead"         (default 1) k_gram_regions reads the operands of a 4-row step during the products of the step before; 0: every step
+ *                             opens with its own reads (as k_gram_il).  The same products in the same order: the same Gram matrix bit for bit
  *   "gram_blocks_only"        1: always the 8 x 8-tile block form of the Gram kernel (k_gram_blk)
  *   "fuse_chol_inputs"        0: round 2's k_tf_gather / k_tf_abh assemble the factorisations' inputs
  *   "featy_skip"              DEVELOPER BUILD ONLY (-DOVG_FEAT_ABLATE; the shipped library answers OVGPU_ERR_INVALID): bit mask

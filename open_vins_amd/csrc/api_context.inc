@@ -282,6 +282,7 @@ struct ovgpu_ctx {
   bool no_feat_kernel = false;  // options.no_fast_feature_kernel
   // the unprojected stack of the Gram route (ovgpu_types.h: RawStack; k_gram.h: k_gram_regions)
   bool raw_enable = true;          // ovgpu_debug_option "raw_stack"
+  bool gram_read_ahead = true;     // k_gram_regions<PF>: operand reads a k-step ahead (ovgpu_debug_option "gram_read_ahead")
   int raw_work_const = 12;         // per-row cost of a region beside its tiles, in tiles (ovgpu_debug_option "raw_work_const"; see raw_stack_layout)
   bool raw_veto = false;           // this pipeline's stack feeds mode A's factorisation: projected rows (api_pipeline.inc)
   bool raw_one_region = false;     // (developer experiment, ovgpu_debug_option "raw_stack" = 2: every row in the top region)

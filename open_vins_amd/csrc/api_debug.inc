@@ -69,6 +69,9 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
 #else
     return set_err(OVGPU_ERR_INVALID, "featy_skip: ablation switches exist in a developer build only (-DOVG_FEAT_ABLATE)");
 #endif
+  } else if (n == "gram_read_ahead") { // 0: k_gram_regions opens every k-step with its own operand reads (k_gram.h: gram_il_loop without PF) — same products in the same order, the same bits
+    if (old_value) *old_value = c->gram_read_ahead ? 1 : 0;
+    if (value >= 0) c->gram_read_ahead = value != 0;
   } else if (n == "raw_work_const") {
     if (old_value) *old_value = c->raw_work_const;
     if (value >= 0) c->raw_work_const = (int)value;
@@ -122,6 +125,19 @@ int ovgpu_debug_cycles(ovgpu_ctx *c, int enable, long long *out512) {
   }
   return OVGPU_OK;
 }
+
+#ifdef OVG_GRAM_PROF
+// developer build (-DOVG_GRAM_PROF): the phase counters of the last k_gram_regions launch, eight values per wavefront, four wavefronts per workgroup (k_gram.h);
+// *launched = the workgroups of that launch (entries past it are an earlier launch's)
+extern "C" int ovgpu_debug_gram_phases(ovgpu_ctx *c, long long *out, int workgroups, int *launched) {
+  if (!c || !out || !launched || workgroups < 0 || workgroups > 1024) return set_err(OVGPU_ERR_INVALID, "bad argument");
+  *launched = c->gram_wg_n;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(upload_sync(c, c->stream));
+  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(gram::gram_prof_buf), sizeof(long long) * 32 * workgroups));
+  return OVGPU_OK;
+}
+#endif
 
 // one wavefront, a dependent chain of integer multiply-adds for ~0.3 ms (20 000 steps): shader cycles against the constant reference counter
 __global__ void k_clock_probe(long long *out, int iters) {

@@ -317,12 +317,14 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     HIPCHK(c->gram_part.reserve((size_t)std::max(c->gram_wg_tiles, 1) * 256));
     static bool attr_r = false;
     if (!attr_r) {
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_regions, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void *)gram::k_gram_regions<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void *)gram::k_gram_regions<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr_r = true;
     }
-    hipLaunchKernelGGL(gram::k_gram_regions, dim3(c->gram_wg_n), dim3(256), gram::gram_lds_bytes(), c->stream, (const double *)c->Hraw.p, (const gram::GramRegionWG *)c->gram_wg.p,
-                       c->gram_part.p);
-    hipLaunchKernelGGL(gram::k_gram_regions_reduce, dim3(NP), dim3(1024), 0, c->stream, NT, D, c->raw_rs, (const double *)c->gram_part.p, c->gram_G.p);
+    hipLaunchKernelGGL(c->gram_read_ahead ? gram::k_gram_regions<true> : gram::k_gram_regions<false>, dim3(c->gram_wg_n), dim3(256), gram::gram_lds_bytes(), c->stream,
+                       (const double *)c->Hraw.p, (const gram::GramRegionWG *)c->gram_wg.p, c->gram_part.p);
+    hipLaunchKernelGGL(gram::k_gram_regions_reduce, dim3(NP, 256 / gram::RR_E), dim3(gram::RR_E * gram::RR_G), 0, c->stream, NT, D, c->raw_rs,
+                       (const gram::GramRegionWG *)c->gram_wg.p, c->gram_wg_n, (const double *)c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
     return factor ? enqueue_gram_factor(c) : OVGPU_OK;
   }

@@ -727,14 +727,16 @@ static int raw_stack_layout(ovgpu_ctx *c, const uint16_t *cc) {
     const int w = (int)std::min<int64_t>(wgs[k], nchunks);
     {
       const int q = c->raw_rs.n++;
-      c->raw_rs.ntc[q] = c->raw_ntc[k], c->raw_rs.rcol[q] = c->raw_rcol[k], c->raw_rs.neg[q] = k == RAW_NEG ? 1 : 0, c->raw_rs.part_tile[q] = tiles, c->raw_rs.nwg[q] = w;
+      c->raw_rs.ntc[q] = c->raw_ntc[k], c->raw_rs.rcol[q] = c->raw_rcol[k];
     }
     for (int j = 0; j < w; j++) {
       gram::GramRegionWG r;
-      r.ntc = c->raw_ntc[k], r.ld = c->raw_ld[k], r.rcol = c->raw_rcol[k], r.neg = k == RAW_NEG ? 1 : 0;
+      r.ntc = c->raw_ntc[k], r.ld = c->raw_ld[k], r.rcol = c->raw_rcol[k], r.pad = 0;
+      // (k_gram_regions zeroes the LDS columns ld .. 16 ntc - 1 only, the staging writes the rest: a row must fit its region's tile columns)
+      if (r.ld > 16 * r.ntc) return set_err(OVGPU_ERR_INVALID, "raw_stack_layout: a region's row stride exceeds its tile columns");
       r.h_off = c->raw_base[k], r.rows = c->raw_rows[k];
       r.chunk_begin = (int)((nchunks * j) / w), r.chunk_end = (int)((nchunks * (j + 1)) / w);
-      r.part_tile = tiles;
+      r.part_tile = tiles, r.region = (c->raw_rs.n - 1) | (k == RAW_NEG ? 16 : 0);
       tiles += r.ntc * (r.ntc + 1) / 2;
       tab.push_back(r);
     }

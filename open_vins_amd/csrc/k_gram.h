@@ -73,6 +73,18 @@ constexpr int GR_ACC = 34; // tiles per wavefront: 64 - (R0 + R1 + R2 + R3)
 
 #define GRAM_MFMA(a, b, c) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0)
 
+// Phase counters of k_gram_regions (tools/dev_gram_phases.py): a developer build only (-DOVG_GRAM_PROF), eight values per wavefront —
+// [0] / [1] the 100 MHz reference counter at entry / exit, then shader cycles: [2] LDS zeroing, [3] the two un-overlapped first stage fills and the
+// first barrier, [4] the stage loop, [5] of it the waits for the first operand read of a k-step, [6] of it the stage barriers, [7] the tile stores.
+// The stamps fence the schedule (every use drains the LDS counter): read the SHARES, never this build's run time.
+#ifdef OVG_GRAM_PROF
+__device__ long long gram_prof_buf[1024 * 4 * 8];
+#define GRAM_T(x)                          \
+  __builtin_amdgcn_sched_barrier(0);       \
+  const long long x = clock64();           \
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+
 // one LDS stage (GR_ROWS rows) into the wavefront's accumulators
 // (NTC = tile columns rounded up to even, a compile-time bound: the k-step is straight-line code, so the LDS reads of a step
 // are issued ahead of its MFMAs)
@@ -209,7 +221,13 @@ template <int NTC> __global__ void __launch_bounds__(256) k_gram(GramParams p) {
 // sinks into the common successor — behind all matrix instructions again.  Inside, __builtin_amdgcn_sched_barrier(0) pins the order
 // [products of a tile column] [one staging slot] [products of the next column] ..; without it the scheduler gathers the slots into
 // runs (ISA of the first attempt: 90 address instructions up front, 7 LDS writes in a row behind every k-step).
-template <int W, int NTC, bool BAL = false> __device__ __forceinline__ void gram_il_loop(const GramParams &p, double *gram_lds, int tid, int lane, int chunk_begin, int chunk_end,
+//
+// PF (k_gram_regions): the operand reads run a k-step AHEAD.  A k-step used to open with its NTC LDS reads and, one wavefront per SIMD, the first
+// product waited out the LDS round trip with nothing else to issue — eight times per stage.  With PF the read of column j for k-step ks + 1 follows the
+// products of column j of k-step ks (second register set, 2 NTC registers), so only the first k-step of a stage waits: its rows are complete only behind
+// the stage barrier.  Same products in the same order: bit-identical tiles.  (profiles/r16_gram_phases.txt: the stage loop of the widest region
+// 254.8 -> 236.9 kcycles, the kernel 120.0 -> 115.5 us.)
+template <int W, int NTC, bool BAL = false, bool PF = false> __device__ __forceinline__ void gram_il_loop(const GramParams &p, double *gram_lds, int tid, int lane, int chunk_begin, int chunk_end,
                                                                      d4 (&acc)[GR_ACC]) {
   using WR = typename std::conditional<BAL, WaveRowsBal<W>, WaveRows<W>>::type;
   const int LD = p.LD;
@@ -244,6 +262,10 @@ template <int W, int NTC, bool BAL = false> __device__ __forceinline__ void gram
     const int e = tid + 256 * q;
     v[q] = src_f[e < left_f ? e : left_f - 1];
   };
+#ifdef OVG_GRAM_PROF
+  long long prof_wait = 0, prof_bar = 0;
+  GRAM_T(prof_t0)
+#endif
   if (chunk_begin < chunk_end) {
     aim(chunk_begin);
 #pragma unroll
@@ -257,6 +279,10 @@ template <int W, int NTC, bool BAL = false> __device__ __forceinline__ void gram
     left_v = left_f;
   }
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#ifdef OVG_GRAM_PROF
+  GRAM_T(prof_t1)
+#endif
+  double bb[2][GR_NT]; // the operands of a k-step; PF: of this one and the next
   for (int chunk = chunk_begin; chunk < chunk_end; chunk++) {
     const double *cur = gram_lds + (size_t)((chunk - chunk_begin) & 1) * GR_ROWS * GR_LS;
     double *nxt = gram_lds + (size_t)((chunk - chunk_begin + 1) & 1) * GR_ROWS * GR_LS; // last read two stages ago
@@ -265,25 +291,39 @@ template <int W, int NTC, bool BAL = false> __device__ __forceinline__ void gram
     for (int ks = 0; ks < 8; ks++) {
       if (ks == 4) aim(chunk + 2);
       const double *rowp = cur + (4 * ks + g) * GR_LS + cl;
-      double b[GR_NT];
+      double(&b)[GR_NT] = bb[ks & 1], (&bn)[GR_NT] = bb[(ks + 1) & 1];
+      const bool ahead = PF && ks < 7; // this k-step carries the reads of the next one
+      if (!PF || ks == 0) {
 #pragma unroll
-      for (int j = JLO; j < NTC; j++) b[j] = rowp[16 * j];
-      __builtin_amdgcn_sched_barrier(0);
+        for (int j = JLO; j < NTC; j++) b[j] = rowp[16 * j];
+        __builtin_amdgcn_sched_barrier(0);
+#ifdef OVG_GRAM_PROF
+        if constexpr (JLO < NTC) { // until the first of the reads is back (all but NTC - JLO - 1 of them)
+          constexpr int first_back = 0xC07F | ((JLO < NTC ? NTC - JLO - 1 : 0) << 8);
+          GRAM_T(w0)
+          __builtin_amdgcn_s_waitcnt(first_back);
+          GRAM_T(w1)
+          prof_wait += w1 - w0;
+        }
+#endif
+      }
 #pragma unroll
       for (int j = JLO; j < NTC; j++) {
         if (j >= WR::R0 && WR::R0 < NTC) GRAM_MFMA(b[WR::R0 < NTC ? WR::R0 : 0], b[j], acc[j >= WR::R0 ? WR::O0 + j - WR::R0 : 0]);
         if (j >= WR::R1 && WR::R1 < NTC) GRAM_MFMA(b[WR::R1 < NTC ? WR::R1 : 0], b[j], acc[j >= WR::R1 ? WR::O1 + j - WR::R1 : 0]);
         if (j >= WR::R2 && WR::R2 < NTC) GRAM_MFMA(b[WR::R2 < NTC ? WR::R2 : 0], b[j], acc[j >= WR::R2 ? WR::O2 + j - WR::R2 : 0]);
         if (j >= WR::R3 && WR::R3 < NTC) GRAM_MFMA(b[WR::R3 < NTC ? WR::R3 : 0], b[j], acc[j >= WR::R3 ? WR::O3 + j - WR::R3 : 0]);
-        if (j - JLO < SL) {
-          __builtin_amdgcn_sched_barrier(0);
+        const bool slot = j - JLO < SL;
+        if (ahead || slot) __builtin_amdgcn_sched_barrier(0);
+        if (ahead) bn[j] = rowp[4 * GR_LS + 16 * j];
+        if (slot) {
           const int q = (ks & 3) * SL + (j - JLO);
           if (q < NQ) {
             if (ks < 4) put(nxt, q); // k-steps 0-3: stage s + 1 from the registers into the other buffer
             else fetch1(q);          // k-steps 4-7: stage s + 2 into the registers just freed
           }
-          __builtin_amdgcn_sched_barrier(0);
         }
+        if (ahead || slot) __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
       for (int sl = NTC - JLO; sl < SL; sl++) { // wavefronts with fewer tile columns than slots
@@ -296,8 +336,22 @@ template <int W, int NTC, bool BAL = false> __device__ __forceinline__ void gram
       __builtin_amdgcn_sched_barrier(0);
     }
     left_v = left_f;
+#ifdef OVG_GRAM_PROF
+    GRAM_T(b0)
+#endif
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#ifdef OVG_GRAM_PROF
+    GRAM_T(b1)
+    prof_bar += b1 - b0;
+#endif
   }
+#ifdef OVG_GRAM_PROF
+  GRAM_T(prof_t2)
+  if (BAL && lane == 0) {
+    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 4 + W) * 8;
+    o[3] = prof_t1 - prof_t0, o[4] = prof_t2 - prof_t1, o[5] = prof_wait, o[6] = prof_bar;
+  }
+#endif
 }
 
 template <int NTC> __global__ void __launch_bounds__(256) k_gram_il(GramParams p) {
@@ -333,96 +387,138 @@ template <int NTC> __global__ void __launch_bounds__(256) k_gram_il(GramParams p
 // (Skipping zero tiles inside one kernel over feature-major rows was tried first and lost to its own branches: profiles/r06_d_*.)
 // ---------------------------------------------------------------------------------------------------
 struct GramRegionWG {
-  int32_t ntc, ld, rcol, neg;   // the region: tile columns, row stride, the residual's column, 1 = its tiles are subtracted
+  int32_t ntc, ld, rcol, pad;   // the region: tile columns, row stride (<= 16 ntc: raw_stack_layout checks), the residual's column
   int64_t h_off, rows;          // first element and rows of the region
-  int32_t chunk_begin, chunk_end, part_tile, pad; // this workgroup's stages of GR_ROWS rows; its first partial tile
+  int32_t chunk_begin, chunk_end, part_tile, region; // this workgroup's stages of GR_ROWS rows; its first partial tile; its region's place in GramRegionSum, + 16: subtracted
 };
-template <int NTC> __device__ __forceinline__ void gram_region_body(const GramParams &p, double *gram_lds, int tid, int lane, int wave, int cb, int ce) {
+template <int NTC, bool PF> __device__ __forceinline__ void gram_region_body(const GramParams &p, double *gram_lds, int tid, int lane, int wave, int cb, int ce) {
   d4 acc[GR_ACC];
 #pragma unroll
   for (int i = 0; i < GR_ACC; i++) acc[i] = d4{0, 0, 0, 0};
   switch (wave) {
-  case 0: gram_il_loop<0, NTC, true>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<0, true>(p.part, NTC, lane, acc); break;
-  case 1: gram_il_loop<1, NTC, true>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<1, true>(p.part, NTC, lane, acc); break;
-  case 2: gram_il_loop<2, NTC, true>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<2, true>(p.part, NTC, lane, acc); break;
-  default: gram_il_loop<3, NTC, true>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<3, true>(p.part, NTC, lane, acc); break;
+  case 0: gram_il_loop<0, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<0, true>(p.part, NTC, lane, acc); break;
+  case 1: gram_il_loop<1, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<1, true>(p.part, NTC, lane, acc); break;
+  case 2: gram_il_loop<2, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<2, true>(p.part, NTC, lane, acc); break;
+  default: gram_il_loop<3, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<3, true>(p.part, NTC, lane, acc); break;
   }
 }
-__global__ void __launch_bounds__(256) k_gram_regions(const double *H, const GramRegionWG *tab, double *part) {
+// PF = false keeps the k-step of k_gram_il (every k-step opens with its own operand reads): ovgpu_debug_option "gram_read_ahead" = 0, the other side of the
+// bit comparison in tests/test_gpu_gram_regions_shapes.py
+template <bool PF> __global__ void __launch_bounds__(256) k_gram_regions(const double *H, const GramRegionWG *tab, double *part) {
   extern __shared__ double gram_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const GramRegionWG r = tab[blockIdx.x];
-  for (int i = tid; i < 2 * GR_ROWS * GR_LS; i += 256) gram_lds[i] = 0.0;
+#ifdef OVG_GRAM_PROF
+  const long long prof_w0 = wall_clock64();
+  GRAM_T(prof_c0)
+#endif
+  // the staging writes every element of the ld columns of a stage's rows, rows past the region's end as zeros, and the k-steps read 16 ntc columns:
+  // only the columns between the two, of both buffers, are read and never written — they are all there is to zero (a few stores per thread; the
+  // whole 139 KB took 4460 cycles = 2 us of every workgroup, profiles/r16_gram_phases.txt)
+  for (int i = tid, w = 16 * r.ntc - r.ld; i < 2 * GR_ROWS * w; i += 256) gram_lds[(i / w) * GR_LS + r.ld + i % w] = 0.0;
   __syncthreads();
+#ifdef OVG_GRAM_PROF
+  GRAM_T(prof_c1)
+#endif
   GramParams p;
   p.LD = r.ld, p.NT = r.ntc, p.rows_total = r.rows, p.H = H + r.h_off, p.part = part + (size_t)r.part_tile * 256;
   switch (r.ntc) {
-  case 4: gram_region_body<4>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 6: gram_region_body<6>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 8: gram_region_body<8>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 10: gram_region_body<10>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 12: gram_region_body<12>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 14: gram_region_body<14>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  default: gram_region_body<15>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 4: gram_region_body<4, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 6: gram_region_body<6, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 8: gram_region_body<8, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 10: gram_region_body<10, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 12: gram_region_body<12, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 14: gram_region_body<14, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  default: gram_region_body<15, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
   }
+#ifdef OVG_GRAM_PROF
+  __builtin_amdgcn_s_waitcnt(0x0070); // the tile stores are out
+  GRAM_T(prof_c2)
+  if (lane == 0) {
+    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 4 + wave) * 8;
+    o[0] = prof_w0, o[1] = wall_clock64(), o[2] = prof_c1 - prof_c0, o[7] = (prof_c2 - prof_c1) - o[3] - o[4];
+  }
+#endif
 }
 
-// The regions' partial tiles -> G [LG x LG] (what k_gram_reduce leaves): one workgroup per tile pair of the FULL grid (NT tile columns, the
-// residual in column D), every element summed over the regions that hold it — column j < D is column j of every region wide enough, column D is
-// column rcol of every region — region by region, workgroup by workgroup, four running quarters per region added in a fixed order: reproducible.
+// The regions' partial tiles -> G [LG x LG] (what k_gram_reduce leaves): every element summed over the regions that hold it — column j < D is column j of
+// every region wide enough, column D is column rcol of every region; the dropped rows' region is subtracted.
+//
+// The partials are memory round trips and nothing else, so ALL of an element's partials are requested at once: a workgroup is a quarter of a tile pair
+// (blockIdx.y: 64 slots) x 16 wavefronts, and wavefront g takes the workgroups g, g + 16, .. of k_gram_regions' grid (all regions in one list: their
+// records name the region and the first partial tile) sixteen loads to a trip — 256 workgroups of k_gram_regions are ONE trip of the loop below, more of them
+// (a device with more compute units, more live regions than compute units) further dependent trips; correct for any number.  The grid is
+// NT (NT + 1) / 2 x 4 workgroups of 1024 threads (420 at 14 tile columns).  (Before: one workgroup per tile pair, every thread walking ~64 partials
+// region by region, ~16 dependent round trips.)  Sums in a FIXED tree — the loads of a trip pairwise, the
+// trips in order, the sixteen wavefronts pairwise: reproducible bit for bit, no atomics.
 struct GramRegionSum {
   int32_t n;                                              // regions with workgroups
-  int32_t ntc[9], rcol[9], neg[9], part_tile[9], nwg[9];  // part_tile: the region's first workgroup's
+  int32_t ntc[9], rcol[9];                                // (which workgroups are a region's, and its sign: GramRegionWG::region)
 };
-__global__ void __launch_bounds__(1024) k_gram_regions_reduce(int NT, int D, GramRegionSum rs, const double *part, double *G) {
-  __shared__ double tot[4][256];
+constexpr int RR_E = 64, RR_G = 16, RR_U = 16; // slots of a tile per workgroup; wavefronts; loads per thread and trip
+__global__ void __launch_bounds__(RR_E *RR_G) k_gram_regions_reduce(int NT, int D, GramRegionSum rs, const GramRegionWG *__restrict__ tab, int total, const double *__restrict__ part,
+                                                                        double *__restrict__ G) {
+  __shared__ int eoff[9][RR_E];
+  __shared__ double tot[RR_G][RR_E];
   const int LG = 16 * NT;
-  const int idx = blockIdx.x, t = threadIdx.x & 255, grp = threadIdx.x >> 8;
+  const int idx = blockIdx.x, e = threadIdx.x & (RR_E - 1), t = RR_E * blockIdx.y + e;
+  const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x / RR_E);
   int ti = 0, rem = idx;
   while (rem >= NT - ti) rem -= NT - ti, ti++;
   const int tj = ti + rem;
   const int q = 2 * (t >> 7) + (t & 1), lane = (t >> 1) & 63; // slot t = h * 128 + 2 * lane + e holds register q = 2 h + e (gram_put)
   const int i = 16 * ti + 4 * q + (lane >> 4), j = 16 * tj + (lane & 15);
-  double s = 0.0;
-  for (int k = 0; k < rs.n; k++) {
-    const int rc = rs.rcol[k], ntc = rs.ntc[k];
-    // column / row of the element in the region, -1 = the region does not hold it
+  if (grp < rs.n) { // wavefront k: where region k holds the element, in doubles from the first tile of one of its workgroups (-1: it does not)
+    const int rc = rs.rcol[grp], ntc = rs.ntc[grp];
     int li = i == D ? rc : (i < rc && i < D ? i : -1), lj = j == D ? rc : (j < rc && j < D ? j : -1);
-    if (li < 0 || lj < 0) continue;
-    if ((li >> 4) > (lj >> 4)) { // (the residual's ROW against a column of its own tile row: the stored triangle holds the mirror image)
-      const int x = li;
-      li = lj, lj = x;
+    int off = -1;
+    if (li >= 0 && lj >= 0) {
+      if ((li >> 4) > (lj >> 4)) { // (the residual's ROW against a column of its own tile row: the stored triangle holds the mirror image)
+        const int x = li;
+        li = lj, lj = x;
+      }
+      const int lq = (li & 15) >> 2, llane = 16 * (li & 3) + (lj & 15);
+      off = pair_index(ntc, li >> 4, lj >> 4) * 256 + (lq >> 1) * 128 + 2 * llane + (lq & 1);
     }
-    const int lq = (li & 15) >> 2, llane = 16 * (li & 3) + (lj & 15);
-    const int slot = (lq >> 1) * 128 + 2 * llane + (lq & 1);
-    const int NP = ntc * (ntc + 1) / 2;
-    const double *src = part + ((size_t)rs.part_tile[k] + pair_index(ntc, li >> 4, lj >> 4)) * 256 + slot;
-    const int nw = rs.nwg[k], w_lo = (nw * grp) / 4, w_hi = (nw * (grp + 1)) / 4;
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-    int w = w_lo;
-    for (; w + 16 <= w_hi; w += 16) { // (sixteen loads in flight per trip: the partials of a region are memory round trips, nothing else)
-      double a[16];
-#pragma unroll
-      for (int u = 0; u < 16; u++) a[u] = src[(size_t)(w + u) * NP * 256];
-#pragma unroll
-      for (int u = 0; u < 16; u += 4) s0 += a[u], s1 += a[u + 1], s2 += a[u + 2], s3 += a[u + 3];
-    }
-    for (; w + 4 <= w_hi; w += 4) {
-      double a[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) a[u] = src[(size_t)(w + u) * NP * 256];
-      s0 += a[0], s1 += a[1], s2 += a[2], s3 += a[3];
-    }
-    for (; w < w_hi; w++) s0 += src[(size_t)w * NP * 256];
-    const double sk = (s0 + s1) + (s2 + s3);
-    s += rs.neg[k] ? -sk : sk;
+    eoff[grp][e] = off;
   }
-  tot[grp][t] = s;
+  __syncthreads();
+  double s = 0.0;
+  for (int base = 0; base < total; base += RR_G * RR_U) {
+    int ptile[RR_U], reg[RR_U]; // the sixteen records first (scalar loads, independent of each other), then the sixteen partials
+#pragma unroll
+    for (int u = 0; u < RR_U; u++) {
+      const int f = base + grp + RR_G * u, fc = f < total ? f : total - 1;
+      ptile[u] = tab[fc].part_tile, reg[u] = f < total ? tab[fc].region : -1;
+    }
+    double a[RR_U];
+    bool ok[RR_U];
+#pragma unroll
+    for (int u = 0; u < RR_U; u++) { // (clamped, not predicated: sixteen loads in one basic block)
+      const int off = eoff[reg[u] >= 0 ? reg[u] & 15 : 0][e];
+      ok[u] = reg[u] >= 0 && off >= 0;
+      a[u] = part[(size_t)ptile[u] * 256 + (off >= 0 ? off : 0)];
+    }
+#pragma unroll
+    for (int u = 0; u < RR_U; u++) a[u] = ok[u] ? ((reg[u] & 16) ? -a[u] : a[u]) : 0.0;
+#pragma unroll
+    for (int w = 1; w < RR_U; w *= 2)
+#pragma unroll
+      for (int u = 0; u < RR_U; u += 2 * w) a[u] += a[u + w];
+    s += a[0];
+  }
+  tot[grp][e] = s;
   __syncthreads();
   if (grp != 0) return;
-  const double v = (tot[0][t] + tot[1][t]) + (tot[2][t] + tot[3][t]);
-  G[(size_t)i * LG + j] = v;
-  if (ti != tj) G[(size_t)j * LG + i] = v;
+  double v[RR_G];
+#pragma unroll
+  for (int g = 0; g < RR_G; g++) v[g] = tot[g][e];
+#pragma unroll
+  for (int w = 1; w < RR_G; w *= 2)
+#pragma unroll
+    for (int g = 0; g < RR_G; g += 2 * w) v[g] += v[g + w];
+  G[(size_t)i * LG + j] = v[0];
+  if (ti != tj) G[(size_t)j * LG + i] = v[0];
 }
 
 // ---------------------------------------------------------------------------------------------------
