@@ -69,6 +69,39 @@ struct DevBuf {
   }
 };
 
+// a window into another buffer's allocation (the words of the control block): nothing to reserve, grow or release
+template <class T>
+struct DevView {
+  T *p = nullptr;
+};
+
+// a host array somebody else owns
+template <class T>
+struct HostSpan {
+  const T *p = nullptr;
+  size_t n = 0;
+  const T &operator[](size_t i) const { return p[i]; }
+  size_t size() const { return n; }
+};
+template <class T>
+static HostSpan<T> span_of(const std::vector<T> &v) { return HostSpan<T>{v.data(), v.size()}; }
+
+// What a pipeline stage runs on: the resident feature batch, or a slice of it (a chunk of ovgpu_slam_update_chunked).  A value that owns
+// nothing: the context's DevBufs and vectors own the arrays, batch_of() composes this from them at the moment of the call, and a stage reads
+// every one of these fields from the Batch it took at its top, never from the context.
+struct Batch {
+  int F = 0, M = 0, m_max = 0;
+  int64_t rows_total = 0;
+  HostSpan<int32_t> h_offsets, h_order, h_feat_lm; // meas_offsets, sys_order and the lm_index the batch was handed, on the host
+  HostSpan<int64_t> h_row_off;
+  bool have_sigma = false, have_mult = false;
+  int32_t *meas_offsets = nullptr, *sys_order = nullptr, *status = nullptr;
+  uint16_t *meas_cc = nullptr;
+  float *uv = nullptr, *uvn = nullptr;
+  int64_t *row_off = nullptr;
+  double *pA = nullptr, *pG = nullptr, *chi2 = nullptr, *chi2_thr = nullptr, *feat_sigma = nullptr, *feat_mult = nullptr;
+};
+
 struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
 };
@@ -200,7 +233,8 @@ struct ovgpu_ctx {
   DevBuf<int32_t> isx_cols;         // per feature: the context's column of every H_x column, in Hx_order
   std::vector<int32_t> h_isx_cols;
 
-  // ---- features
+  // ---- features: the resident batch's owners.  Stages read them through batch_of()
+  const Batch *view = nullptr; // the batch in force when it is not the whole resident one (BatchScope: a chunk of ovgpu_slam_update_chunked)
   bool have_feats = false;
   bool tri_readable = false; // ovgpu_slam_delayed_init ended: the column map changed, so its batch cannot feed another update (have_feats = false),
                              // but what its triangulation stage left (pA / pG / anchor of the same F features) is still what ovgpu_get_triangulation documents
@@ -229,7 +263,7 @@ struct ovgpu_ctx {
 
   // ---- workspaces
   DevBuf<double> Hbig, gate_ws, Rws, Mt, Aaug, Yaug, dx;
-  DevBuf<int32_t> flags;
+  DevView<int32_t> flags;
   int W = 1;
   int64_t rows_per_node = 128;
   // read-only ovgpu_debug_option names "tsqr_leaves", "tsqr_rows_per_node", "tsqr_last_leaf_kernel", "tsqr_last_tree", "tsqr_last_qh": what the last
@@ -299,7 +333,8 @@ struct ovgpu_ctx {
   int gram_wg_n = 0, gram_wg_tiles = 0;
   gram::GramRegionSum raw_rs;      // the regions that have workgroups, for k_gram_regions_reduce
   bool last_stack_raw = false;     // the last pipeline's Gram matrix came from the unprojected stack
-  DevBuf<int32_t> feat_counter, fs_minfo, fs_meas_feat, fs_pos; // fs_*: the row store of the fast path (feat::FeatStore); fs_pos: each measurement's clone-major position (k_batch_layout)
+  DevView<int32_t> feat_counter;
+  DevBuf<int32_t> fs_minfo, fs_meas_feat, fs_pos; // fs_*: the row store of the fast path (feat::FeatStore); fs_pos: each measurement's clone-major position (k_batch_layout)
   DevBuf<int32_t> fs_slots;   // [F][8] the fused kernels' schedule: per slot (features by descending track length) feature, first measurement, count, rows, row offset
   std::vector<int32_t> h_order; // the same order on the host
   std::vector<uint16_t> h_cc;   // packed (camera, clone) codes of the batch being uploaded (kept: no allocation per call)
@@ -308,7 +343,7 @@ struct ovgpu_ctx {
   struct LoopComm *loop = nullptr; // several ranks on ONE device (ovgpu_multi_create with a repeated device): the collective is emulated
   int comm_rank = 0, comm_world = 1;
   DevBuf<double> comm_buf;     // gathered triangles of the Householder exchange
-  DevBuf<int32_t> chol_prog;   // [2][16] per-step flags of the single-launch Cholesky (k_chol.h), one set per factorisation in flight
+  DevView<int32_t> chol_prog;  // [2][16] per-step flags of the single-launch Cholesky (k_chol.h), one set per factorisation in flight
   // flags (4), rows_used (1), feat_counter (1) and chol_prog (32) are views into ONE block, zeroed by one memset at the start of a
   // pipeline call; ctrl_clean says which of them have not been touched since (bits CTRL_*), so that the places that used to zero
   // them one by one (five 5-us launches per update) skip it
@@ -364,7 +399,8 @@ struct ovgpu_ctx {
   bool unwhiten_blocked = true;       // ovgpu_debug_option "unwhiten_blocked" (0: k_unwhiten of rounds 3-5)
   bool pchol_blocked = true;     // ovgpu_debug_option "pchol_blocked": mode A's pivoted factor by k_gram_pchol_blk (k_pchol.h; 0: the rank-one kernel of rounds 3-5)
   bool speculative_prior = true; // ovgpu_debug_option "speculative_prior": ovgpu_set_features starts that factorisation (api_pipeline.inc: enqueue_speculative_prior)
-  DevBuf<int32_t> gram_dropped, rows_used; // rows_used: rows of accepted features, counted by k_system
+  DevBuf<int32_t> gram_dropped;
+  DevView<int32_t> rows_used; // rows of accepted features, counted by k_system
   int sys_grid = 1;
   int64_t gate_ws_stride = 0;
   bool sys_rows_global = false;    // k_system_t<true>: the longest track's Jacobian records do not fit LDS
@@ -380,6 +416,36 @@ struct ovgpu_ctx {
   bool timing = true;
   int timing_period = 1;        // ovgpu_debug_option "stage_timing_period": the stage events go into every n-th update only (each is a
   uint64_t timing_seq = 0;      // marker packet the next kernel waits for: ~3 us apiece, six per update)
+};
+
+// The batch the stages run on: the view in force, or else the whole resident batch composed from its owners NOW (no pointer outlives a
+// reserve of its buffer, so none can go stale).  The one list of what a view replaces is Batch's members.
+static Batch batch_of(const ovgpu_ctx *c) {
+  if (c->view) return *c->view;
+  Batch b;
+  b.F = c->F, b.M = c->M, b.m_max = c->m_max, b.rows_total = c->rows_total;
+  b.h_offsets = span_of(c->h_offsets), b.h_order = span_of(c->h_order), b.h_feat_lm = span_of(c->h_feat_lm), b.h_row_off = span_of(c->h_row_off);
+  b.have_sigma = c->have_feat_sigma, b.have_mult = c->have_feat_mult;
+  b.meas_offsets = c->meas_offsets.p, b.sys_order = c->sys_order.p, b.status = c->status.p, b.meas_cc = c->meas_cc.p, b.uv = c->uv.p, b.uvn = c->uvn.p;
+  b.row_off = c->row_off.p, b.pA = c->pA.p, b.pG = c->pG.p, b.chi2 = c->chi2.p, b.chi2_thr = c->chi2_thr.p, b.feat_sigma = c->feat_sigma.p, b.feat_mult = c->feat_mult.p;
+  return b;
+}
+// puts a batch in force for a scope: no return path leaves it behind
+struct BatchScope {
+  ovgpu_ctx *c;
+  BatchScope(ovgpu_ctx *ctx, const Batch *b) : c(ctx) { c->view = b; }
+  ~BatchScope() { c->view = nullptr; }
+  BatchScope(const BatchScope &) = delete;
+  BatchScope &operator=(const BatchScope &) = delete;
+};
+// no stage events for a scope (ovgpu_ctx::timing)
+struct NoStageTiming {
+  ovgpu_ctx *c;
+  bool was;
+  explicit NoStageTiming(ovgpu_ctx *ctx) : c(ctx), was(ctx->timing) { c->timing = false; }
+  ~NoStageTiming() { c->timing = was; }
+  NoStageTiming(const NoStageTiming &) = delete;
+  NoStageTiming &operator=(const NoStageTiming &) = delete;
 };
 
 // removes element `idx` of a device array of `n` records of `w` doubles / ints (through a scratch copy: the ranges overlap)

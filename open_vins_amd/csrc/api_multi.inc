@@ -118,7 +118,7 @@ static int loop_finish(LoopComm *L, bool gram) {
 static int sharded_local(ovgpu_ctx *c, bool &gram) {
   gram = c->compress_gram == 1 && (c->LD + 15) / 16 <= gram::GR_NT_BLK && !c->force_tsqr;
   const int rc = enqueue_pipeline(c, STAGE_LOCAL, false, true, gram);
-  if (rc == OVGPU_OK && gram && c->F == 0) { // an empty shard: nothing was whitened here, but the sum it joins is the other ranks' whitened Gram matrix
+  if (rc == OVGPU_OK && gram && batch_of(c).F == 0) { // an empty shard: nothing was whitened here, but the sum it joins is the other ranks' whitened Gram matrix
     const size_t n = (size_t)256 * ((c->LD + 15) / 16) * ((c->LD + 15) / 16);
     HIPCHK(c->gram_G.reserve(n));
     c->gram_is_whitened = c->whiten;
@@ -132,7 +132,7 @@ static int sharded_exchange(ovgpu_ctx *c, bool gram) {
   const int G = c->comm_world;
   if (gram) {
     const size_t n = (size_t)256 * ((c->LD + 15) / 16) * ((c->LD + 15) / 16);
-    if (c->F == 0) HIPCHK(hipMemsetAsync(c->gram_G.p, 0, sizeof(double) * n, c->stream)); // an empty shard contributes nothing
+    if (batch_of(c).F == 0) HIPCHK(hipMemsetAsync(c->gram_G.p, 0, sizeof(double) * n, c->stream)); // an empty shard contributes nothing
     if (c->loop) return OVGPU_OK; // (loop_finish delivers the sum once every rank is here)
     if (G > 1) {
       const int rc = r.AllReduce(c->gram_G.p, c->gram_G.p, n, NCCL_DOUBLE, NCCL_SUM, c->comm, c->stream);
@@ -142,7 +142,7 @@ static int sharded_exchange(ovgpu_ctx *c, bool gram) {
   }
   const size_t tri = (size_t)c->D * c->LD;
   HIPCHK(c->comm_buf.reserve(tri * G));
-  if (c->F == 0) { // an empty shard's triangle is all zeros (the leaf kernels never ran): say so explicitly before it is gathered
+  if (batch_of(c).F == 0) { // an empty shard's triangle is all zeros (the leaf kernels never ran): say so explicitly before it is gathered
     HIPCHK(c->Rws.reserve(tri));
     HIPCHK(hipMemsetAsync(c->Rws.p, 0, sizeof(double) * tri, c->stream));
   }
@@ -429,7 +429,7 @@ int ovgpu_multi_msckf_update(ovgpu_multi *m, int32_t *feat_status, double *chi2,
   for (int g = 0; g < G; g++) {
     ovgpu_ctx *c = m->ctx[g];
     HIPCHK(hipSetDevice(c->device));
-    const int Fl = c->F;
+    const int Fl = batch_of(c).F;
     std::vector<int32_t> st(Fl);
     std::vector<double> c2(Fl), th(Fl), pg((size_t)3 * Fl);
     ovgpu_update_stats loc;

@@ -3,12 +3,13 @@
 // pipeline stages (all asynchronous on ctx->stream)
 // ---------------------------------------------------------------------------
 static int enqueue_triangulate(ovgpu_ctx *c, const double *seed_pA = nullptr, const int32_t *seed_anchor = nullptr) {
-  if (c->F == 0) return OVGPU_OK;
+  const Batch b = batch_of(c);
+  if (b.F == 0) return OVGPU_OK;
   TriParams p;
   p.seed_pA = seed_pA, p.seed_anchor = seed_anchor, p.anchor_pre = c->anchor_pre.p;
-  p.F = c->F, p.C = c->C, p.K = c->K;
-  p.meas_offsets = c->meas_offsets.p, p.meas_cc = c->meas_cc.p, p.uvn = c->uvn.p, p.tab_cc = c->tab_cc.p;
-  p.p_FinA = c->pA.p, p.p_FinG = c->pG.p, p.anchor_meas = c->anchor.p, p.status = c->status.p;
+  p.F = b.F, p.C = c->C, p.K = c->K;
+  p.meas_offsets = b.meas_offsets, p.meas_cc = b.meas_cc, p.uvn = b.uvn, p.tab_cc = c->tab_cc.p;
+  p.p_FinA = b.pA, p.p_FinG = b.pG, p.anchor_meas = c->anchor.p, p.status = b.status;
   p.opt = c->dopt;
   const size_t lds = (size_t)c->K * c->C * 12 * sizeof(double);
   // Features (wavefronts) per workgroup.  The prior block's factorisation is dispatched a few microseconds BEHIND this kernel and needs whole
@@ -21,14 +22,14 @@ static int enqueue_triangulate(ovgpu_ctx *c, const double *seed_pA = nullptr, co
     wpb = 4;
     const int room = c->num_cu - 6;
     for (int w = 4; w <= 8 && room > 0; w *= 2) {
-      const int blocks = (c->F + w - 1) / w;
+      const int blocks = (b.F + w - 1) / w;
       if (blocks <= room) {
         if (4 * blocks >= 3 * room) wpb = w;
         break;
       }
     }
   }
-  hipLaunchKernelGGL(k_triangulate, dim3((c->F + wpb - 1) / wpb), dim3(64 * wpb), lds, c->stream, p);
+  hipLaunchKernelGGL(k_triangulate, dim3((b.F + wpb - 1) / wpb), dim3(64 * wpb), lds, c->stream, p);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
@@ -49,7 +50,7 @@ static int launch_featy(ovgpu_ctx *c, const SysParams &p, const double *sr, cons
   const size_t lds = feat::featy_lds_layout(nt, nta, NW, CB).total;
   if (lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_CAPACITY, "k_feat_y: track too long for its LDS block");
   const int per_cu = std::max(1, std::min(std::max(1, 4 * OCC / NW), (int)((size_t)c->lds_limit / lds))); // OCC wavefronts per SIMD, four SIMDs
-  const int grid = std::max(1, std::min(c->F, c->num_cu * per_cu));
+  const int grid = std::max(1, std::min(batch_of(c).F, c->num_cu * per_cu));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl);
   return OVGPU_OK;
 }
@@ -58,31 +59,31 @@ static int launch_featy(ovgpu_ctx *c, const SysParams &p, const double *sr, cons
 // f_one >= 0: only that feature, in StateHelper::initialize mode with the landmark representation init_rep
 // whiten: the rows leave as [H L | r] with L = c->Lw (the prior block's factor must be complete on this stream)
 static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool whiten = false) {
-  if (c->F == 0) return OVGPU_OK;
+  const Batch b = batch_of(c);
+  if (b.F == 0) return OVGPU_OK;
   SysParams p;
-  p.F = c->F, p.C = c->C, p.K = c->K, p.D = c->D, p.LD = c->LD, p.N = c->N;
-  p.meas_offsets = c->meas_offsets.p, p.meas_cc = c->meas_cc.p, p.uv = c->uv.p;
+  p.F = b.F, p.C = c->C, p.K = c->K, p.D = c->D, p.LD = c->LD, p.N = c->N;
+  p.meas_offsets = b.meas_offsets, p.meas_cc = b.meas_cc, p.uv = b.uv;
   p.tab_clone = c->tab_clone.p, p.tab_cam = c->tab_cam.p, p.intr = c->intr.p, p.fisheye = c->fisheye.p;
   p.clone_col = c->clone_col.p, p.calib_col = c->calib_col.p, p.intr_col = c->intr_col.p;
   p.col_cov = c->col_cov.p, p.col_kind = c->col_kind.p, p.col_var = c->col_var.p, p.col_sub = c->col_sub.p;
-  p.P = c->P.p, p.p_FinG = c->pG.p, p.p_FinA = c->pA.p, p.anchor_meas = c->anchor.p;
-  p.status = c->status.p, p.chi2 = c->chi2.p, p.chi2_thresh = c->chi2_thr.p;
+  p.P = c->P.p, p.p_FinG = b.pG, p.p_FinA = b.pA, p.anchor_meas = c->anchor.p;
+  p.status = b.status, p.chi2 = b.chi2, p.chi2_thresh = b.chi2_thr;
   p.chi2_table = c->chi2_table.p, p.chi2_table_len = c->chi2_table_len;
-  p.row_off = c->row_off.p, p.Hbig = c->Hbig.p, p.ws = c->gate_ws.p, p.ws_stride = c->gate_ws_stride;
+  p.row_off = b.row_off, p.Hbig = c->Hbig.p, p.ws = c->gate_ws.p, p.ws_stride = c->gate_ws_stride;
   p.Hbig32 = nullptr, p.LDF = 0;
   c->stack_is_f32 = false;
-  p.m_lds_max = c->m_lds_max, p.m_max = std::max(c->m_max, 1), p.row_stride = c->row_stride;
+  p.m_lds_max = c->m_lds_max, p.m_max = std::max(b.m_max, 1), p.row_stride = c->row_stride;
   p.opt = c->dopt;
   p.dbg = c->dbg_cycles.p ? c->dbg_cycles.p : qr_dbg_buffer();
   p.slam = c->slam_rows ? 1 : 0;
   p.p_fej = c->pFej.p, p.feat_lm = c->feat_lm.p, p.feat_lmcol = c->feat_lmcol.p, p.feat_lmcov = c->feat_lmcov.p, p.feat_anchor = c->feat_anchor.p;
   p.lm_size = 3, p.init_dof_less = 0, p.lm_rep = nullptr;
-  p.feat_sigma = c->have_feat_sigma ? c->feat_sigma.p : nullptr, p.feat_chi2mult = c->have_feat_mult ? c->feat_mult.p : nullptr;
+  p.feat_sigma = b.have_sigma ? b.feat_sigma : nullptr, p.feat_chi2mult = b.have_mult ? b.feat_mult : nullptr;
   if (p.slam) { // the landmarks' representation, not the MSCKF features'; single depth = MSCKF inverse depth Jacobians (UpdaterSLAM.cpp:338-341)
     p.lm_rep = c->lm_repd.p; // per landmark: k_system reads the representation and the size from the landmark each feature observes
   }
-  p.f_begin = 0, p.f_end = c->F, p.init = 0, p.init_out = nullptr, p.init_flag = nullptr, p.init_keep = 0, p.order = c->sys_order.p;
-  HIPCHK(c->rows_used.reserve(2));
+  p.f_begin = 0, p.f_end = b.F, p.init = 0, p.init_out = nullptr, p.init_flag = nullptr, p.init_keep = 0, p.order = b.sys_order;
   p.rows_used = c->rows_used.p;
   p.Lw = (whiten && f_one < 0) ? c->Lw.p : nullptr;
   p.skip = c->featy_skip;
@@ -107,7 +108,6 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   if (p.Lw && c->feat_variant && (c->L == 0 || (c->lm_fast_on && c->lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
     p.row_stride = 48; // the fused kernels' records (fs_rows holds M * c->row_stride >= 48 M doubles): a 72-double stride — an anchored feat_rep_msckf, anchored
                        // landmarks, an earlier delayed initialisation — is the general kernel's alone
-    HIPCHK(c->feat_counter.reserve(1));
     HIPCHK(ctrl_zero(c, CTRL_COUNTER, c->feat_counter.p, sizeof(int32_t), c->stream));
     p.work_counter = c->feat_counter.p;
     // rows (per measurement) -> gate (needs P only) -> projected whitened rows (need L and z).  The prior block's factorisation and
@@ -126,14 +126,14 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
       }
       if (featy_stack_f32(c, f_one)) { // options.gram_fp32: the rows leave as floats, stride 32 ceil(LD / 32) (k_gram32.h)
         c->stack_ldf = ((c->LD + 31) / 32) * 32;
-        HIPCHK(c->Hbig32.reserve((size_t)(std::max<int64_t>(c->rows_total, 1) + 32) * c->stack_ldf));
+        HIPCHK(c->Hbig32.reserve((size_t)(std::max<int64_t>(b.rows_total, 1) + 32) * c->stack_ldf));
         // k_gram_f32 copies whole 32-row stages: the rows behind the last feature's must read as zeros
-        HIPCHK(hipMemsetAsync(c->Hbig32.p + (size_t)c->rows_total * c->stack_ldf, 0, sizeof(float) * 32 * c->stack_ldf, c->stream));
+        HIPCHK(hipMemsetAsync(c->Hbig32.p + (size_t)b.rows_total * c->stack_ldf, 0, sizeof(float) * 32 * c->stack_ldf, c->stream));
         p.Hbig32 = c->Hbig32.p, p.LDF = c->stack_ldf;
         c->stack_is_f32 = true;
       }
-      if (p.opt.feat_rep >= OVGPU_REP_ANCHORED_3D) hipLaunchKernelGGL(feat::k_feat_rows_anchored, dim3((c->M + 255) / 256), dim3(256), 0, c->stream, p, st, c->M);
-      else hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((c->M + 255) / 256), dim3(256), 0, c->stream, p, st, c->M);
+      if (p.opt.feat_rep >= OVGPU_REP_ANCHORED_3D) hipLaunchKernelGGL(feat::k_feat_rows_anchored, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
+      else hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
       const bool big = c->feat_variant == 3 || c->featy_big;
       const int cb = featy_block_cols(c, p.Hbig32 != nullptr);
       if (c->raw_enable && c->raw_tables_ok && !c->raw_veto && !big && !p.Hbig32 && cb == feat::FY_CB) {
@@ -145,7 +145,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
         const int rci = enqueue_instance_lists(c, cb);
         if (rci != OVGPU_OK) return rci;
       }
-      hipLaunchKernelGGL(feat::k_feat_vt, dim3((c->F + 3) / 4), dim3(256), (size_t)4 * (14 * p.m_max + 64) * sizeof(double), c->stream, p, st, c->fs_tq.p);
+      hipLaunchKernelGGL(feat::k_feat_vt, dim3((b.F + 3) / 4), dim3(256), (size_t)4 * (14 * p.m_max + 64) * sizeof(double), c->stream, p, st, c->fs_tq.p);
       if (c->prior_on_side) { // (L and the carried columns come out of one launch since round 5)
         HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
         c->prior_on_side = false; // this stream is behind the factorisation from here on: the update's second half needs no wait of its own (a wait on a
@@ -161,7 +161,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
           (void)hipFuncSetAttribute((const void *)feat::k_feat_y_big<8, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
           attr_b = true;
         }
-        const int nt = c->feat_nt_max, gridb = std::max(1, std::min(c->F, c->num_cu));
+        const int nt = c->feat_nt_max, gridb = std::max(1, std::min(b.F, c->num_cu));
         const size_t ldsb = feat::featyb_lds_layout(nt, 8).total;
         if (ldsb > (size_t)c->lds_limit || nt > 29) return set_err(OVGPU_ERR_CAPACITY, "k_feat_y_big: track too long for its LDS block");
         HIPCHK(c->featyb_ws.reserve((size_t)gridb * feat::featyb_ws_doubles(nt)));
@@ -281,7 +281,8 @@ static int enqueue_merge_tree(ovgpu_ctx *c, int G, bool leaves_live = false, hip
 static int enqueue_gram_factor(ovgpu_ctx *c);
 static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   const int D = c->D, LD = c->LD, NT = (LD + 15) / 16, NP = NT * (NT + 1) / 2, LG = 16 * NT;
-  const int64_t nchunks = (c->rows_total + gram::GR_ROWS - 1) / gram::GR_ROWS;
+  const int64_t rows_total = batch_of(c).rows_total;
+  const int64_t nchunks = (rows_total + gram::GR_ROWS - 1) / gram::GR_ROWS;
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>(c->num_cu, nchunks));
   HIPCHK(c->gram_part.reserve((size_t)G * NP * 256));
   HIPCHK(c->gram_G.reserve((size_t)LG * LG));
@@ -296,8 +297,8 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
       c->gram32_ntm = NTM, c->gram32_P = P;
     }
     // workgroups per part: no more than G32_ROWS_WG rows each; on a short stack as many as keep every compute unit busy (>= 4 stages each)
-    const int64_t by_rows = (c->rows_total + gram32::G32_ROWS_WG - 1) / gram32::G32_ROWS_WG;
-    const int64_t by_cus = std::min<int64_t>((2 * c->num_cu + P - 1) / P, (c->rows_total + 127) / 128);
+    const int64_t by_rows = (rows_total + gram32::G32_ROWS_WG - 1) / gram32::G32_ROWS_WG;
+    const int64_t by_cus = std::min<int64_t>((2 * c->num_cu + P - 1) / P, (rows_total + 127) / 128);
     const int Gw = (int)std::max<int64_t>(1, std::max(by_rows, by_cus));
     HIPCHK(c->gram32_part.reserve((size_t)P * Gw * gram32::G32_NW * gram32::G32_MAXT * 1024));
     static bool attr32 = false;
@@ -306,7 +307,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
       attr32 = true;
     }
     gram32::Gram32Params q;
-    q.H = c->Hbig32.p, q.part = c->gram32_part.p, q.tiles = c->gram32_tiles.p, q.rows_total = c->rows_total, q.LDF = LDF, q.LD = LD;
+    q.H = c->Hbig32.p, q.part = c->gram32_part.p, q.tiles = c->gram32_tiles.p, q.rows_total = rows_total, q.LDF = LDF, q.LD = LD;
     hipLaunchKernelGGL(gram32::k_gram_f32, dim3(Gw, P), dim3(gram32::G32_NTH), gram32::gram32_lds_bytes(LDF), c->stream, q);
     hipLaunchKernelGGL(gram32::k_gram_f32_reduce, dim3(slots, 4), dim3(256), 0, c->stream, (const int32_t *)c->gram32_tiles.p, Gw,
                        (const float *)c->gram32_part.p, c->gram_G.p, LG);
@@ -329,7 +330,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     return factor ? enqueue_gram_factor(c) : OVGPU_OK;
   }
   gram::GramParams g;
-  g.LD = LD, g.NT = NT, g.rows_total = c->rows_total, g.H = c->Hbig.p, g.part = c->gram_part.p;
+  g.LD = LD, g.NT = NT, g.rows_total = rows_total, g.H = c->Hbig.p, g.part = c->gram_part.p;
   if (NT == gram::GR_NT + 7 && !c->gram_fp32 && !c->gram_blocks_only) { // configs[4]'s 23 tile columns: two passes over the stack (k_gram_wide)
     static bool attr_w = false;
     if (!attr_w) {
@@ -417,6 +418,7 @@ static int enqueue_compress(ovgpu_ctx *c) {
   const int D = c->D, LD = c->LD;
   const int NT = (LD + 15) / 16;
   const int W = c->W;
+  const int64_t rows_total = batch_of(c).rows_total;
   c->tsqr_last_W = W, c->tsqr_last_rpn = c->rows_per_node, c->tsqr_last_tree = 0, c->tsqr_last_qh = 0;
   c->tsqr_last_leaf = NT <= 15 ? 0 : (NT == 16 ? 1 : 2);
   if (NT <= 16) {
@@ -424,7 +426,7 @@ static int enqueue_compress(ovgpu_ctx *c) {
     q.D = D, q.LD = LD, q.NT = NT;
     q.acc = c->Rws.p, q.acc_stride = 1;
     q.src = c->Hbig.p, q.src_stride = 0;
-    q.rows_per_node = c->rows_per_node, q.rows_total = c->rows_total, q.zero_init = 1, q.dbg = qr_dbg_buffer(), q.progress = nullptr;
+    q.rows_per_node = c->rows_per_node, q.rows_total = rows_total, q.zero_init = 1, q.dbg = qr_dbg_buffer(), q.progress = nullptr;
     // The merge tree can run NEXT TO the leaf kernel (second stream): leaf nodes publish the panels of their last append
     // as they finish, level-1 merge nodes pick them up.  Both kernels run 256-VGPR waves, two per SIMD, so a leaf and a
     // merge workgroup do NOT share a CU: the overlap pays only while leaves + merge nodes (2W-1) fit the chip one per CU
@@ -456,7 +458,7 @@ static int enqueue_compress(ovgpu_ctx *c) {
     q.D = D, q.LD = LD;
     q.dst = c->Rws.p, q.dst_wg_stride = 1;
     q.src = c->Hbig.p, q.src_wg_stride = c->rows_per_node * LD;
-    q.src_rows_per_wg = c->rows_per_node, q.src_rows_total = c->rows_total, q.triangular = 0, q.zero_dst = 1;
+    q.src_rows_per_wg = c->rows_per_node, q.src_rows_total = rows_total, q.triangular = 0, q.zero_dst = 1;
     hipLaunchKernelGGL(k_qr_append<QR_B>, dim3(W), dim3(nt), 0, c->stream, q);
     HIPCHK(hipGetLastError());
   }
@@ -544,7 +546,6 @@ static int launch_chol_fused(ovgpu_ctx *c, chol::CholParams &q, int slot, hipStr
 static bool chol_wide_usable(const ovgpu_ctx *c, int D) { return !c->no_chol_pipe && c->chol_wide && D > chol::CW_D1 && D <= 2 * chol::CW_D1; }
 static int enqueue_chol_wide(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, double *Lt) {
   const int D2 = p.D - chol::CW_D1, LA2 = p.LA - chol::CW_D1;
-  HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
   HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
   HIPCHK(c->chol_wide_A.reserve((size_t)D2 * LA2));
   HIPCHK(c->chol_wide_Y.reserve((size_t)D2 * LA2));
@@ -576,7 +577,6 @@ static int enqueue_chol_wide(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, do
 static int enqueue_chol_carry(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, double *Lt, const CholSource &from) {
   if (chol_pipe_usable(c, p.D)) {
     // one launch: the factor workgroup's chain stays inside a compute unit, the carried columns follow through flags (k_chol.h)
-    HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
     HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
     const int slot = chol_next_slot(c);
     chol::CholParams q;
@@ -753,6 +753,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
     const int rcl = set_row_layout(c, slam);
     if (rcl != OVGPU_OK) return rcl;
   }
+  const Batch b = batch_of(c);
   EventPair *eu = nullptr, *ec = nullptr, *es = nullptr;
   bool tform = false;
   if (c->timing && (c->timing_period <= 1 || c->timing_seq++ % c->timing_period == 0)) {
@@ -765,7 +766,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   c->timed_this_update = eu != nullptr; // fill_times: an update that recorded no events reports no stage times (not an earlier update's)
   if (eu) HIPCHK(hipEventRecord(eu->a, c->stream));
   int rc = OVGPU_OK;
-  const bool fits = (c->LD + 15) / 16 <= gram::GR_NT_BLK && c->F > 0;
+  const bool fits = (c->LD + 15) / 16 <= gram::GR_NT_BLK && b.F > 0;
   tform = !gram_only && c->compress_gram == 1 && !c->force_tsqr && fits && (stages & STAGE_EKF) != 0 && (stages & STAGE_LOCAL) != 0;
   // Mode A through the Gram matrix: whitened rows -> Gram matrix -> its Cholesky factor -> un-whitened (k_unwhiten): a compressed (H, r)
   // of the reference's form at the cost of the Gram route instead of the Householder TSQR's (4.0 ms host to host at 2000 features).
@@ -775,7 +776,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   //     tests/test_gpu_parity.py::test_mode_a_pivoted_factor_shapes).
   // compress_route = OVGPU_COMPRESS_TSQR keeps the Householder triangle; so do SLAM stacks, more than 383 columns, the fp32 Gram
   // variant, an un-whitened stack and a prior block whose own factorisation fails (compress_impl repeats the call then).
-  const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && c->F > 0 && (c->LD + 15) / 16 <= gram::GR_NT_BLK &&
+  const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && b.F > 0 && (c->LD + 15) / 16 <= gram::GR_NT_BLK &&
                            (stages & STAGE_EKF) == 0 && (stages & STAGE_LOCAL) != 0 && c->whiten && !c->gram_fp32 && !slam; // (the SLAM stack is short: its mode A stays Householder)
   c->factor_from_gram = false, c->last_factor_from_gram = factor_gram;
   c->force_tsqr = false;
@@ -797,7 +798,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   if (stages & STAGE_LOCAL) {
     if (c->given_tri) {
       // the gate overwrites status; restore the caller's per-feature status for this run
-      if (c->F > 0) HIPCHK(hipMemcpyAsync(c->status.p, c->given_status.p, sizeof(int32_t) * c->F, hipMemcpyDeviceToDevice, c->stream));
+      if (b.F > 0) HIPCHK(hipMemcpyAsync(b.status, c->given_status.p, sizeof(int32_t) * b.F, hipMemcpyDeviceToDevice, c->stream));
     } else if ((rc = enqueue_triangulate(c)) != OVGPU_OK) return rc;
     if (es) HIPCHK(hipEventRecord(es->a, c->stream));
     c->want_stack_f32 = c->gram_fp32 && whiten && (gram_only || tform) && (c->LD + 31) / 32 <= 12;
@@ -858,7 +859,8 @@ struct PendingFeatOut {
   size_t o_st = 0, o_c2 = 0, o_th = 0, o_pg = 0, o_gb = 0, end = 0;
 };
 static void unpack_feature_outputs(ovgpu_ctx *c, const PendingFeatOut &q) {
-  const int F = c->F;
+  const Batch b = batch_of(c);
+  const int F = b.F;
   int32_t *feat_status = q.feat_status;
   double *chi2 = q.chi2, *chi2_thresh = q.chi2_thresh, *p_FinG = q.p_FinG;
   ovgpu_update_stats *stats = q.stats;
@@ -874,12 +876,12 @@ static void unpack_feature_outputs(ovgpu_ctx *c, const PendingFeatOut &q) {
   const double qnan = std::nan("");
   int n_used = 0;
   int64_t rows = 0;
-  const std::vector<int32_t> &offs = c->h_offsets;
+  const HostSpan<int32_t> &offs = b.h_offsets;
   for (int f = 0; f < F; f++) {
     if (st[f] == OVGPU_FEAT_USED) {
       n_used++;
       // SLAM stacks all 2m rows (2m - 2 for a single-depth landmark)
-      const int ldof = (c->slam_rows && (int)c->h_feat_lm.size() == F) ? lm_dof(c->h_lm_rep[c->h_feat_lm[f]]) : 3;
+      const int ldof = (c->slam_rows && (int)b.h_feat_lm.size() == F) ? lm_dof(c->h_lm_rep[b.h_feat_lm[f]]) : 3;
       rows += 2 * (offs[f + 1] - offs[f]) - (c->slam_rows ? 3 - ldof : 3);
     }
     // the gate is only reached by features that triangulated
@@ -898,7 +900,8 @@ static void unpack_feature_outputs(ovgpu_ctx *c, const PendingFeatOut &q) {
 }
 static int read_feature_outputs(ovgpu_ctx *c, int32_t *feat_status, double *chi2, double *chi2_thresh, double *p_FinG, ovgpu_update_stats *stats,
                                 PendingFeatOut *pend = nullptr, size_t tail_bytes = 0) {
-  const int F = c->F;
+  const Batch b = batch_of(c);
+  const int F = b.F;
   hipStream_t s = c->stream;
   PendingFeatOut q;
   q.feat_status = feat_status, q.chi2 = chi2, q.chi2_thresh = chi2_thresh, q.p_FinG = p_FinG, q.stats = stats;
@@ -908,11 +911,11 @@ static int read_feature_outputs(ovgpu_ctx *c, int32_t *feat_status, double *chi2
     q.o_gb = (q.o_pg + sizeof(double) * 3 * F + 63) & ~(size_t)63;
     q.end = q.o_gb + 64;
     HIPCHK(down_reserve(c, q.end + tail_bytes)); // (before the first copy: a later reserve that grew the zone would free it under the copies)
-    HIPCHK(download_deferred(c, q.o_st, c->status.p, sizeof(int32_t) * F));
+    HIPCHK(download_deferred(c, q.o_st, b.status, sizeof(int32_t) * F));
     if (stats) HIPCHK(download_deferred(c, q.o_gb, c->rows_used.p + 1, sizeof(int32_t)));
-    if (chi2) HIPCHK(download_deferred(c, q.o_c2, c->chi2.p, sizeof(double) * F));
-    if (chi2_thresh) HIPCHK(download_deferred(c, q.o_th, c->chi2_thr.p, sizeof(double) * F));
-    if (p_FinG) HIPCHK(download_deferred(c, q.o_pg, c->pG.p, sizeof(double) * 3 * F));
+    if (chi2) HIPCHK(download_deferred(c, q.o_c2, b.chi2, sizeof(double) * F));
+    if (chi2_thresh) HIPCHK(download_deferred(c, q.o_th, b.chi2_thr, sizeof(double) * F));
+    if (p_FinG) HIPCHK(download_deferred(c, q.o_pg, b.pG, sizeof(double) * 3 * F));
   } else if (tail_bytes) {
     HIPCHK(down_reserve(c, tail_bytes));
   }
@@ -944,13 +947,14 @@ int ovgpu_triangulate(ovgpu_ctx *c, double *p_FinA, double *p_FinG, int32_t *anc
   HIPCHK(hipSetDevice(c->device));
   int rc = enqueue_triangulate(c);
   if (rc != OVGPU_OK) return rc;
-  const int F = c->F;
+  const Batch b = batch_of(c);
+  const int F = b.F;
   hipStream_t s = c->stream;
   if (F > 0) {
-    if (p_FinA) HIPCHK(hipMemcpyAsync(p_FinA, c->pA.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
-    if (p_FinG) HIPCHK(hipMemcpyAsync(p_FinG, c->pG.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if (p_FinA) HIPCHK(hipMemcpyAsync(p_FinA, b.pA, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if (p_FinG) HIPCHK(hipMemcpyAsync(p_FinG, b.pG, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
     if (anchor_meas) HIPCHK(hipMemcpyAsync(anchor_meas, c->anchor.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->status.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
+    if (status) HIPCHK(hipMemcpyAsync(status, b.status, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(upload_sync(c, s));
   return OVGPU_OK;
@@ -960,7 +964,8 @@ int ovgpu_refine(ovgpu_ctx *c, const double *p_FinA_in, const int32_t *anchor_me
   if (!c || !p_FinA_in || !anchor_meas_in) return set_err(OVGPU_ERR_INVALID, "null argument");
   if (!c->have_state || !c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "state / features not set");
   HIPCHK(hipSetDevice(c->device));
-  const int F = c->F;
+  const Batch b = batch_of(c);
+  const int F = b.F;
   hipStream_t s = c->stream;
   HIPCHK(c->seed_pA.reserve((size_t)3 * std::max(F, 1)));
   HIPCHK(c->seed_anchor.reserve(std::max(F, 1)));
@@ -971,9 +976,9 @@ int ovgpu_refine(ovgpu_ctx *c, const double *p_FinA_in, const int32_t *anchor_me
   const int rc = enqueue_triangulate(c, c->seed_pA.p, c->seed_anchor.p);
   if (rc != OVGPU_OK) return rc;
   if (F > 0) {
-    if (p_FinA) HIPCHK(hipMemcpyAsync(p_FinA, c->pA.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
-    if (p_FinG) HIPCHK(hipMemcpyAsync(p_FinG, c->pG.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
-    if (status) HIPCHK(hipMemcpyAsync(status, c->status.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
+    if (p_FinA) HIPCHK(hipMemcpyAsync(p_FinA, b.pA, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if (p_FinG) HIPCHK(hipMemcpyAsync(p_FinG, b.pG, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if (status) HIPCHK(hipMemcpyAsync(status, b.status, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(upload_sync(c, s));
   return OVGPU_OK;
@@ -983,12 +988,13 @@ int ovgpu_get_triangulation(ovgpu_ctx *c, double *p_FinA, double *p_FinG, int32_
   if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
   if (!c->have_state || !(c->have_feats || c->tri_readable)) return set_err(OVGPU_ERR_NO_STATE, "state / features not set");
   HIPCHK(hipSetDevice(c->device));
-  const int F = c->F;
+  const Batch b = batch_of(c);
+  const int F = b.F;
   hipStream_t s = c->stream;
   if (F > 0) {
-    if ((p_FinA && !c->pA.p) || (p_FinG && !c->pG.p) || (anchor_meas && !c->anchor.p)) return set_err(OVGPU_ERR_NO_STATE, "no triangulation has run on these features");
-    if (p_FinA) HIPCHK(hipMemcpyAsync(p_FinA, c->pA.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
-    if (p_FinG) HIPCHK(hipMemcpyAsync(p_FinG, c->pG.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if ((p_FinA && !b.pA) || (p_FinG && !b.pG) || (anchor_meas && !c->anchor.p)) return set_err(OVGPU_ERR_NO_STATE, "no triangulation has run on these features");
+    if (p_FinA) HIPCHK(hipMemcpyAsync(p_FinA, b.pA, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    if (p_FinG) HIPCHK(hipMemcpyAsync(p_FinG, b.pG, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
     if (anchor_meas) HIPCHK(hipMemcpyAsync(anchor_meas, c->anchor.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(upload_sync(c, s));
@@ -1001,19 +1007,20 @@ int ovgpu_set_triangulation(ovgpu_ctx *c, const double *p_FinA, const double *p_
   if (c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D && (!p_FinA || !anchor_meas))
     return set_err(OVGPU_ERR_INVALID, "anchored representations need p_FinA and anchor_meas");
   HIPCHK(hipSetDevice(c->device));
-  const int F = c->F;
+  const Batch b = batch_of(c);
+  const int F = b.F;
   hipStream_t s = c->stream;
   std::vector<int32_t> st(F, OVGPU_FEAT_USED);
   for (int f = 0; f < F; f++) {
     if (status) st[f] = status[f];
-    if (c->h_offsets[f + 1] - c->h_offsets[f] < 2) st[f] = OVGPU_FEAT_TOO_FEW_MEAS;
-    if (anchor_meas && st[f] == OVGPU_FEAT_USED && (anchor_meas[f] < c->h_offsets[f] || anchor_meas[f] >= c->h_offsets[f + 1]))
+    if (b.h_offsets[f + 1] - b.h_offsets[f] < 2) st[f] = OVGPU_FEAT_TOO_FEW_MEAS;
+    if (anchor_meas && st[f] == OVGPU_FEAT_USED && (anchor_meas[f] < b.h_offsets[f] || anchor_meas[f] >= b.h_offsets[f + 1]))
       return set_err(OVGPU_ERR_INVALID, "anchor_meas outside the feature's measurements");
   }
   HIPCHK(c->given_status.reserve(F));
   if (F > 0) {
-    HIPCHK(upload(c->pG.p, p_FinG, sizeof(double) * 3 * F, s));
-    if (p_FinA) HIPCHK(upload(c->pA.p, p_FinA, sizeof(double) * 3 * F, s));
+    HIPCHK(upload(b.pG, p_FinG, sizeof(double) * 3 * F, s));
+    if (p_FinA) HIPCHK(upload(b.pA, p_FinA, sizeof(double) * 3 * F, s));
     if (anchor_meas) HIPCHK(upload(c->anchor.p, anchor_meas, sizeof(int32_t) * F, s));
     HIPCHK(upload(c->given_status.p, st.data(), sizeof(int32_t) * F, s));
   }

@@ -107,15 +107,17 @@ int ovgpu_get_landmark_reps(ovgpu_ctx *c, int32_t *L_out, int32_t *feat_rep) {
 
 // One SLAM update on the stream for the F features whose landmarks lm_index_dev names: their per-feature landmark data gathered from the
 // resident landmarks, the system and the EKF update, the resident landmarks' share of dx.  No upload, no wait.
-static int enqueue_slam_gather(ovgpu_ctx *c, int F, const int32_t *lm_index_dev) {
+static int enqueue_slam_gather(ovgpu_ctx *c, const int32_t *lm_index_dev) {
+  const Batch b = batch_of(c);
+  const int F = b.F;
   if (F <= 0) return OVGPU_OK;
-  hipLaunchKernelGGL(k_slam_gather, dim3((F + 255) / 256), dim3(256), 0, c->stream, F, lm_index_dev, (const int32_t *)c->meas_offsets.p, landmark_store(c), c->pG.p,
-                     c->pA.p, c->pFej.p, c->feat_lm.p, c->feat_lmcol.p, c->feat_lmcov.p, c->feat_anchor.p, c->given_status.p);
+  hipLaunchKernelGGL(k_slam_gather, dim3((F + 255) / 256), dim3(256), 0, c->stream, F, lm_index_dev, (const int32_t *)b.meas_offsets, landmark_store(c), b.pG,
+                     b.pA, c->pFej.p, c->feat_lm.p, c->feat_lmcol.p, c->feat_lmcov.p, c->feat_anchor.p, c->given_status.p);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
-static int enqueue_slam_step(ovgpu_ctx *c, int F, const int32_t *lm_index_dev) {
-  int rc = enqueue_slam_gather(c, F, lm_index_dev);
+static int enqueue_slam_step(ovgpu_ctx *c, const int32_t *lm_index_dev) {
+  int rc = enqueue_slam_gather(c, lm_index_dev);
   if (rc != OVGPU_OK || (rc = enqueue_pipeline(c, STAGE_LOCAL | STAGE_EKF, true)) != OVGPU_OK) return rc;
   hipLaunchKernelGGL(k_landmark_update, dim3((3 * c->L + 255) / 256), dim3(256), 0, c->stream, c->L, (const int32_t *)nullptr, (const int32_t *)c->lm_repd.p, c->dx.p,
                      c->lm_cov.p, c->lm_val.p, (const int32_t *)nullptr);
@@ -155,7 +157,7 @@ static int slam_prepare(ovgpu_ctx *c, const int32_t *lm_index, ovgpu_update_stat
   if (F > 0) {
     HIPCHK(upload(c->lm_index.p, lm_index, sizeof(int32_t) * F, s));
     HIPCHK(upload_sync(c, s));
-    const int rcg = gather ? enqueue_slam_gather(c, F, c->lm_index.p) : (int)OVGPU_OK;
+    const int rcg = gather ? enqueue_slam_gather(c, c->lm_index.p) : (int)OVGPU_OK;
     if (rcg != OVGPU_OK) return rcg;
   }
   c->given_tri = true; // positions come from the state: no triangulation stage
@@ -168,7 +170,7 @@ int ovgpu_slam_update(ovgpu_ctx *c, const int32_t *lm_index, int32_t *feat_statu
   if (rc != OVGPU_OK) return rc;
   hipStream_t s = c->stream;
   return update_with_fallbacks(c, stats, [&]() {
-    int rc2 = enqueue_slam_step(c, c->F, c->lm_index.p); // (a repeat gathers again: the failed attempt left the landmarks as they were)
+    int rc2 = enqueue_slam_step(c, c->lm_index.p); // (a repeat gathers again: the failed attempt left the landmarks as they were)
     if (rc2 != OVGPU_OK) return rc2;
     PendingFeatOut pend; // one synchronisation for the per-feature outputs, the landmarks and dx / P'
     if ((rc2 = read_feature_outputs(c, feat_status, chi2, chi2_thresh, nullptr, stats, &pend, finish_update_bytes(c))) != OVGPU_OK) return rc2;
@@ -190,53 +192,43 @@ int ovgpu_slam_compress(ovgpu_ctx *c, const int32_t *lm_index, int32_t *feat_sta
 // ovgpu_set_features / ovgpu_slam_update pays per chunk a host walk of the columns, the batch's uploads, a blocking upload of lm_index and a
 // read-back with its synchronisation; none of it is needed between chunks: the batch, the indices and every chunk's column set are known up
 // front, the host sizes follow from the integer structure, and nothing a gate decides changes what is enqueued next.  Here: one upload (the
-// chunk table, every chunk's column set in column order, lm_index, the feature orders and row offsets), per chunk a VIEW of the resident
-// batch (BatchView below: sizes and host mirrors of the chunk, the device arrays at the chunk's offset — so a chunk's per-feature outputs
-// land at its place in the whole-batch arrays — the rebased offsets of k_chunk_offsets) under which the single call's own enqueue functions
-// run unchanged, k_chunk_collect behind each (k_slam_chunks.h), one gather and one synchronisation at the end.
+// chunk table, every chunk's column set in column order, lm_index, the feature orders and row offsets), per chunk a Batch VALUE (sizes and
+// host mirrors from the plan, the whole batch's device arrays at the chunk's offset — so a chunk's per-feature outputs land at its place in the
+// whole-batch arrays — the rebased offsets of k_chunk_offsets) put in force for the chunk's launches (BatchScope), under which the single
+// call's own enqueue functions run unchanged, k_chunk_collect behind each (k_slam_chunks.h), one gather and one synchronisation at the end.
 // ---------------------------------------------------------------------------
 namespace {
 struct ChunkPlan {
   int n = 0, F = 0;
   std::vector<int32_t> first, act_off, act, D, order; // act: the chunks' column sets, concatenated, each in covariance order; order: by descending track length, per chunk
+  std::vector<int32_t> h_offsets, m_max;              // the chunks' meas_offsets rebased to 0 (per chunk F_k + 1 entries, at first[k] + k) and longest tracks
   std::vector<int64_t> row_off;                       // per chunk F_k + 1 entries, at first[k] + k
   std::vector<int32_t> tab;                           // first | act | lm_index | order, as uploaded
   size_t o_act = 0, o_lm = 0, o_order = 0;
-  int D_max = 0, m_max = 0;
+  int D_max = 0;
   int64_t rows_max = 0;
-};
-// what a chunk's view replaces in the context
-struct BatchView {
-  int F, M, m_max;
-  int64_t rows_total;
-  std::vector<int32_t> h_offsets, h_order, h_feat_lm;
-  std::vector<int64_t> h_row_off;
-  bool have_sigma, have_mult, timing;
-  int32_t *meas_offsets, *sys_order, *status;
-  uint16_t *meas_cc;
-  float *uv, *uvn;
-  int64_t *row_off;
-  double *pA, *pG, *chi2, *chi2_thr, *feat_sigma, *feat_mult;
-  void save(ovgpu_ctx *c) {
-    F = c->F, M = c->M, m_max = c->m_max, rows_total = c->rows_total;
-    h_offsets = c->h_offsets, h_order = c->h_order, h_feat_lm = c->h_feat_lm, h_row_off = c->h_row_off;
-    have_sigma = c->have_feat_sigma, have_mult = c->have_feat_mult, timing = c->timing;
-    meas_offsets = c->meas_offsets.p, sys_order = c->sys_order.p, status = c->status.p, meas_cc = c->meas_cc.p, uv = c->uv.p, uvn = c->uvn.p;
-    row_off = c->row_off.p, pA = c->pA.p, pG = c->pG.p, chi2 = c->chi2.p, chi2_thr = c->chi2_thr.p, feat_sigma = c->feat_sigma.p, feat_mult = c->feat_mult.p;
-  }
-  void restore(ovgpu_ctx *c) const {
-    c->F = F, c->M = M, c->m_max = m_max, c->rows_total = rows_total;
-    c->h_offsets = h_offsets, c->h_order = h_order, c->h_feat_lm = h_feat_lm, c->h_row_off = h_row_off;
-    c->have_feat_sigma = have_sigma, c->have_feat_mult = have_mult, c->timing = timing;
-    c->meas_offsets.p = meas_offsets, c->sys_order.p = sys_order, c->status.p = status, c->meas_cc.p = meas_cc, c->uv.p = uv, c->uvn.p = uvn;
-    c->row_off.p = row_off, c->pA.p = pA, c->pG.p = pG, c->chi2.p = chi2, c->chi2_thr.p = chi2_thr, c->feat_sigma.p = feat_sigma, c->feat_mult.p = feat_mult;
-  }
 };
 } // namespace
 
-// Chunk k on the stream at the state the launches before it leave: the column map of its landmarks (k_active_columns on the resident set), the
-// view, the single call's gather / pipeline / landmark update, its results into slot k.  No upload, no wait.
-static int enqueue_chunk(ovgpu_ctx *c, const ChunkPlan &pl, const BatchView &w, int k) {
+// Chunk k of the whole batch w as a value: the plan's arrays for the host mirrors, w's device arrays at the chunk's offsets
+static Batch chunk_batch(const ovgpu_ctx *c, const ChunkPlan &pl, const Batch &w, int k) {
+  const int f0 = pl.first[k], Fk = pl.first[k + 1] - f0, m0 = w.h_offsets[f0];
+  const size_t at = (size_t)f0 + k;
+  Batch b = w;
+  b.F = Fk, b.M = w.h_offsets[f0 + Fk] - m0, b.m_max = pl.m_max[k], b.rows_total = pl.row_off[at + Fk];
+  b.h_offsets = {pl.h_offsets.data() + at, (size_t)Fk + 1}, b.h_row_off = {pl.row_off.data() + at, (size_t)Fk + 1};
+  b.h_order = {pl.order.data() + f0, (size_t)Fk}, b.h_feat_lm = {pl.tab.data() + pl.o_lm + f0, (size_t)Fk};
+  b.meas_offsets = c->chk_offs.p + at, b.sys_order = c->chk_tab.p + pl.o_order + f0, b.row_off = c->chk_rowoff.p + at;
+  b.meas_cc = w.meas_cc + m0, b.uv = w.uv + 2 * (size_t)m0, b.uvn = w.uvn + 2 * (size_t)m0;
+  b.status = w.status + f0, b.chi2 = w.chi2 + f0, b.chi2_thr = w.chi2_thr + f0, b.pA = w.pA + 3 * (size_t)f0, b.pG = w.pG + 3 * (size_t)f0;
+  if (w.have_sigma) b.feat_sigma = w.feat_sigma + f0;
+  if (w.have_mult) b.feat_mult = w.feat_mult + f0;
+  return b;
+}
+
+// Chunk k on the stream at the state the launches before it leave: the column map of its landmarks (k_active_columns on the resident set), its
+// batch in force, the single call's gather / pipeline / landmark update, its results into slot k.  No upload, no wait.
+static int enqueue_chunk(ovgpu_ctx *c, const ChunkPlan &pl, int k) {
   const int f0 = pl.first[k], Fk = pl.first[k + 1] - f0;
   if (Fk == 0) return OVGPU_OK; // an empty chunk does nothing (its dx row and flag words were zeroed with the others)
   hipStream_t s = c->stream;
@@ -246,27 +238,18 @@ static int enqueue_chunk(ovgpu_ctx *c, const ChunkPlan &pl, const BatchView &w, 
   int rc = layout_columns(c, false, c->chk_tab.p + pl.o_act + pl.act_off[k]);
   if (rc != OVGPU_OK) return rc;
   if (c->cols_over || c->D != pl.D[k]) return set_err(OVGPU_ERR_INVALID, "internal: a chunk's column count differs from the plan's");
-  // ---- the view
-  const int m0 = w.h_offsets[f0];
-  c->F = Fk, c->M = w.h_offsets[f0 + Fk] - m0;
-  c->h_offsets.resize(Fk + 1);
-  int m_max = 0;
-  for (int i = 0; i <= Fk; i++) c->h_offsets[i] = w.h_offsets[f0 + i] - m0;
-  for (int i = 0; i < Fk; i++) m_max = std::max(m_max, c->h_offsets[i + 1] - c->h_offsets[i]);
-  c->m_max = m_max;
-  c->h_order.assign(pl.order.begin() + f0, pl.order.begin() + f0 + Fk);
-  c->h_feat_lm.assign(pl.tab.begin() + pl.o_lm + f0, pl.tab.begin() + pl.o_lm + f0 + Fk);
-  c->meas_offsets.p = c->chk_offs.p + f0 + k, c->sys_order.p = c->chk_tab.p + pl.o_order + f0, c->row_off.p = c->chk_rowoff.p + f0 + k;
-  c->meas_cc.p = w.meas_cc + m0, c->uv.p = w.uv + 2 * (size_t)m0, c->uvn.p = w.uvn + 2 * (size_t)m0;
-  c->status.p = w.status + f0, c->chi2.p = w.chi2 + f0, c->chi2_thr.p = w.chi2_thr + f0, c->pA.p = w.pA + 3 * (size_t)f0, c->pG.p = w.pG + 3 * (size_t)f0;
-  c->have_feat_sigma = w.have_sigma, c->have_feat_mult = w.have_mult;
-  c->feat_sigma.p = w.have_sigma ? w.feat_sigma + f0 : w.feat_sigma, c->feat_mult.p = w.have_mult ? w.feat_mult + f0 : w.feat_mult;
-  if ((rc = set_row_layout(c, true, false, true)) != OVGPU_OK) return rc;
+  const Batch b = chunk_batch(c, pl, batch_of(c), k);
+  const BatchScope in_force(c, &b);
+  // the plan's rows (per landmark, from the whole batch's offsets) against the layout's rule on the batch the stages will see
+  std::vector<int64_t> rows(Fk + 1);
+  row_offsets_of(c, b, true, rows.data());
   for (int i = 0; i <= Fk; i++)
-    if (c->h_row_off[i] != pl.row_off[(size_t)f0 + k + i]) return set_err(OVGPU_ERR_INVALID, "internal: a chunk's row layout differs from the plan's");
+    if (rows[i] != b.h_row_off[i]) return set_err(OVGPU_ERR_INVALID, "internal: a chunk's row layout differs from the plan's");
+  c->slam_rows = true; // (the row offsets are on the device already and the batch's tables stay: the stage's sizes alone)
+  if ((rc = size_feature_stage(c)) != OVGPU_OK) return rc;
   c->have_feats = true, c->given_tri = true;
   // ---- the single call's launches
-  if ((rc = enqueue_slam_step(c, Fk, c->chk_tab.p + pl.o_lm + f0)) != OVGPU_OK) return rc;
+  if ((rc = enqueue_slam_step(c, c->chk_tab.p + pl.o_lm + f0)) != OVGPU_OK) return rc;
   ChunkCollect cc;
   cc.N = c->N, cc.dx = c->dx.p, cc.flags = c->flags.p, cc.gate = c->rows_used.p + 1;
   cc.dx_row = c->chk_dx.p + (size_t)k * c->N, cc.flags_out = c->chk_flags.p + 4 * k, cc.gate_out = c->chk_flags.p + 4 * pl.n + k;
@@ -309,7 +292,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   if (c->L <= 0) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_landmarks was never called");
   if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features must follow ovgpu_set_landmarks");
   if (n_chunks < 1 || n_chunks > 4096 || !chunk_first) return set_err(OVGPU_ERR_INVALID, "null chunk_first or no chunk");
-  const int F = c->F, n = n_chunks, N = c->N, L = c->L;
+  const int F = batch_of(c).F, n = n_chunks, N = c->N, L = c->L;
   if (chunk_first[0] != 0 || chunk_first[n] != F) return set_err(OVGPU_ERR_INVALID, "chunk_first must span [0, F]");
   for (int k = 0; k < n; k++)
     if (chunk_first[k + 1] < chunk_first[k]) return set_err(OVGPU_ERR_INVALID, "chunk_first not monotone");
@@ -319,12 +302,13 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   ChunkPlan pl;
   pl.n = n, pl.F = F;
   pl.first.assign(chunk_first, chunk_first + n + 1);
-  pl.act_off.assign(n + 1, 0), pl.D.assign(n, 0), pl.order.assign(std::max(F, 1), 0), pl.row_off.assign((size_t)F + n, 0);
+  pl.act_off.assign(n + 1, 0), pl.D.assign(n, 0), pl.m_max.assign(n, 0), pl.order.assign(std::max(F, 1), 0);
+  pl.h_offsets.assign((size_t)F + n, 0), pl.row_off.assign((size_t)F + n, 0);
   {
+    const HostSpan<int32_t> offs = batch_of(c).h_offsets;
     int D_fixed = 0;
     for (const auto &v : c->h_sorted) D_fixed += v.kind != COL_LANDMARK ? v.size : 0;
     std::vector<uint8_t> on(L);
-    std::vector<int32_t> start;
     for (int k = 0; k < n; k++) {
       const int f0 = pl.first[k], Fk = pl.first[k + 1] - f0;
       std::fill(on.begin(), on.end(), 0);
@@ -336,19 +320,16 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
       if (D + 1 > 512)
         return set_err(OVGPU_ERR_CAPACITY, "chunk " + std::to_string(k) + ": its " + std::to_string(n_act) + " landmarks give " + std::to_string(D) + " Jacobian columns, more than 511");
       pl.D_max = std::max(pl.D_max, D);
-      // rows (set_row_layout's rule with the landmarks named) and the order of k_system's slots (begin_feature_batch's counting sort), chunk-local
-      int mk = 0;
+      // chunk-local: the offsets, the rows (feature_rows with the landmarks named) and the order of k_system's slots (track_order)
+      int32_t *ho = pl.h_offsets.data() + f0 + k;
       int64_t *ro = pl.row_off.data() + f0 + k;
       for (int i = 0; i < Fk; i++) {
-        const int m = c->h_offsets[f0 + i + 1] - c->h_offsets[f0 + i], proj = 3 - lm_dof(c->h_lm_rep[lm_index[f0 + i]]);
-        ro[i + 1] = ro[i] + (2 * m > proj ? 2 * m - proj : 0);
-        mk = std::max(mk, m);
+        const int m = offs[f0 + i + 1] - offs[f0 + i];
+        ho[i + 1] = ho[i] + m, ro[i + 1] = ro[i] + feature_rows(true, m, 3 - lm_dof(c->h_lm_rep[lm_index[f0 + i]]));
+        pl.m_max[k] = std::max(pl.m_max[k], m);
       }
-      pl.rows_max = std::max(pl.rows_max, ro[Fk]), pl.m_max = std::max(pl.m_max, mk);
-      start.assign(mk + 2, 0);
-      for (int i = 0; i < Fk; i++) start[mk - (c->h_offsets[f0 + i + 1] - c->h_offsets[f0 + i]) + 1]++;
-      for (int b = 0; b <= mk; b++) start[b + 1] += start[b];
-      for (int i = 0; i < Fk; i++) pl.order[f0 + start[mk - (c->h_offsets[f0 + i + 1] - c->h_offsets[f0 + i])]++] = i;
+      pl.rows_max = std::max(pl.rows_max, ro[Fk]);
+      track_order(ho, Fk, pl.m_max[k], pl.order.data() + f0);
     }
   }
   { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; }
@@ -381,7 +362,6 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     HIPCHK(c->feat_lmcov.reserve(Fm));
     HIPCHK(c->feat_anchor.reserve(Fm));
     HIPCHK(c->given_status.reserve(Fm));
-    HIPCHK(c->rows_used.reserve(2));
     HIPCHK(c->chk_offs.reserve((size_t)F + n));
     HIPCHK(c->chk_rowoff.reserve((size_t)F + n));
     HIPCHK(c->chk_flags.reserve((size_t)5 * n));
@@ -399,17 +379,15 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   HIPCHK(upload_deferred(c, c->chk_tab.p, pl.tab.data(), sizeof(int32_t) * pl.tab.size()));
   HIPCHK(upload_deferred(c, c->chk_rowoff.p, pl.row_off.data(), sizeof(int64_t) * pl.row_off.size()));
   HIPCHK(upload_fence(c, s));
-  hipLaunchKernelGGL(k_chunk_offsets, dim3((F + n + 255) / 256), dim3(256), 0, s, n, F, (const int32_t *)c->chk_tab.p, (const int32_t *)c->meas_offsets.p, c->chk_offs.p);
+  hipLaunchKernelGGL(k_chunk_offsets, dim3((F + n + 255) / 256), dim3(256), 0, s, n, F, (const int32_t *)c->chk_tab.p, (const int32_t *)batch_of(c).meas_offsets, c->chk_offs.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
   HIPCHK(hipMemsetAsync(c->chk_dx.p, 0, sizeof(double) * (size_t)n * N, s));
   int rc = state_snapshot(c, c->chk_save.p, true, false); // the entry state, for the restore-and-chain path
   if (rc != OVGPU_OK) return rc;
   // ---- every chunk, one after the other on the stream
-  BatchView w;
-  w.save(c);
-  c->timing = false; // (no stage events inside the pass: six marker packets per chunk; ovgpu_update_stats::ms_* stay 0)
-  for (int k = 0; k < n && rc == OVGPU_OK; k++) rc = enqueue_chunk(c, pl, w, k);
+  const NoStageTiming untimed(c); // (no stage events inside the pass: six marker packets per chunk; ovgpu_update_stats::ms_* stay 0)
+  for (int k = 0; k < n && rc == OVGPU_OK; k++) rc = enqueue_chunk(c, pl, k);
   // ---- one read-back
   std::vector<int32_t> flags((size_t)5 * n, 0);
   const size_t al = 63;
@@ -420,6 +398,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     HIPCHK(down_reserve(c, o_end));
     HIPCHK(download_deferred(c, o_fl, c->chk_flags.p, sizeof(int32_t) * 5 * n));
     if (F > 0) {
+      const Batch w = batch_of(c);
       HIPCHK(download_deferred(c, o_st, w.status, sizeof(int32_t) * F));
       if (chi2) HIPCHK(download_deferred(c, o_c2, w.chi2, sizeof(double) * F));
       if (chi2_thresh) HIPCHK(download_deferred(c, o_th, w.chi2_thr, sizeof(double) * F));
@@ -431,9 +410,9 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     std::memcpy(flags.data(), c->down_arena.p + o_fl, sizeof(int32_t) * 5 * n);
     return OVGPU_OK;
   };
-  // on return the active set in force is "all" and the batch is the whole batch as uploaded (the all-landmarks map leaves with the gather's launch)
+  // on return the active set in force is "all" (the all-landmarks map leaves with the gather's launch); the batch was never anything but the
+  // whole batch as uploaded: no chunk's Batch outlives enqueue_chunk
   auto leave = [&]() -> int {
-    w.restore(c);
     c->h_feat_lm.assign(lm_index, lm_index + F);
     c->active_given = false, c->h_lm_active.clear();
     const int rcl = layout_columns(c); // (as ovgpu_set_active_landmarks(n < 0): the batch has to be handed over again before another update)
@@ -463,13 +442,11 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     if ((rc = launch_build_tables(c)) != OVGPU_OK) return rc;
     HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
     HIPCHK(hipMemsetAsync(c->chk_dx.p, 0, sizeof(double) * (size_t)n * N, s));
-    w.save(c);
-    c->timing = false;
     k_done = 0;
     for (int k = 0; k < n && status == OVGPU_OK; k++) {
       int32_t fl[4] = {0, 0, 0, 0};
       status = update_with_fallbacks(c, nullptr, [&]() {
-        int rc2 = enqueue_chunk(c, pl, w, k);
+        int rc2 = enqueue_chunk(c, pl, k);
         if (rc2 != OVGPU_OK) return rc2;
         if (hipMemcpyAsync(fl, c->chk_flags.p + 4 * k, sizeof(fl), hipMemcpyDeviceToHost, s) != hipSuccess || upload_sync(c, s) != hipSuccess)
           return set_err(OVGPU_ERR_HIP, "read-back of a chunk's flag words failed");
@@ -525,7 +502,8 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
 // (ovgpu_slam_init_systems): the system is copied out between the first two.  Lcap: landmark slots the update kernel covers.
 static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap, size_t init_lds, double *dx, const InitExportParams *exp) {
   hipStream_t s = c->stream;
-  const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+  const Batch b = batch_of(c);
+  const int m = b.h_offsets[f + 1] - b.h_offsets[f];
   int rc = enqueue_system(c, f, rep);
   if (rc != OVGPU_OK) return rc;
   if (exp && exp->rows * std::max(exp->h, 3) > 0) {
@@ -534,12 +512,12 @@ static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap
   }
   InitParams ip;
   ip.N = Nmax, ip.D = c->D, ip.LD = c->LD, ip.rep = rep, ip.f = f, ip.sz = lm_dof(rep), ip.col_cov = c->col_cov.p, ip.init_out = c->init_ws.p, ip.P = c->P.p;
-  ip.sigma2 = c->dopt.sigma_pix_sq, ip.ctr = c->init_ctr.p, ip.p_FinG = c->pG.p, ip.p_FinA = c->pA.p, ip.meas_cc = c->meas_cc.p;
+  ip.sigma2 = c->dopt.sigma_pix_sq, ip.ctr = c->init_ctr.p, ip.p_FinG = b.pG, ip.p_FinA = b.pA, ip.meas_cc = b.meas_cc;
   ip.anchor_meas = c->anchor.p, ip.lm = landmark_store(c), ip.feat_slot = c->feat_slot.p;
   hipLaunchKernelGGL(k_init_invertible, dim3(1), dim3(256), init_lds, s, ip);
   HIPCHK(hipGetLastError());
   EkfJob job;
-  job.R = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, job.rows = 2 * m - 3, job.pred = c->init_ctr.p + 2, job.dx = dx;
+  job.R = c->Hbig.p + (size_t)b.h_row_off[f] * c->LD, job.rows = 2 * m - 3, job.pred = c->init_ctr.p + 2, job.dx = dx;
   job.keep_flags = true;
   if ((rc = enqueue_ekf(c, job)) != OVGPU_OK) return rc;
   hipLaunchKernelGGL(k_landmark_update, dim3((3 * Lcap + 255) / 256), dim3(256), 0, s, 0, (const int32_t *)(c->init_ctr.p + 1), (const int32_t *)c->lm_repd.p, job.dx,
@@ -552,19 +530,20 @@ static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap
 static bool initf_holds(const ovgpu_ctx *c, int m) { return m >= 2 && m <= INITF_M_MAX && chol_pipe_usable(c, 2 * m - 3); }
 static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, double *dx) {
   hipStream_t s = c->stream;
-  const int m = c->h_offsets[f + 1] - c->h_offsets[f], r = 2 * m - 3;
+  const Batch b = batch_of(c);
+  const int m = b.h_offsets[f + 1] - b.h_offsets[f], r = 2 * m - 3;
   int rc = enqueue_system(c, f, rep);
   if (rc != OVGPU_OK) return rc;
   c->last_update_tform = false;
   InitFusedParams p;
   p.N = Nmax, p.D = c->D, p.LD = c->LD, p.r = r, p.LA = r + Nmax + 1, p.rep = rep, p.f = f, p.sz = lm_dof(rep);
-  p.col_cov = c->col_cov.p, p.init_out = c->init_ws.p, p.stack = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, p.P = c->P.p;
+  p.col_cov = c->col_cov.p, p.init_out = c->init_ws.p, p.stack = c->Hbig.p + (size_t)b.h_row_off[f] * c->LD, p.P = c->P.p;
   p.A = c->Aaug.p, p.Y = c->Yaug.p, p.T = c->init_ws.p + (size_t)3 * c->LD + 16, p.PLL = p.T + (size_t)3 * Nmax;
   p.sigma2 = c->dopt.sigma_pix_sq, p.ctr = c->init_ctr.p, p.dx = dx, p.flags = c->flags.p;
   p.C = c->C, p.K = c->K, p.clone_cov = c->clone_cov.p, p.calib_cov = c->calib_cov.p, p.intr_cov = c->intr_cov.p;
   p.clone_qp = c->clone_qp.p, p.calib_qp = c->calib_qp.p, p.intr = c->intr.p, p.clone_fej = c->clone_fej.p;
   p.tab_clone = c->tab_clone.p, p.tab_cam = c->tab_cam.p, p.tab_cc = c->tab_cc.p;
-  p.p_FinG = c->pG.p, p.p_FinA = c->pA.p, p.meas_cc = c->meas_cc.p, p.anchor_meas = c->anchor.p, p.lm = landmark_store(c), p.feat_slot = c->feat_slot.p;
+  p.p_FinG = b.pG, p.p_FinA = b.pA, p.meas_cc = b.meas_cc, p.anchor_meas = c->anchor.p, p.lm = landmark_store(c), p.feat_slot = c->feat_slot.p;
   const int slot = chol_next_slot(c);
   p.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot;
   c->ctrl_clean &= ~(slot ? CTRL_PROG1 : CTRL_PROG0), c->ctrl_pre &= ~(slot ? CTRL_PROG1 : CTRL_PROG0); // (the step words are k_initf_s's to clear, and dirty afterwards)
@@ -598,7 +577,8 @@ struct InitChain {
 // The chain's set-up for the features [first, F): the 48 / 72 row layout, the workspaces, the triangulation (or the caller's), P padded to the
 // capacity N0 + the candidates' dof (the rows / columns of landmarks that do not exist yet are zero), the device counters, the cleared flags.
 static int begin_init_chain(ovgpu_ctx *c, int32_t feat_rep, int first, bool fused, InitChain &ch) {
-  const int F = c->F;
+  const Batch b = batch_of(c); // (only fields the row layout below leaves alone are read from it)
+  const int F = b.F;
   hipStream_t s = c->stream;
   ch.N0 = ch.Nmax = c->N, ch.L0 = c->L, ch.r_max = 1;
   ch.rep.assign(std::max(F, 1), feat_rep);
@@ -606,7 +586,7 @@ static int begin_init_chain(ovgpu_ctx *c, int32_t feat_rep, int first, bool fuse
   bool new_anchored = false;
   for (int f = first; f < F; f++) {
     ch.Nmax += lm_dof(ch.rep[f]), new_anchored = new_anchored || ch.rep[f] >= OVGPU_REP_ANCHORED_3D;
-    ch.r_max = std::max(ch.r_max, 2 * (c->h_offsets[f + 1] - c->h_offsets[f]) - 3);
+    ch.r_max = std::max(ch.r_max, 2 * (b.h_offsets[f + 1] - b.h_offsets[f]) - 3);
   }
   // the per-feature kernel needs the anchor blocks in its row store for an anchored representation
   const int want_stride = (new_anchored || c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D || lm_any_anchored(c)) ? 72 : 48;
@@ -625,10 +605,7 @@ static int begin_init_chain(ovgpu_ctx *c, int32_t feat_rep, int first, bool fuse
   HIPCHK(c->init_ctr.reserve(8));
   HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
   HIPCHK(c->dx_seq.reserve((size_t)std::max(F, 1) * Nmax));
-  if (fused) {
-    HIPCHK(c->chol_prog.reserve(CHOL_PROG_STRIDE + 16));
-    HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
-  }
+  if (fused) HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
   HIPCHK(c->Mt.reserve(rD * Nmax));
   HIPCHK(c->Aaug.reserve(rD * (rD + Nmax + 1)));
   HIPCHK(c->Yaug.reserve(rD * (rD + Nmax + 1)));
@@ -638,7 +615,7 @@ static int begin_init_chain(ovgpu_ctx *c, int32_t feat_rep, int first, bool fuse
   if (!c->given_tri) {
     if ((rc = enqueue_triangulate(c)) != OVGPU_OK) return rc;
   } else if (F > 0) {
-    HIPCHK(hipMemcpyAsync(c->status.p, c->given_status.p, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.status, c->given_status.p, sizeof(int32_t) * F, hipMemcpyDeviceToDevice, s));
   }
   if ((rc = cov_resize(c, ch.N0, ch.Nmax, ch.N0)) != OVGPU_OK) return rc; // (the entry's P waits in Ppad)
   const int32_t ctr0[8] = {ch.N0, ch.L0, 0, 0, 0, 0, 0, 0};
@@ -668,11 +645,12 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   InitChain ch;
   int rc = begin_init_chain(c, feat_rep, 0, fused, ch);
   if (rc != OVGPU_OK) return rc;
-  const int F = c->F, N0 = ch.N0, L0 = ch.L0, Nmax = ch.Nmax;
+  const Batch b = batch_of(c); // (as the chain's set-up laid it out)
+  const int F = b.F, N0 = ch.N0, L0 = ch.L0, Nmax = ch.Nmax;
   hipStream_t s = c->stream;
   // ---- 4. one feature after the other (UpdaterSLAM.cpp:147-239)
   for (int f = 0; f < F && rc == OVGPU_OK; f++) {
-    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+    const int m = b.h_offsets[f + 1] - b.h_offsets[f];
     if (m < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
     if (fused && c->init_fused_on && initf_holds(c, m)) {
       rc = enqueue_init_feature_fused(c, f, ch.rep[f], Nmax, c->dx_seq.p + (size_t)f * Nmax);
@@ -712,9 +690,9 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   int32_t flags[4] = {0, 0, 0, 0};
   HIPCHK(hipMemcpyAsync(flags, c->flags.p, sizeof(flags), hipMemcpyDeviceToHost, s));
   std::vector<int32_t> tri_am(std::max(F, 1), -1);
-  std::vector<uint16_t> tri_cc(std::max(c->M, 1), 0);
+  std::vector<uint16_t> tri_cc(std::max(b.M, 1), 0);
   if (F > 0 && (!c->given_tri || c->given_has_anchor)) HIPCHK(hipMemcpyAsync(tri_am.data(), c->anchor.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
-  if (c->M > 0) HIPCHK(hipMemcpyAsync(tri_cc.data(), c->meas_cc.p, sizeof(uint16_t) * c->M, hipMemcpyDeviceToHost, s));
+  if (b.M > 0) HIPCHK(hipMemcpyAsync(tri_cc.data(), b.meas_cc, sizeof(uint16_t) * b.M, hipMemcpyDeviceToHost, s));
   c->slam_rows = false;
   rc = read_feature_outputs(c, feat_status, chi2, chi2_thresh, nullptr, stats); // synchronises
   if (rc != OVGPU_OK) return rc;
@@ -783,12 +761,13 @@ static int init_sys_layout(ovgpu_ctx *c, int32_t feat_rep, int first, InitSysLay
   if (!c->have_state || c->poses_only) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_state was never called");
   if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "ovgpu_set_features was never called (or the state changed since)");
   if (feat_rep < OVGPU_REP_GLOBAL_3D || feat_rep > OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) return set_err(OVGPU_ERR_INVALID, "unknown landmark representation");
-  const int F = c->F, M = c->M;
+  const Batch b = batch_of(c);
+  const int F = b.F, M = b.M;
   if (first < 0 || first > F) return set_err(OVGPU_ERR_INVALID, "first_feature out of range");
   if (c->cols_over) return set_err(OVGPU_ERR_CAPACITY, c->cols_over_msg);
   HIPCHK(hipSetDevice(c->device));
   std::vector<uint16_t> cc(std::max(M, 1));
-  if (M > 0) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, c->stream));
+  if (M > 0) HIPCHK(hipMemcpyAsync(cc.data(), b.meas_cc, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(upload_sync(c, c->stream));
   std::vector<int32_t> col_of(std::max(c->N, 1), -1);
   for (int j = 0; j < c->D; j++) col_of[c->h_col_cov[j]] = j;
@@ -799,12 +778,12 @@ static int init_sys_layout(ovgpu_ctx *c, int32_t feat_rep, int first, InitSysLay
   std::vector<char> seen_clone(c->C), seen_cam(c->K);
   for (int f = 0; f < F; f++) {
     lo.var_off[f] = lo.tot.n_vars, lo.hx_off[f] = lo.tot.n_hx, lo.hf_off[f] = lo.tot.n_hf, lo.res_off[f] = lo.tot.n_res, lo.col_off[f] = (int64_t)lo.cols.size();
-    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+    const int m = b.h_offsets[f + 1] - b.h_offsets[f];
     if (f < first || m < 2) continue;
     const bool single = feat_rep_of(c, feat_rep, f) == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE;
     vars.clear();
     std::fill(seen_clone.begin(), seen_clone.end(), 0), std::fill(seen_cam.begin(), seen_cam.end(), 0);
-    for (int i = c->h_offsets[f]; i < c->h_offsets[f + 1]; i++) {
+    for (int i = b.h_offsets[f]; i < b.h_offsets[f + 1]; i++) {
       const int cam = anchor_cam(cc[i]), cl = anchor_clone(cc[i]);
       if (!seen_clone[cl]) seen_clone[cl] = 1, vars.push_back({c->h_clone_cov[cl], 6});
       if (!seen_cam[cam]) {
@@ -843,7 +822,7 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
   InitSysLayout lo;
   int rc = init_sys_layout(c, feat_rep, first_feature, lo);
   if (rc != OVGPU_OK) return rc;
-  const int F = c->F, first = first_feature;
+  const int F = batch_of(c).F, first = first_feature;
   if (F > 0 && !sys) return set_err(OVGPU_ERR_INVALID, "null sys");
   if ((lo.tot.n_vars > 0 && (!var_id || !var_size)) || (lo.tot.n_hx > 0 && !H_x) || (lo.tot.n_hf > 0 && (!H_f || !res)))
     return set_err(OVGPU_ERR_INVALID, "null output arrays");
@@ -862,14 +841,15 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
   InitChain ch;
   ch.save = c->isx_save.p, ch.up_src = &lo.cols, ch.up_dst = c->isx_cols.p;
   if ((rc = begin_init_chain(c, feat_rep, first, false, ch)) != OVGPU_OK) return rc;
+  const Batch b = batch_of(c); // (as the chain's set-up laid it out; the device arrays and offsets are the same under the layout put back below)
   double *a_hx = c->isx_arena.p, *a_hf = a_hx + lo.tot.n_hx, *a_res = a_hf + lo.tot.n_hf;
   c->init_export = true;
   for (int f = first; f < F && rc == OVGPU_OK; f++) {
     if (lo.rows[f] == 0) continue; // fewer than two measurements: OVGPU_FEAT_TOO_FEW_MEAS
     InitExportParams ep;
     ep.LD = c->LD, ep.D = c->D, ep.h = lo.h[f], ep.rows = lo.rows[f], ep.single = ch.rep[f] == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE, ep.f = f;
-    ep.init_out = c->init_ws.p, ep.stack = c->Hbig.p + (size_t)c->h_row_off[f] * c->LD, ep.cols = c->isx_cols.p + lo.col_off[f];
-    ep.feat_sigma = c->have_feat_sigma ? c->feat_sigma.p : nullptr, ep.sigma = std::sqrt(c->dopt.sigma_pix_sq);
+    ep.init_out = c->init_ws.p, ep.stack = c->Hbig.p + (size_t)b.h_row_off[f] * c->LD, ep.cols = c->isx_cols.p + lo.col_off[f];
+    ep.feat_sigma = b.have_sigma ? b.feat_sigma : nullptr, ep.sigma = std::sqrt(c->dopt.sigma_pix_sq);
     ep.Hx = a_hx + lo.hx_off[f], ep.Hf = a_hf + lo.hf_off[f], ep.res = a_res + lo.res_off[f];
     rc = enqueue_init_feature(c, f, ch.rep[f], ch.Nmax, ch.L0 + F, ch.init_lds, c->dx_seq.p, &ep);
   }
@@ -877,17 +857,17 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
   // ---- results: one gather, one synchronisation
   std::vector<int32_t> st(std::max(F, 1), OVGPU_FEAT_TOO_FEW_MEAS), am(std::max(F, 1), -1), slot(std::max(F, 1), -1);
   std::vector<double> x2(std::max(F, 1)), thr(std::max(F, 1)), pA(3 * (size_t)std::max(F, 1)), pG(3 * (size_t)std::max(F, 1));
-  std::vector<uint16_t> cc(std::max(c->M, 1), 0);
+  std::vector<uint16_t> cc(std::max(b.M, 1), 0);
   int32_t flags[4] = {0, 0, 0, 0};
   if (rc == OVGPU_OK && F > 0) {
-    HIPCHK(hipMemcpyAsync(st.data(), c->status.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(x2.data(), c->chi2.p, sizeof(double) * F, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(thr.data(), c->chi2_thr.p, sizeof(double) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(st.data(), b.status, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(x2.data(), b.chi2, sizeof(double) * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(thr.data(), b.chi2_thr, sizeof(double) * F, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(slot.data(), c->feat_slot.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(pA.data(), c->pA.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(pG.data(), c->pG.p, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pA.data(), b.pA, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pG.data(), b.pG, sizeof(double) * 3 * F, hipMemcpyDeviceToHost, s));
     if (!c->given_tri || c->given_has_anchor) HIPCHK(hipMemcpyAsync(am.data(), c->anchor.p, sizeof(int32_t) * F, hipMemcpyDeviceToHost, s));
-    if (c->M > 0) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * c->M, hipMemcpyDeviceToHost, s));
+    if (b.M > 0) HIPCHK(hipMemcpyAsync(cc.data(), b.meas_cc, sizeof(uint16_t) * b.M, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(flags, c->flags.p, sizeof(flags), hipMemcpyDeviceToHost, s));
     if (lo.tot.n_hx > 0) HIPCHK(hipMemcpyAsync(H_x, a_hx, sizeof(double) * lo.tot.n_hx, hipMemcpyDeviceToHost, s));
     if (lo.tot.n_hf > 0) HIPCHK(hipMemcpyAsync(H_f, a_hf, sizeof(double) * lo.tot.n_hf, hipMemcpyDeviceToHost, s));
@@ -928,7 +908,7 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
       o.status = -1;
       continue;
     }
-    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
+    const int m = b.h_offsets[f + 1] - b.h_offsets[f];
     o.status = m < 2 ? OVGPU_FEAT_TOO_FEW_MEAS : st[f];
     const bool has_system = lo.rows[f] > 0 && (o.status == OVGPU_FEAT_USED || o.status == OVGPU_FEAT_CHI2_REJECTED);
     if (has_system) {
@@ -936,7 +916,7 @@ int ovgpu_slam_init_systems(ovgpu_ctx *c, int32_t feat_rep, int32_t first_featur
       o.chi2 = x2[f], o.chi2_thresh = thr[f];
     }
     n_acc += slot[f] >= 0;
-    if (am[f] >= 0 && am[f] < c->M) o.anchor_cam = anchor_cam(cc[am[f]]), o.anchor_clone = anchor_clone(cc[am[f]]);
+    if (am[f] >= 0 && am[f] < b.M) o.anchor_cam = anchor_cam(cc[am[f]]), o.anchor_clone = anchor_clone(cc[am[f]]);
     const double *p = (o.feat_rep >= OVGPU_REP_ANCHORED_3D ? pA.data() : pG.data()) + 3 * f;
     for (int i = 0; i < 3; i++) o.p_seed[i] = p[i];
   }

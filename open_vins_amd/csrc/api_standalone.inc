@@ -108,7 +108,7 @@ int ovgpu_msckf_local_gram(ovgpu_ctx *c, int32_t *feat_status, double *chi2, dou
   if (rc != OVGPU_OK) return rc;
   const size_t n = (size_t)256 * ((c->LD + 15) / 16) * ((c->LD + 15) / 16);
   double *dst = static_cast<double *>(gram_dev);
-  if (c->F > 0) {
+  if (batch_of(c).F > 0) {
     HIPCHK(hipMemcpyAsync(dst, c->gram_G.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(k_gram_count, dim3(1), dim3(1), 0, c->stream, dst + n, c->rows_used.p);
     HIPCHK(hipGetLastError());

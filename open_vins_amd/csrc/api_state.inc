@@ -37,12 +37,13 @@ int ovgpu_create(const ovgpu_options *opts, int device, ovgpu_ctx **out) {
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   HIPCHK(c->ctrl.reserve(CTRL_INTS));
   HIPCHK(hipMemset(c->ctrl.p, 0, CTRL_INTS * sizeof(int32_t)));
-  c->flags.p = c->ctrl.p, c->flags.cap = 4;               // views: never released on their own
+  // the views into it, set here and nowhere else (DevView: nothing to reserve or release; they go with ctrl)
+  c->flags.p = c->ctrl.p; // 4 words
   // words 24 .. 26 sit BETWEEN the two sets of Cholesky step flags (8 .. 23, 32 .. 47): together with either set they are one contiguous range
   // (enqueue_speculative_prior zeroes them and the set the update's own factorisation will use ahead of time, in one launch)
-  c->rows_used.p = c->ctrl.p + 24, c->rows_used.cap = 2; // [0] rows of accepted features, [1] features passed by the gate's residual bound
-  c->feat_counter.p = c->ctrl.p + 26, c->feat_counter.cap = 1;
-  c->chol_prog.p = c->ctrl.p + 8, c->chol_prog.cap = 40; // set 0 at +0, set 1 at +24 (CHOL_PROG_STRIDE)
+  c->rows_used.p = c->ctrl.p + 24; // [0] rows of accepted features, [1] features passed by the gate's residual bound
+  c->feat_counter.p = c->ctrl.p + 26;
+  c->chol_prog.p = c->ctrl.p + 8; // 40 words: set 0 at +0, set 1 at +24 (CHOL_PROG_STRIDE)
   c->ctrl_pre = 0;
   DevOptions &d = c->dopt;
   d.chi2_multipler = opts->chi2_multipler;
@@ -129,7 +130,6 @@ void ovgpu_destroy(ovgpu_ctx *c) {
   c->trk_count.release(), c->trk_cam.release(), c->trk_slot_in.release(), c->trk_cam_in.release(), c->trk_sel.release(), c->trk_nvalid.release(), c->trk_flag.release();
   c->trk_time.release(), c->trk_clone_times.release(), c->trk_aux.release(), c->trk_uv.release(), c->trk_uvn.release(), c->trk_uv_in.release(), c->trk_uvn_in.release();
   c->dx.release(), c->given_status.release();
-  c->flags.p = nullptr, c->rows_used.p = nullptr, c->feat_counter.p = nullptr, c->chol_prog.p = nullptr; // views into ctrl
   c->ctrl.release();
   c->gram_part.release(), c->gram_G.release(), c->gram_rho.release(), c->Yaug2.release(), c->gram_dropped.release(), c->Lw.release(), c->dbg_cycles.release();
   c->chol_uinv.release();
@@ -410,7 +410,6 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
   HIPCHK(c->Aaug.reserve((size_t)D * (D + N + 1)));
   HIPCHK(c->Yaug.reserve((size_t)D * (D + N + 1)));
   HIPCHK(c->dx.reserve(N));
-  HIPCHK(c->flags.reserve(4));
 
   hipStream_t s = c->stream;
   // calibration ids the kernels see: -1 when that calibration is not being estimated
@@ -474,18 +473,19 @@ int ovgpu_reset_state(ovgpu_ctx *c) {
   return OVGPU_OK;
 }
 
-// Sizes the stacked-system buffer and the TSQR leaf layout for c->rows_total rows of c->LD columns:
+// Sizes the stacked-system buffer and the TSQR leaf layout for the batch's rows_total rows of c->LD columns:
 // one leaf node per CU when there are enough rows, every node a whole number of 128-row appends.
 static int configure_tsqr(ovgpu_ctx *c) {
   const int D = c->D, LD = c->LD;
-  HIPCHK(c->Hbig.reserve((size_t)std::max<int64_t>(c->rows_total, 1) * LD));
+  const int64_t rows_total = batch_of(c).rows_total;
+  HIPCHK(c->Hbig.reserve((size_t)std::max<int64_t>(rows_total, 1) * LD));
   const int64_t blk = 4 * QR_LEAF_Q;
   const int64_t target = std::max<int64_t>(1, c->tsqr_workers > 0 ? c->tsqr_workers : c->num_cu);
-  int64_t rpn = (c->rows_total + target - 1) / target;
+  int64_t rpn = (rows_total + target - 1) / target;
   rpn = std::max<int64_t>(blk, ((rpn + blk - 1) / blk) * blk);
-  if (rpn < 2 * blk && c->rows_total > 2 * blk) rpn = 2 * blk; // a leaf shorter than D rows compresses nothing
+  if (rpn < 2 * blk && rows_total > 2 * blk) rpn = 2 * blk; // a leaf shorter than D rows compresses nothing
   c->rows_per_node = rpn;
-  c->W = (int)std::max<int64_t>(1, (c->rows_total + rpn - 1) / rpn);
+  c->W = (int)std::max<int64_t>(1, (rows_total + rpn - 1) / rpn);
   HIPCHK(c->Rws.reserve((size_t)std::max(c->W, 16) * D * LD));
   return OVGPU_OK;
 }
@@ -527,17 +527,18 @@ static bool featy_stack_f32(const ovgpu_ctx *c, int f_one) {
 // timing loop over a resident batch pays what a filter that hands over a new batch per frame pays inside ovgpu_set_features (bench.py's
 // headline since round 6).
 static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
-  const int F = c->F;
-  const bool fast = c->feat_variant != 0 && c->M > 0, lists = fast && c->featy_ok;
+  const Batch b = batch_of(c);
+  const int F = b.F;
+  const bool fast = c->feat_variant != 0 && b.M > 0, lists = fast && c->featy_ok;
   if (F > 0 && (anchors || fast)) {
-    const int m_max = feat::batch_layout_m_pad(std::max(c->m_max, 1));
+    const int m_max = feat::batch_layout_m_pad(std::max(b.m_max, 1));
     // features per workgroup (k_featy.h: why eight); fewer where long tracks' tables would not fit 48 KB of LDS
     const size_t lds_one = feat::batch_layout_lds_ints(m_max) * sizeof(int32_t);
     int fpw_want = 1; // the fewest features per workgroup that keep the launch at 250 workgroups or fewer (measured: 800 features 0.4433 ms at four, 0.4477 at eight)
     while (fpw_want < std::min(c->layout_fpw, (int)feat::BL_FPW) && (F + fpw_want - 1) / fpw_want > 250) fpw_want *= 2;
     const int fpw = fast ? std::max(1, std::min<int>(fpw_want, (int)((48 * 1024) / lds_one))) : 1;
     const size_t lds = fast ? (size_t)fpw * lds_one : 0;
-    hipLaunchKernelGGL(feat::k_batch_layout, dim3((F + fpw - 1) / fpw), dim3(fast ? feat::BL_NTH * fpw : 64), lds, c->stream, F, m_max, c->D, (const int32_t *)c->meas_offsets.p, (const uint16_t *)c->meas_cc.p,
+    hipLaunchKernelGGL(feat::k_batch_layout, dim3((F + fpw - 1) / fpw), dim3(fast ? feat::BL_NTH * fpw : 64), lds, c->stream, F, m_max, c->D, (const int32_t *)b.meas_offsets, (const uint16_t *)b.meas_cc,
                        (const int32_t *)c->clone_col.p, (const int32_t *)c->calib_col.p, (const int32_t *)c->intr_col.p, anchors ? c->anchor_pre.p : (int32_t *)nullptr,
                        fast ? c->fs_meas_feat.p : (int32_t *)nullptr, fast ? c->fs_pos.p : (int32_t *)nullptr, lists ? c->fs_inst.p : (int32_t *)nullptr, c->feat_nt_max, cb, c->C, c->K,
                        (const uint8_t *)c->cls_of_clone.p, (const int32_t *)c->raw_featbase.p, (fast && c->raw_tables_ok) ? c->raw_dst.p : (int32_t *)nullptr);
@@ -550,26 +551,35 @@ static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
 static int enqueue_instance_lists(ovgpu_ctx *c, int cb) { return enqueue_batch_layout(c, false, cb); }
 static int enqueue_batch_tables(ovgpu_ctx *c, bool anchors) { return enqueue_batch_layout(c, anchors, c->featy_ok ? featy_block_cols(c, featy_stack_f32(c, -1)) : feat::FY_CB); }
 
-// Row layout of the stacked system for the uploaded tracks, the per-feature kernel's LDS carve and the TSQR leaf layout.
-//   MSCKF / delayed init: 2m - 3 rows per feature after the nullspace projection (UpdaterHelper.cpp:449-450);
-//   SLAM update: all 2m rows (UpdaterSLAM.cpp:381-383).
-// host_only (ovgpu_slam_update_chunked): sizes, carve and workspaces alone — the row offsets are on the device already and the batch's tables stay
-static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bool host_only = false) {
-  const int F = c->F;
+// The rows a feature of m measurements stacks.  MSCKF / delayed init: 2m - 3 after the nullspace projection (UpdaterHelper.cpp:449-450); SLAM
+// update: all 2m (UpdaterSLAM.cpp:381-383) less the `proj` rows a single-depth landmark's bearing takes (UpdaterSLAM.cpp:371-379: 3 - dof).
+static int feature_rows(bool slam_rows, int m, int proj) { return slam_rows ? std::max(2 * m - proj, 0) : (m >= 2 ? 2 * m - 3 : 0); }
+// ... of every feature of b, as offsets: out[0 .. b.F].  A batch over landmarks of both sizes is laid out per feature once its landmarks are
+// named (slam_prepare, a chunk); until then every feature gets the 2m rows of a 3-dof landmark
+static void row_offsets_of(const ovgpu_ctx *c, const Batch &b, bool slam_rows, int64_t *out) {
   const int udof = lm_uniform_dof(c);
-  std::vector<int64_t> row_off(F + 1, 0);
-  for (int f = 0; f < F; f++) {
-    const int m = c->h_offsets[f + 1] - c->h_offsets[f];
-    // the bearing of a single-depth landmark is projected out (UpdaterSLAM.cpp:371-379).  A batch over landmarks of both sizes is laid out
-    // per feature once its landmarks are named (slam_prepare); until then every feature gets the 2m rows of a 3-dof landmark
+  out[0] = 0;
+  for (int f = 0; f < b.F; f++) {
     int proj = udof == 1 ? 2 : 0;
-    if (udof == 0 && (int)c->h_feat_lm.size() == F) proj = 3 - lm_dof(c->h_lm_rep[c->h_feat_lm[f]]);
-    row_off[f + 1] = row_off[f] + (slam_rows ? (2 * m > proj ? 2 * m - proj : 0) : (m >= 2 ? 2 * m - 3 : 0));
+    if (udof == 0 && (int)b.h_feat_lm.size() == b.F) proj = 3 - lm_dof(c->h_lm_rep[b.h_feat_lm[f]]);
+    out[f + 1] = out[f] + feature_rows(slam_rows, b.h_offsets[f + 1] - b.h_offsets[f], proj);
   }
-  c->rows_total = row_off[F];
-  c->h_row_off = row_off;
-  c->slam_rows = slam_rows;
-  const int m_max = c->m_max;
+}
+// The track order: feature indices by descending length, equal lengths in batch order — a counting sort (round 6; a comparison sort of 2000
+// tracks was ~30 us of every frame).  offsets[0 .. F], order[0 .. F)
+static void track_order(const int32_t *offsets, int F, int m_max, int32_t *order) {
+  std::vector<int32_t> start(m_max + 2, 0);
+  for (int f = 0; f < F; f++) start[m_max - (offsets[f + 1] - offsets[f]) + 1]++;
+  for (int b = 0; b <= m_max; b++) start[b + 1] += start[b];
+  for (int f = 0; f < F; f++) order[start[m_max - (offsets[f + 1] - offsets[f])]++] = f;
+}
+
+// Sizes the per-feature stage for the batch in force and its row layout: the per-feature kernel's LDS carve, grids, workspaces and variant, the
+// fused kernels' slot records, the stack and the TSQR leaf layout.  Reads the batch, writes none of it.
+static int size_feature_stage(ovgpu_ctx *c) {
+  const Batch b = batch_of(c);
+  const int F = b.F, m_max = b.m_max;
+  const bool slam_rows = c->slam_rows;
   // ---- per-feature kernel: LDS carve and (for long tracks) a global gate workspace
   size_t fixed = sys_lds_fixed_bytes(std::max(m_max, 1), c->row_stride, c->D);
   c->sys_rows_global = false;
@@ -642,7 +652,7 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bo
   }
   c->lm_fast_ok = c->L > 0 && c->feat_variant != 0 && c->featy_ok;
   if (c->feat_variant) { // row store of the fast path
-    const int M = std::max(c->M, 1);
+    const int M = std::max(b.M, 1);
     HIPCHK(c->fs_tq.reserve((size_t)std::max(F, 1) * 8));
     HIPCHK(c->fs_inst.reserve((size_t)std::max(F, 1) * std::max(c->feat_nt_max, 1) * feat::FY_ISTR));
     HIPCHK(c->fs_rows.reserve((size_t)M * c->row_stride));
@@ -653,20 +663,32 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bo
     // the fused kernels' schedule: one record per slot, slots in the order of c->sys_order
     std::vector<int32_t> slots((size_t)8 * std::max(F, 1), 0);
     for (int sidx = 0; sidx < F; sidx++) {
-      const int f = c->h_order[sidx];
+      const int f = b.h_order[sidx];
+      const HostSpan<int64_t> &row_off = b.h_row_off;
       int32_t *r = &slots[(size_t)8 * sidx];
-      r[0] = f, r[1] = c->h_offsets[f], r[2] = c->h_offsets[f + 1] - c->h_offsets[f], r[3] = (int32_t)(row_off[f + 1] - row_off[f]);
+      r[0] = f, r[1] = b.h_offsets[f], r[2] = b.h_offsets[f + 1] - b.h_offsets[f], r[3] = (int32_t)(row_off[f + 1] - row_off[f]);
       r[4] = (int32_t)(uint32_t)((uint64_t)row_off[f] & 0xffffffffu), r[5] = (int32_t)(uint32_t)((uint64_t)row_off[f] >> 32);
     }
     HIPCHK(c->fs_slots.reserve(slots.size()));
     HIPCHK(upload_deferred(c, c->fs_slots.p, slots.data(), sizeof(int32_t) * slots.size()));
   }
   // ---- stacked system and TSQR accumulators
-  const int rct = configure_tsqr(c);
-  if (rct != OVGPU_OK) return rct;
-  if (host_only) return OVGPU_OK;
+  return configure_tsqr(c);
+}
+
+// Row layout of the resident batch (the whole one: this writes its owners): the row offsets by the rule above, the stage sized for them, the
+// offsets and the batch's integer tables on their way to the device.
+static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false) {
+  if (c->view) return set_err(OVGPU_ERR_INVALID, "internal: the resident batch cannot be laid out while a part of it is in force");
+  const int F = c->F;
+  c->h_row_off.resize(F + 1);
+  row_offsets_of(c, batch_of(c), slam_rows, c->h_row_off.data());
+  c->rows_total = c->h_row_off[F];
+  c->slam_rows = slam_rows;
+  const int rcs = size_feature_stage(c);
+  if (rcs != OVGPU_OK) return rcs;
   HIPCHK(c->row_off.reserve(F + 1));
-  HIPCHK(upload_deferred(c, c->row_off.p, row_off.data(), sizeof(int64_t) * (F + 1)));
+  HIPCHK(upload_deferred(c, c->row_off.p, c->h_row_off.data(), sizeof(int64_t) * (F + 1)));
   // everything ovgpu_set_features packed into the arena (offsets, packed codes, pixel coordinates, the slot records and row offsets above)
   // leaves by ONE scatter launch; behind it the batch's integer tables (one launch; `anchors`: a new batch, end_feature_batch)
   HIPCHK(upload_fence(c, c->stream));
@@ -677,13 +699,14 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false, bo
 // in every region, the stack's size and the workgroups of k_gram_regions (dealt by rows x tiles of the region's triangle).
 static int raw_stack_layout(ovgpu_ctx *c, const uint16_t *cc) {
   c->raw_tables_ok = false;
-  const int F = c->F, M = c->M, n = c->raw_ncls;
+  const Batch b = batch_of(c);
+  const int F = b.F, M = b.M, n = c->raw_ncls;
   if (!c->raw_enable || !c->raw_cols_ok || F <= 0 || M <= 0 || n <= 0) return OVGPU_OK;
   std::vector<int32_t> fb((size_t)F * RAW_MAXCLS, 0);
   int64_t run[RAW_MAXCLS + 1] = {0};
   for (int f = 0; f < F; f++) {
     int cnt[RAW_MAXCLS] = {0};
-    for (int i = c->h_offsets[f]; i < c->h_offsets[f + 1]; i++) cnt[c->h_cls_of_clone[anchor_clone(cc[i])]]++;
+    for (int i = b.h_offsets[f]; i < b.h_offsets[f + 1]; i++) cnt[c->h_cls_of_clone[anchor_clone(cc[i])]]++;
     int below = 0;
     for (int k = 0; k < n; k++) {
       fb[(size_t)f * RAW_MAXCLS + k] = (int32_t)(run[k] - 2 * below);
@@ -788,14 +811,8 @@ static int begin_feature_batch(ovgpu_ctx *c, int F, int M, const int32_t *offset
   HIPCHK(c->status.reserve(F));
 
   hipStream_t s = c->stream;
-  // longest track first, equal lengths in batch order: a counting sort (round 6; a comparison sort of 2000 tracks was ~30 us of every frame)
   std::vector<int32_t> order(std::max(F, 1), 0);
-  {
-    std::vector<int32_t> start(m_max + 2, 0);
-    for (int f = 0; f < F; f++) start[m_max - (offsets[f + 1] - offsets[f]) + 1]++;
-    for (int b = 0; b <= m_max; b++) start[b + 1] += start[b];
-    for (int f = 0; f < F; f++) order[start[m_max - (offsets[f + 1] - offsets[f])]++] = f;
-  }
+  track_order(offsets, F, m_max, order.data()); // longest track first
   c->h_order.assign(order.begin(), order.begin() + F);
   HIPCHK(c->sys_order.reserve(std::max(F, 1)));
   (void)s;

@@ -710,8 +710,9 @@ int ovgpu_tracks_to_features(ovgpu_ctx *c, int32_t F, const int64_t *featid, con
   if (rc != OVGPU_OK) return rc;
   HIPCHK(upload_flush(c)); // (the gather below reads the offsets begin_feature_batch packed)
   if (F > 0) {
+    const Batch b = batch_of(c); // (the batch begin_feature_batch made room for)
     hipLaunchKernelGGL(k_tracks_gather, dim3((F + 127) / 128), dim3(128), 0, s, F, K, C, c->trk_sel.p, c->trk_clone_times.p, track_store(c), c->trk_nvalid.p,
-                       (const int32_t *)c->meas_offsets.p, c->uv.p, c->uvn.p, c->meas_cc.p, 1, desc, order_dev);
+                       (const int32_t *)b.meas_offsets, b.uv, b.uvn, b.meas_cc, 1, desc, order_dev);
     HIPCHK(hipGetLastError());
   }
   return end_feature_batch(c);
@@ -721,17 +722,18 @@ int ovgpu_get_features(ovgpu_ctx *c, int32_t *F_out, int32_t *M_out, int32_t *me
   if (!c) return set_err(OVGPU_ERR_INVALID, "null ctx");
   if (!c->have_feats) return set_err(OVGPU_ERR_NO_STATE, "no feature batch is resident");
   HIPCHK(hipSetDevice(c->device));
-  const int F = c->F, M = c->M;
+  const Batch b = batch_of(c);
+  const int F = b.F, M = b.M;
   if (F_out) *F_out = F;
   if (M_out) *M_out = M;
-  if (meas_offsets) std::memcpy(meas_offsets, c->h_offsets.data(), sizeof(int32_t) * (F + 1));
+  if (meas_offsets) std::memcpy(meas_offsets, b.h_offsets.p, sizeof(int32_t) * (F + 1));
   hipStream_t s = c->stream;
   const bool want_cc = clone_idx || cam_idx, want_any = M > 0 && (uv || uvn || want_cc);
   if (!want_any) return OVGPU_OK; // offsets and counts only (the drop-in's length check): host tables, no copy, no synchronisation
   std::vector<uint16_t> cc(want_cc ? std::max(M, 1) : 1);
-  if (uv) HIPCHK(hipMemcpyAsync(uv, c->uv.p, sizeof(float) * 2 * M, hipMemcpyDeviceToHost, s));
-  if (uvn) HIPCHK(hipMemcpyAsync(uvn, c->uvn.p, sizeof(float) * 2 * M, hipMemcpyDeviceToHost, s));
-  if (want_cc) HIPCHK(hipMemcpyAsync(cc.data(), c->meas_cc.p, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, s));
+  if (uv) HIPCHK(hipMemcpyAsync(uv, b.uv, sizeof(float) * 2 * M, hipMemcpyDeviceToHost, s));
+  if (uvn) HIPCHK(hipMemcpyAsync(uvn, b.uvn, sizeof(float) * 2 * M, hipMemcpyDeviceToHost, s));
+  if (want_cc) HIPCHK(hipMemcpyAsync(cc.data(), b.meas_cc, sizeof(uint16_t) * M, hipMemcpyDeviceToHost, s));
   HIPCHK(upload_sync(c, s));
   for (int i = 0; want_cc && i < M; i++) {
     if (clone_idx) clone_idx[i] = anchor_clone(cc[i]);

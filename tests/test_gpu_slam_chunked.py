@@ -378,3 +378,33 @@ def test_a_failed_chunk_restores_the_entry_state_and_runs_the_chain(Updater):
     assert up.debug_option("slam_chunked_fallbacks") == 0
     assert_equal_outputs(out, ref, "the pass itself")
     up.close()
+
+
+# --------------------------------------------------------------------------- a batch that outgrows every buffer a chunk's batch pointed into
+@pytest.mark.parametrize("fail_chunk", [None, 0], ids=["the_pass", "restore_and_chain"])
+def test_a_larger_batch_after_a_chunked_call(Updater, fail_chunk):
+    """The tracks of landmarks 0..5 in chunks of 2 / 0 / 4 through the chunked entry (fail_chunk = 0: through its restore-and-chain path) and through
+    the chain, then all twelve tracks with per-feature options on both contexts: F and M above anything either context has held, so every batch
+    array and per-feature option buffer reallocates behind the chunks' batches.  Equality throughout; both contexts close."""
+    opts = capi.default_options(chi2_multipler=1.0)
+    p = problem(12, 3)
+    q6, q12 = batch_of(p, np.arange(6)), batch_of(p, np.arange(12))
+    assert q12.F > q6.F and q12.M > q6.M
+    first = [0, 2, 2, 6]
+    out, up = chunked(Updater, opts, q6, first, keep=True, fail_chunk=fail_chunk)
+    ref, up2 = chain(Updater, opts, q6, first, keep=True)
+    assert up.debug_option("slam_chunked_fallbacks") == (0 if fail_chunk is None else 1)
+    assert_equal_outputs(out, ref, "the first batch")
+    assert sum(s["n_used"] for s in out["stats"] if s) >= 3
+    sigma, mult = np.linspace(0.8, 2.0, q12.F), np.linspace(0.5, 3.0, q12.F)
+    up2.set_active_landmarks(None)  # (the chunked call left "all" in force itself)
+    nxt = []
+    for u in (up, up2):
+        u.set_features(q12)
+        u.set_feature_options(sigma_pix=sigma, chi2_multipler=mult)
+        o = u.slam_update(q12.lm_index)
+        o.update(u.get_state(P=False))
+        nxt.append(o)
+    assert_equal_outputs(nxt[0], nxt[1], "the larger batch", keys=("feat_status", "chi2", "chi2_thresh", "dx", "P", "landmarks", "clone_q_p", "calib_q_p", "intrinsics"))
+    assert nxt[0]["stats"]["n_used"] >= 6
+    up.close(), up2.close()

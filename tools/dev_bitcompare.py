@@ -2,7 +2,8 @@
 kernel of the headline shape (feat::k_feat_y<4, 11, 2>, both stack precisions) and the other per-feature kernels through the library
 in the tree and stores every output; `compare <a.npz> <b.npz>` compares two such files bit for bit.  Used when a build changes
 nothing but instruction ORDER (a scheduler strategy, ovgpu_featy_tu.hip): no tolerance applies, and no oracle time is spent
-(tools/gpu_bitcompare.sh swaps the library files on one box)."""
+(tools/gpu_bitcompare.sh swaps the library files on one box).  `dump` also runs the entries that read the resident feature batch on
+small seeded landmark states (batch_scenarios below): used when a change is meant to touch host code only."""
 import sys
 
 import numpy as np
@@ -31,6 +32,96 @@ def shapes():
     # the 8-wavefront and block-row shapes (translation unit 1: unchanged code, here as the control)
     yield "cfg4_long_tracks", dict(cfg=4, F=300), {}
     yield "cfg5_block_rows", dict(cfg=5, F=60), {}
+
+
+STAT_INTS = ("n_used", "n_rows", "D", "n_rows_comp", "status", "n_gate_bound")  # (the ms_* fields are timings)
+REPS6 = (0, 1, 2, 3, 4, 5)  # capi.REP_GLOBAL_3D .. capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE
+CAND = ("meas_offsets", "uv", "uvn", "clone_idx", "cam_idx", "p_FinG_true")
+
+
+def put(out, prefix, res):
+    """every array and integer of a result dictionary (lists of dictionaries entry by entry); timings stay out"""
+    for k, v in res.items():
+        if k == "stats":
+            for i, st in enumerate(v if isinstance(v, list) else [v]):
+                out[f"{prefix}.stats{i}"] = np.array([st[j] for j in STAT_INTS])
+        elif isinstance(v, np.ndarray):
+            out[f"{prefix}.{k}"] = np.ascontiguousarray(v)
+        elif isinstance(v, (int, float, np.integer, np.floating)):
+            out[f"{prefix}.{k}"] = np.array([v])
+        elif isinstance(v, list) and all(isinstance(t, tuple) for t in v):
+            out[f"{prefix}.{k}"] = np.array(v, dtype=np.int64).reshape(-1)
+
+
+def batch_scenarios(out):
+    """The entries that read the resident batch, on seeded states of 30 clones and two cameras."""
+    import copy
+    from open_vins_amd import capi, synth
+    from open_vins_amd.updater import UpdaterMSCKF
+    opts = capi.default_options(chi2_multipler=1.0)
+    n0 = len(out)
+    # ovgpu_slam_update: twelve landmarks of all six representations
+    p12 = synth.make_slam_problem(2, L=12, lm_rep=np.array(REPS6 * 2, np.int32), seed=3)
+    up = UpdaterMSCKF(opts, device=0)
+    up.set_slam_problem(p12)
+    res = up.slam_update()
+    res.update(up.get_state(P=False))
+    put(out, "slam_update", res)
+    up.close()
+    # ovgpu_slam_update_chunked: three chunks, the middle one empty, options that differ between the chunks; then through the restore-and-chain path
+    F = p12.F
+    sigma, mult = np.where(np.arange(F) < 5, 1.0, 2.5), np.where(np.arange(F) < 5, 1.0, 0.25)
+    for tag, fail in (("chunked", None), ("chunked_restore_and_chain", 1)):
+        up = UpdaterMSCKF(opts, device=0)
+        up.set_slam_problem(p12)
+        up.set_feature_options(sigma_pix=sigma, chi2_multipler=mult)
+        if fail is not None:
+            up.debug_option("slam_chunked_fail_chunk", fail)
+        res = up.slam_update_chunked(p12.lm_index, [0, 5, 5, F])
+        res.update(up.get_state(P=False))
+        res["fallbacks"] = up.debug_option("slam_chunked_fallbacks")
+        put(out, tag, res)
+        up.close()
+    # three resident landmarks, eight candidate tracks: both delayed initialisations (each followed by ovgpu_reset_state) and mode A of it
+    cand = copy.copy(synth.make_slam_problem(2, L=3, lm_rep=np.array([0, 5, 2], np.int32), seed=21))
+    tracks = synth.make_problem(2, F=8, seed=22)
+    for k in CAND:
+        setattr(cand, k, getattr(tracks, k))
+
+    def resident():
+        u = UpdaterMSCKF(opts, device=0)
+        u.set_slam_state(cand)
+        u.set_active_landmarks([])
+        u.set_features(cand)
+        return u
+
+    for tag, fused in (("delayed_init", False), ("delayed_init_fused", True)):
+        up = resident()
+        res = up.delayed_init(capi.REP_GLOBAL_3D, fused=fused)
+        res["landmarks"] = up.get_landmarks()["value"]
+        put(out, tag, res)
+        up.reset_state()
+        put(out, tag + ".after_reset", up.get_state(P=True))
+        up.close()
+    for first in (0, 2):
+        up = resident()
+        for f, d in enumerate(up.init_systems(capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, first_feature=first)):
+            put(out, f"init_systems_from_{first}.f{f}", {k: v for k, v in d.items() if v is not None})
+        put(out, f"init_systems_from_{first}.state", up.get_state(P=True))
+        up.close()
+    # ovgpu_msckf_update_lm: an MSCKF batch over resident landmarks that have no column
+    lm = copy.copy(synth.make_slam_problem(2, L=8, lm_rep=np.array(REPS6 + (0, 5), np.int32), seed=3))
+    tracks = synth.make_problem(2, F=60, seed=4)
+    for k in CAND:
+        setattr(lm, k, getattr(tracks, k))
+    up = UpdaterMSCKF(opts, device=0)
+    up.set_slam_state(lm)
+    up.set_active_landmarks([])
+    up.set_features(lm)
+    put(out, "msckf_update_lm", up.update_lm())
+    up.close()
+    # (ovgpu_msckf_compress: the `.modeA.` arrays of every shape above)
+    print("batch scenarios:", len(out) - n0, "arrays", flush=True)
 
 
 def prepare(path):
@@ -70,6 +161,7 @@ def dump(path, problems=None):
                 out[f"{name}.modeA.{k}"] = np.ascontiguousarray(ca[k])
         up.close()
         print(name, "F", prob.F, "used", res["stats"]["n_used"], "route", out[f"{name}.route"][0], flush=True)
+    batch_scenarios(out)
     np.savez(path, **out)
 
 
@@ -79,7 +171,8 @@ def compare(a, b):
     bad = []
     for k in A.files:
         x, y = A[k], B[k]
-        if x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes():
+        # (numpy.array_equal on the bytes: NaNs — chi2 of a feature that never reached its gate — compare by bit pattern)
+        if x.shape != y.shape or x.dtype != y.dtype or not np.array_equal(np.frombuffer(x.tobytes(), np.uint8), np.frombuffer(y.tobytes(), np.uint8)):
             d = float(np.max(np.abs(x.astype(np.float64) - y.astype(np.float64)))) if x.shape == y.shape else float("nan")
             bad.append((k, d))
     print(f"{len(A.files)} arrays compared, {len(bad)} differ")
