@@ -89,6 +89,9 @@ extern "C" {
 /*      Likewise ovgpu_slam_delayed_init_fused (the delayed initialisation with  */
 /*      every candidate's step as five launches; ovgpu_slam_delayed_init keeps   */
 /*      its kernels and its bits).                                               */
+/*      Likewise the debug option "slam_fused" (ovgpu_slam_update's per-feature  */
+/*      stage as one fused kernel on the matrix cores; off by default: every     */
+/*      entry enqueues what it enqueued and returns its bits).  No new symbol.   */
 /* ------------------------------------------------------------------------- */
 #define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
@@ -555,7 +558,11 @@ int ovgpu_set_active_landmarks(ovgpu_ctx *ctx, int32_t n, const int32_t *lm_inde
  *   feat_status, chi2, chi2_thresh [F];  dx [N];  P_out [N*N];  lm_out [3*L] updated
  *   landmark values in representation coordinates (Landmark::update, Landmark.h:80-89:
  *   additive).  The landmarks stay resident: a following ovgpu_slam_update /
- *   ovgpu_slam_delayed_init continues from the updated values.                          */
+ *   ovgpu_slam_delayed_init continues from the updated values.
+ * With ovgpu_debug_option "slam_fused" = 1 (default 0) a batch whose landmarks are all 3-dof and whose
+ * longest track holds at most 62 measurements takes its per-feature stage as ONE fused kernel
+ * (S0 = Y Y^T + sigma^2 I from the whitened rows Y = H L the stack holds anyway): the same update to
+ * rounding, this entry and ovgpu_slam_update_chunked alike.                                */
 int ovgpu_slam_update(ovgpu_ctx *ctx, const int32_t *lm_index, int32_t *feat_status,
                       double *chi2, double *chi2_thresh, double *dx, double *P_out,
                       double *lm_out, ovgpu_update_stats *stats);
@@ -1179,7 +1186,17 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             (ovgpu_msckf_compress), the fp32 variant, the Householder route and batches assembled by ovgpu_tracks_to_features
  *                             always stack projected rows.  ("raw_work_const": the region work model's constant; 2: one region, developer experiments)
  *   "last_stack_raw"          (read only) the last pipeline's Gram matrix came from the unprojected stack
- *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one
+ *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one,
+ *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
+ *   "slam_fused"              (default 0) 1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
+ *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every
+ *                             landmark the batch observes is 3-dof, its longest track holds at most 62 measurements, 16 <= D, K C <= 8192,
+ *                             options.no_fast_feature_kernel is 0 and the update takes the whitened (Gram) route; per-feature sigma_pix /
+ *                             chi2_multipler do not disqualify.  Everything else keeps the general kernel: a batch with a single-depth landmark,
+ *                             the Householder route (compress_route = OVGPU_COMPRESS_TSQR, more than 383 columns, the repeat after a failed prior
+ *                             pivot), ovgpu_slam_compress, the delayed initialisation.  Takes effect with the next ovgpu_set_features
+ *   "slam_fused_batches"      counter: batch pipelines that took k_slam_y, once per update — the pipelines of an attempt the library repeats (through the
+ *                             Householder route after a failed prior pivot, with the step-wise Cholesky after a time-out) are not counted; a value >= 0 sets it
  *   "anchored_fast"           (default 1) batches of an anchored feat_rep_msckf take the fused per-feature kernels: 48-double records with
  *                             H_f = A dl at the p_FinG the anchor gives and no anchor blocks, which the nullspace projection annihilates
  *                             (k_featy.h: k_feat_rows_anchored) — the same update to rounding; 0: the general kernel with its 72-double

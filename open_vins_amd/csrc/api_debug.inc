@@ -41,6 +41,12 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "anchored_fast") { // 0: batches of an anchored feat_rep_msckf keep the general kernel (the routing before k_feat_rows_anchored); takes effect with the next ovgpu_set_features
     if (old_value) *old_value = c->anchored_fast ? 1 : 0;
     if (value >= 0) c->anchored_fast = value != 0;
+  } else if (n == "slam_fused") { // 1: SLAM batches of 3-dof landmarks take the fused per-feature kernel k_slam_y on the whitened route (k_slam_y.h); default 0; takes effect with the next ovgpu_set_features
+    if (old_value) *old_value = c->slam_fused ? 1 : 0;
+    if (value >= 0) c->slam_fused = value != 0;
+  } else if (n == "slam_fused_batches") { // reads the count of batch pipelines that took k_slam_y, once per update (the pipelines of a repeated attempt — Householder route, step-wise Cholesky — are not counted); a value >= 0 sets it
+    if (old_value) *old_value = c->slam_fused_batches;
+    if (value >= 0) c->slam_fused_batches = value;
   } else if (n == "gram_blocks_only") {
     if (old_value) *old_value = c->gram_blocks_only ? 1 : 0;
     if (value >= 0) c->gram_blocks_only = value != 0;
@@ -84,7 +90,7 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = t;
   } else if (n == "stack_is_f32") { // read-only: the last pipeline stored the stack as floats and ran k_gram_f32 (options.gram_fp32)
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
-  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big
+  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big, 4 k_slam_y (SLAM batches under "slam_fused")
     if (old_value) *old_value = c->last_feat_kernel;
   } else if (n == "chol_wide") { // 0: beyond 256 columns the Cholesky-with-carry runs as one launch of k_ekf_chol_step per 16 rows instead of two panels of k_chol_fused (k_chol_wide.h)
     if (old_value) *old_value = c->chol_wide ? 1 : 0;

@@ -185,6 +185,20 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
     c->prior_on_side = false;
   }
+  // UpdaterSLAM::update on the whitened route, a batch laid out for it under ovgpu_debug_option "slam_fused": the fused kernel (k_slam_y.h).
+  // Everything else — the Householder repeat and the other routes without L, the delayed initialisation, a batch it does not hold — keeps k_system_t.
+  if (p.slam && p.Lw && f_one < 0 && c->slam_fused_ok) {
+    static bool attr_s = false;
+    if (!attr_s) {
+      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+      attr_s = true;
+    }
+    if (p.m_max > slamy::SLY_MMAX || c->slamy_lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_INVALID, "internal: k_slam_y was selected for a batch it does not hold");
+    c->last_feat_kernel = 4, c->slam_fused_batches++, c->slam_fused_attempt++;
+    hipLaunchKernelGGL(slamy::k_slam_y, dim3(std::max(1, std::min(b.F, c->num_cu))), dim3(64 * slamy::SLY_NW), c->slamy_lds, c->stream, p);
+    HIPCHK(hipGetLastError());
+    return OVGPU_OK;
+  }
   p.rows_ws = c->sys_rows_global ? c->sys_rows_ws.p : nullptr;
   if (c->sys_rows_global) hipLaunchKernelGGL(k_system_t<true>, dim3(grid), dim3(SYS_NT), c->sys_lds_bytes, c->stream, p);
   else hipLaunchKernelGGL(k_system_t<false>, dim3(grid), dim3(SYS_NT), c->sys_lds_bytes, c->stream, p);
@@ -1104,6 +1118,7 @@ template <class Attempt> static int update_with_fallbacks(ovgpu_ctx *c, ovgpu_up
   int rc;
   for (;;) {
     c->chol_timed_out = false;
+    c->slam_fused_attempt = 0;
     rc = attempt();
     if (rc == OVGPU_ERR_NOT_SPD && c->last_update_tform && !c->chol_timed_out && !tried_householder) {
       tried_householder = true, c->force_tsqr = true;
@@ -1112,6 +1127,7 @@ template <class Attempt> static int update_with_fallbacks(ovgpu_ctx *c, ovgpu_up
     } else {
       break;
     }
+    c->slam_fused_batches -= c->slam_fused_attempt; // the attempt does not stand: "slam_fused_batches" counts the pipelines of the attempt that is the update
     if (stats) std::memset(stats, 0, sizeof(*stats));
   }
   c->no_chol_pipe = user_no_pipe;

@@ -387,6 +387,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   if (rc != OVGPU_OK) return rc;
   // ---- every chunk, one after the other on the stream
   const NoStageTiming untimed(c); // (no stage events inside the pass: six marker packets per chunk; ovgpu_update_stats::ms_* stay 0)
+  const int64_t fused0 = c->slam_fused_batches;
   for (int k = 0; k < n && rc == OVGPU_OK; k++) rc = enqueue_chunk(c, pl, k);
   // ---- one read-back
   std::vector<int32_t> flags((size_t)5 * n, 0);
@@ -438,6 +439,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     // behind it ran on a state the chain would not have produced: the entry state comes back and the chunks run as the chain of single calls
     // runs them, one synchronisation and update_with_fallbacks each.  Correct, slower and rare; counted.
     c->chunk_fallbacks++;
+    c->slam_fused_batches = fused0; // (the pass does not stand: the chain below counts its own pipelines)
     if ((rc = state_snapshot(c, c->chk_save.p, true, true)) != OVGPU_OK) return rc;
     if ((rc = launch_build_tables(c)) != OVGPU_OK) return rc;
     HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));

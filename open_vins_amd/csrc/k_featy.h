@@ -445,10 +445,13 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // acc / tij: this wavefront's tiles; panel: 2 x nta_max tiles of LDS (Y, then X); st0: 128 doubles, stE / stF: 256 each; slot: one double.
 // NT = tile rows that hold rows of S0, NTA = tile rows of M.  Returns chi2 in every lane; ends with the workgroup synchronised.
 // ---------------------------------------------------------------------------------------------------
+// RES_ONLY (k_slam_y.h: a landmark that lives in the state has no projection): R = [r | 0 0 0], the statistic is r^T S0^-1 r = -C_00 alone and G = 0 is never solved
+template <bool RES_ONLY = false>
 __device__ __forceinline__ double gate_corner_chi2(const d4 &t, int q, int coff) { // C = rows 4 q .. 4 q + 3, columns coff .. coff + 3 of the tile (q, coff wave-uniform)
   double v = t[0];
 #pragma unroll
   for (int u = 1; u < 4; u++) v = q == u ? t[u] : v;
+  if (RES_ONLY) return -bcast_lane(v, coff);
   const double c00 = bcast_lane(v, coff), c01 = bcast_lane(v, coff + 1), c02 = bcast_lane(v, coff + 2), c03 = bcast_lane(v, coff + 3);
   const double c11 = bcast_lane(v, 16 + coff + 1), c12 = bcast_lane(v, 16 + coff + 2), c13 = bcast_lane(v, 16 + coff + 3);
   const double c22 = bcast_lane(v, 32 + coff + 2), c23 = bcast_lane(v, 32 + coff + 3), c33 = bcast_lane(v, 48 + coff + 3);
@@ -457,7 +460,7 @@ __device__ __forceinline__ double gate_corner_chi2(const d4 &t, int q, int coff)
   const V3 x = colpiv_qr_solve3(Gm, gv);
   return -c00 - dot(gv, x);
 }
-template <int NW, int TPW>
+template <int NW, int TPW, bool RES_ONLY = false>
 __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)[TPW], int NT, int NTA, int n, double *panel, double *panelx, double *st0, double *stE,
                                                 double *stF, double *slot, int lane, int wv) {
   const int g = lane >> 4, cl = lane & 15;
@@ -482,7 +485,7 @@ __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)
         if (NW == 4) __builtin_amdgcn_s_setprio(3);
         const int nblk = min(4, (n4 - 16 * k) >> 2);
         diag_tile_ldl_blk(av, ev, fv, st0, lane, nblk);
-        if (last) *slot = gate_corner_chi2(av, nblk, 4 * nblk);
+        if (last) *slot = gate_corner_chi2<RES_ONLY>(av, nblk, 4 * nblk);
         else {
 #pragma unroll
           for (int q = 0; q < 4; q++) stE[cl * 16 + g + 4 * q] = ev[q], stF[cl * 16 + g + 4 * q] = fv[q]; // accumulator layout -> the A operand's order
@@ -535,7 +538,7 @@ __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)
 #pragma unroll
       for (int s = 0; s < TPW; s++)
         if (s == slot_t) av = acc[s];
-      *slot = gate_corner_chi2(av, 0, 0);
+      *slot = gate_corner_chi2<RES_ONLY>(av, 0, 0);
     }
   }
   lds_barrier();

@@ -1,0 +1,323 @@
+// k_slam_y.h — the fused per-feature kernel of UpdaterSLAM::update: ONE sweep Y = H L on the matrix cores per feature feeds the stack and the
+// chi2 gate (the form k_featy.h gives MSCKF features, for features whose landmark lives in the state).
+//
+//   UpdaterHelper::get_feature_jacobian_full            UpdaterHelper.cpp:192-424   (sys_measurement_rows, k_system.h: the sparse records)
+//   UpdaterHelper::get_feature_jacobian_representation  UpdaterHelper.cpp:32-190    (anchored_rep_jacobian / inv_depth_jac, k_system.h)
+//   chi2 gate on all 2m rows                            UpdaterSLAM.cpp:390-409
+//   stacking into Hx_big / res_big                      UpdaterSLAM.cpp:427-447
+//
+// A 3-dof SLAM landmark has no nullspace projection and no reflectors: the rows [H | r] go into the stack as they are and the statistic is
+// r^T S0^-1 r with S0 = H P H^T + s_f^2 I.  On the whitened route P_DD = L L^T is at hand (the prior block's factor, k_ekf.h), so
+//
+//        S0 = Y Y^T + s_f^2 I,        Y = H L     (2m x D, dense up to the landmark's last column)
+//
+// and the rows the stack wants ARE Y (scaled by sigma / sigma_f, a feature with its own noise level).  The general kernel (k_system_t) forms
+// T = H P thread-per-column from P in L2, S0 = T H^T by per-thread gathers, factors S0 in LDS eight columns at a time and sweeps H L again
+// for the stack: 0.49 ms per 25-feature chunk.
+//
+// One workgroup of SLY_NW wavefronts per feature, no cross-workgroup traffic, no spin wait:
+//   prologue   representation Jacobian (one thread), the 72-double records + 8-int minfo of sys_measurement_rows (thread per measurement) -> LDS,
+//              the residual column of the stack, the instance lists of the tile rows
+//   per block of 64 columns:
+//     sweep    wavefront w takes tile rows w, w + NW, .. (16 rows = 8 measurements): per instance — a column block some row of the tile row
+//              touches: clone blocks (6), camera extrinsics (6) / intrinsics (8), the anchor clone / anchor extrinsics of an anchored landmark,
+//              the landmark's own 3 columns — and per 16-column output tile   Y_tile += A B,  A[row][k] = H[row][fc + k] (the blocks of a row
+//              that start at fc ADD: an anchor clone that is also the measurement's clone), B[k][col] = L[fc + k][col].  An instance whose
+//              last column lies left of the output tile meets zeros of L only (lower triangular) and is skipped.             | barrier
+//     store    rows 0 .. 2m-1 of oscale Y -> the stack (coalesced: a wavefront writes 512 contiguous bytes of a row)
+//     SYRK     every wavefront: its tiles (i, j) of S0 += Y_i Y_j^T over the block's slabs of 8 columns                      | barrier
+//   gate       M = [S0 + s_f^2 I, r; r^T, 0] (identity on the padding) eliminated by feat::gate_ldl_chi2<.., RES_ONLY>: chi2 = r^T S0^-1 r is the
+//              corner entry alone — the three columns k_feat_y gives H_f stay zero and nothing is divided by them
+//   outputs    k_system_t's for nproj == 0: chi2, chi2_thresh, status = CHI2_REJECTED / atomicAdd(rows_used, 2m) (an integer), and a rejected
+//              feature — or one that did not arrive as USED — leaves its rows of the stack exactly zero.
+// Every sum has a fixed order: two runs on the same inputs return the same bits.
+#pragma once
+#include "k_featy.h"
+
+namespace ovg {
+namespace slamy {
+
+using feat::d4;
+using feat::lds_barrier;
+
+constexpr int SLY_MMAX = 62; // the longest track the kernel holds: 2 m + 4 rows of the augmented gate matrix in 8 tile rows, 36 tiles of its upper triangle
+constexpr int SLY_NW = 8;    // wavefronts per workgroup: one tile row of the sweep each at the bound
+constexpr int SLY_TPW = 5;   // gate tiles per wavefront: 36 <= 8 x 5
+constexpr int SLY_RS = 72;   // doubles per record (RO_* of k_system.h, anchor blocks included)
+constexpr int SLY_CB = 64;   // columns per block
+constexpr int SLY_LS = SLY_CB + 2;
+constexpr int SLY_INST = 27; // instances per tile row: <= 8 clone + 8 extrinsic + 8 intrinsic blocks, anchor clone, anchor extrinsics, landmark
+constexpr int SLY_ISTR = 32; // ints per tile row in the instance table: [0] count, [1 ..] (width << 16) | first column
+
+struct SlamYLds {
+  size_t yb, rows, minfo, hq, stage, inst, misc, total;
+};
+// m_max: longest track of the batch (<= SLY_MMAX)
+__host__ __device__ inline SlamYLds slamy_lds_layout(int m_max) {
+  SlamYLds L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += (bytes + 15) & ~(size_t)15;
+    return at;
+  };
+  const int nt = (2 * m_max + 15) >> 4, nta = (2 * m_max + 4 + 15) >> 4;
+  const size_t blk = (size_t)16 * nt * SLY_LS * sizeof(double), pan = (size_t)2 * nta * 256 * sizeof(double);
+  L.yb = take(blk > pan ? blk : pan); // the block of Y; afterwards the gate's row panel, twice
+  L.rows = take((size_t)m_max * SLY_RS * sizeof(double));
+  L.minfo = take((size_t)m_max * 8 * sizeof(int));
+  L.hq = take(64 * sizeof(double));
+  L.stage = take((128 + 2 * 256) * sizeof(double)); // the gate's diagonal-tile stage: scratch, E, F
+  L.inst = take((size_t)nt * SLY_ISTR * sizeof(int));
+  L.misc = take(4 * sizeof(double));
+  L.total = o;
+  return L;
+}
+
+#ifndef OVG_TU_FEATY
+__global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NW = SLY_NW, TPW = SLY_TPW, NTH = 64 * SLY_NW, RS = SLY_RS, LS = SLY_LS, CB = SLY_CB;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, cl = lane & 15;
+  const int D = p.D, LD = p.LD;
+  const SlamYLds lo = slamy_lds_layout(p.m_max);
+  double *Yb = reinterpret_cast<double *>(smem + lo.yb);
+  const int nta_max = (2 * p.m_max + 4 + 15) >> 4;
+  double *panel = Yb, *panelx = Yb + (size_t)nta_max * 256;
+  double *rows = reinterpret_cast<double *>(smem + lo.rows);
+  int *minfo = reinterpret_cast<int *>(smem + lo.minfo);
+  double *hq = reinterpret_cast<double *>(smem + lo.hq); // [12..20] dpfg_dlambda, [21..38] H_anc, [39..56] H_calib (sys_measurement_rows)
+  double *st0 = reinterpret_cast<double *>(smem + lo.stage), *stE = st0 + 128, *stF = st0 + 384;
+  int *inst = reinterpret_cast<int *>(smem + lo.inst);
+  double *chi2_slot = reinterpret_cast<double *>(smem + lo.misc);
+  int *reject_slot = reinterpret_cast<int *>(chi2_slot + 1);
+  const int nblk = (D + CB - 1) / CB;
+
+  for (int slot = p.f_begin + blockIdx.x; slot < p.f_end; slot += gridDim.x) {
+    const int f = p.order ? p.order[slot] : slot; // longest tracks first
+    const int m0 = p.meas_offsets[f];
+    const int m = p.meas_offsets[f + 1] - m0;
+    const int64_t orow0 = p.row_off[f];
+    const int n_out = (int)(p.row_off[f + 1] - orow0); // 2m
+    __syncthreads(); // the previous feature's LDS is fully consumed
+    double *out = p.Hbig + orow0 * LD;
+    if (p.status[f] != OVGPU_FEAT_USED || m > SLY_MMAX) { // failed before the gate: its rows of the stack are zero (m > SLY_MMAX: the host never sends such a batch)
+      for (int64_t e = tid; e < (int64_t)n_out * LD; e += NTH) out[e] = 0.0;
+      continue;
+    }
+    const int n = 2 * m, NT = (n + 15) >> 4, NTA = (n + 4 + 15) >> 4, NTT = NTA * (NTA + 1) / 2;
+
+    // ------------------------------------------------------------------ (a0) representation Jacobian, as k_system_t (UpdaterHelper.cpp:32-190)
+    V3 p_FinG = load_v3(p.p_FinG + 3 * f);
+    const int lm_id = p.feat_lm[f], lm_col = p.feat_lmcol[f];
+    const int rep_f = p.lm_rep[lm_id]; // a 3-dof representation: the host keeps batches with a single-depth landmark on the general kernel
+    const bool relative = rep_is_relative(rep_f);
+    const double sig2_f = p.feat_sigma ? p.feat_sigma[f] * p.feat_sigma[f] : p.opt.sigma_pix_sq;
+    const double mult_f = p.feat_chi2mult ? p.feat_chi2mult[f] : p.opt.chi2_multipler;
+    const double oscale = p.feat_sigma ? sqrt(p.opt.sigma_pix_sq) / p.feat_sigma[f] : 1.0; // one isotropic noise level in the stack
+    V3 p_FinG_fej = load_v3(p.p_fej + 3 * f);
+    int anchor_cam = -1, anchor_clone = -1;
+    if (relative) { // the landmark's anchor (UpdaterSLAM.cpp:345-348)
+      const int ac = p.feat_anchor[f];
+      anchor_cam = ac >> 10, anchor_clone = ac & 1023;
+      const V3 p_FinA = load_v3(p.p_FinA + 3 * f);
+      const M3 R_ItoC = load_m3(p.tab_cam + 12 * anchor_cam);
+      const V3 p_IinC = load_v3(p.tab_cam + 12 * anchor_cam + 9);
+      const M3 R_GtoI = load_m3(p.tab_clone + 24 * anchor_clone);
+      const V3 p_IinG = load_v3(p.tab_clone + 24 * anchor_clone + 9);
+      p_FinG = mulT(R_GtoI, mulT(R_ItoC, p_FinA - p_IinC)) + p_IinG; // UpdaterHelper.cpp:274
+      p_FinG_fej = p_FinG;                                           // :279-283: the "best" estimate
+    }
+    if (tid == 0) {
+      double *dl = hq + 12;
+      if (rep_f == OVGPU_REP_GLOBAL_3D) {
+        dl[0] = 1, dl[1] = 0, dl[2] = 0, dl[3] = 0, dl[4] = 1, dl[5] = 0, dl[6] = 0, dl[7] = 0, dl[8] = 1;
+      } else if (rep_f == OVGPU_REP_GLOBAL_FULL_INVERSE_DEPTH) {
+        inv_depth_jac(p.opt.do_fej ? p_FinG_fej : p_FinG, dl); // UpdaterHelper.cpp:46
+      } else {
+        anchored_rep_jacobian(rep_f, p.opt.do_fej, p.tab_cam + 12 * anchor_cam, p.tab_clone + 24 * anchor_clone, load_v3(p.p_FinA + 3 * f), dl, hq + 21, hq + 39);
+      }
+    }
+    __syncthreads();
+    // ------------------------------------------------------------------ (a) the records (UpdaterHelper.cpp:314-421)
+    for (int i = tid; i < m; i += NTH) sys_measurement_rows(p, m0 + i, p_FinG, p_FinG_fej, relative, hq, minfo + 8 * i, rows + (size_t)i * RS);
+    __syncthreads();
+    const int anc_ccol = relative ? p.clone_col[anchor_clone] : -1;
+    const int anc_pcol = (relative && p.opt.do_calib_pose) ? p.calib_col[anchor_cam] : -1;
+    // the residual column of the stack
+    for (int a = tid; a < n; a += NTH) out[(int64_t)a * LD + D] = oscale * rows[(size_t)(a >> 1) * RS + RO_RES + (a & 1)];
+    // the instance list of every tile row: the distinct first columns of the blocks its rows touch (blocks are disjoint column ranges: the
+    // first column identifies one), in registers; one thread per tile row
+    if (tid < NT) {
+      int cand[SLY_INST];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const int i = 8 * tid + j;
+        const bool on = i < m;
+        const int *mi = minfo + 8 * min(i, m - 1);
+        const int c0 = mi[2], c1 = mi[3], c2 = mi[4];
+        cand[3 * j] = (on && c0 >= 0) ? (c0 | (6 << 16)) : -1;
+        cand[3 * j + 1] = (on && c1 >= 0) ? (c1 | (6 << 16)) : -1;
+        cand[3 * j + 2] = (on && c2 >= 0) ? (c2 | (8 << 16)) : -1;
+      }
+      cand[24] = anc_ccol >= 0 ? (anc_ccol | (6 << 16)) : -1;
+      cand[25] = anc_pcol >= 0 ? (anc_pcol | (6 << 16)) : -1;
+      cand[26] = lm_col >= 0 ? (lm_col | (3 << 16)) : -1;
+      int *il = inst + tid * SLY_ISTR;
+      int cnt = 0;
+#pragma unroll
+      for (int e = 0; e < SLY_INST; e++) {
+        bool keep = cand[e] >= 0;
+#pragma unroll
+        for (int q = 0; q < e; q++) keep = keep && cand[q] != cand[e];
+        if (keep) il[1 + cnt++] = cand[e];
+      }
+      il[0] = cnt;
+    }
+    // this wavefront's gate tiles: linear index t = s NW + wv over the upper triangle column by column
+    int tij[TPW]; // (j << 8) | i, or -1
+    d4 acc[TPW];
+#pragma unroll
+    for (int s = 0; s < TPW; s++) {
+      const int t = s * NW + wv;
+      int i = -1, j = 0;
+      if (t < NTT) {
+        while ((j + 1) * (j + 2) / 2 <= t) j++;
+        i = t - j * (j + 1) / 2;
+      }
+      tij[s] = __builtin_amdgcn_readfirstlane(i < 0 ? -1 : ((j << 8) | i));
+      acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+#define TI(s) (tij[s] & 255)
+#define TJ(s) (tij[s] >> 8)
+    __syncthreads();
+
+    // ------------------------------------------------------------------ the column blocks
+    for (int kb = 0; kb < nblk; kb++) {
+      const int c_lo = CB * kb;
+      // ---- sweep on the matrix cores: this wavefront's tile rows of Y = H L, columns c_lo .. c_lo + 63 -> LDS
+      for (int i = wv; i < NT; i += NW) {
+        const int r = 16 * i + cl;
+        const bool rv = r < n;
+        const int mr = min(r >> 1, m - 1), par = r & 1;
+        const int *mi = minfo + 8 * mr;
+        const int myc = rv ? mi[2] : -2, myp = rv ? mi[3] : -2, myi = rv ? mi[4] : -2;
+        const int mya = rv ? anc_ccol : -2, myq = rv ? anc_pcol : -2, myl = rv ? lm_col : -2;
+        const double *rd = rows + (size_t)mr * RS;
+        const int g1 = min(4 + g, 5); // (k = 6, 7 of a 6-wide block are masked by the width test below)
+        const double hC0 = rd[RO_CLONE + 6 * par + g], hC1 = rd[RO_CLONE + 6 * par + g1];
+        const double hP0 = rd[RO_CPOSE + 6 * par + g], hP1 = rd[RO_CPOSE + 6 * par + g1];
+        const double hI0 = rd[RO_CINTR + 8 * par + g], hI1 = rd[RO_CINTR + 8 * par + 4 + g];
+        const double hA0 = relative ? rd[RO_ANC + 6 * par + g] : 0.0, hA1 = relative ? rd[RO_ANC + 6 * par + g1] : 0.0;
+        const double hQ0 = relative ? rd[RO_ACAL + 6 * par + g] : 0.0, hQ1 = relative ? rd[RO_ACAL + 6 * par + g1] : 0.0;
+        const double hF0 = rd[RO_HF + 3 * par + min(g, 2)];
+        d4 ay[4];
+        bool okc[4];
+        int cc[4];
+#pragma unroll
+        for (int ct = 0; ct < 4; ct++) {
+          ay[ct] = d4{0.0, 0.0, 0.0, 0.0};
+          okc[ct] = c_lo + 16 * ct + cl < D;
+          cc[ct] = min(c_lo + 16 * ct + cl, D - 1); // clamped address, masked value
+        }
+        const int *il = inst + i * SLY_ISTR;
+        const int cnt = __builtin_amdgcn_readfirstlane(il[0]);
+#pragma unroll 1
+        for (int e = 0; e < cnt; e++) {
+          const int code = __builtin_amdgcn_readfirstlane(il[1 + e]);
+          const int fc = code & 0xffff, w = code >> 16;
+          if (fc + w - 1 < c_lo) continue; // left of the block: zeros of L only
+          // the blocks of this lane's row that start at fc add (an anchor clone that is the measurement's own clone; anchor extrinsics of its camera)
+          double a0 = (myc == fc ? hC0 : 0.0) + (myp == fc ? hP0 : 0.0) + (myi == fc ? hI0 : 0.0) + (myl == fc ? hF0 : 0.0);
+          a0 += mya == fc ? hA0 : 0.0;
+          a0 += myq == fc ? hQ0 : 0.0;
+          double a1 = (myc == fc ? hC1 : 0.0) + (myp == fc ? hP1 : 0.0) + (myi == fc ? hI1 : 0.0);
+          a1 += mya == fc ? hA1 : 0.0;
+          a1 += myq == fc ? hQ1 : 0.0;
+          a0 = g < w ? a0 : 0.0;     // k >= w: rows of L that belong to the next block
+          a1 = 4 + g < w ? a1 : 0.0;
+          const double *L0 = p.Lw + (size_t)min(fc + g, D - 1) * D, *L1 = p.Lw + (size_t)min(fc + 4 + g, D - 1) * D;
+#pragma unroll
+          for (int ct = 0; ct < 4; ct++) {
+            if (fc + w - 1 < c_lo + 16 * ct || c_lo + 16 * ct >= D) continue; // (wave-uniform)
+            const double b0 = okc[ct] ? L0[cc[ct]] : 0.0;
+            FEAT_MFMA(a0, b0, ay[ct]);
+            if (w > 4) {
+              const double b1 = okc[ct] ? L1[cc[ct]] : 0.0;
+              FEAT_MFMA(a1, b1, ay[ct]);
+            }
+          }
+        }
+#pragma unroll
+        for (int ct = 0; ct < 4; ct++)
+#pragma unroll
+          for (int q = 0; q < 4; q++) Yb[(size_t)(16 * i + g + 4 * q) * LS + 16 * ct + cl] = ay[ct][q];
+      }
+      lds_barrier();
+      // ---- rows of oscale Y -> the stack
+      {
+        const int c = c_lo + lane;
+        if (c < D)
+          for (int a = wv; a < n; a += NW) out[(int64_t)a * LD + c] = oscale * Yb[(size_t)a * LS + lane];
+      }
+      // ---- SYRK: S0 tiles += Y_i Y_j^T over the block's slabs of 8 columns (columns >= D of the block hold zeros)
+      const int nsl = min(CB / 8, (D - 1 - c_lo) / 8 + 1);
+#pragma unroll
+      for (int s = 0; s < TPW; s++) {
+        if (tij[s] >= 0 && TJ(s) < NT) {
+          const double *ya = Yb + (size_t)(16 * TI(s) + cl) * LS + 2 * g, *yb = Yb + (size_t)(16 * TJ(s) + cl) * LS + 2 * g;
+#pragma unroll 2
+          for (int sl = 0; sl < nsl; sl++) {
+            const double2 a = *reinterpret_cast<const double2 *>(ya + 8 * sl), b = *reinterpret_cast<const double2 *>(yb + 8 * sl);
+            FEAT_MFMA(a.x, b.x, acc[s]);
+            FEAT_MFMA(a.y, b.y, acc[s]);
+          }
+        }
+      }
+      lds_barrier(); // the block is free again
+    }
+
+    // ------------------------------------------------------------------ M = [Y Y^T + s_f^2 I, r; r^T, 0]: r in column n4 (identity on the padding; the columns n4+1 .. n4+3 stay zero)
+    const int n4 = (n + 3) & ~3;
+#pragma unroll
+    for (int s = 0; s < TPW; s++) {
+      if (tij[s] < 0) continue;
+      if (16 * TJ(s) + 15 >= n) { // a tile that reaches the augmented columns / the padding
+        const int b = 16 * TJ(s) + cl;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int a = 16 * TI(s) + g + 4 * q;
+          double v = acc[s][q];
+          if (a == b) v = a < n ? v + sig2_f : ((a >= n4 && a < n4 + 4) ? 0.0 : 1.0);
+          else if (a < n && b == n4) v = rows[(size_t)(a >> 1) * RS + RO_RES + (a & 1)];
+          acc[s][q] = v;
+        }
+      } else if (TI(s) == TJ(s)) {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          if (g + 4 * q == cl) acc[s][q] += sig2_f;
+      }
+    }
+    const double chi2 = feat::gate_ldl_chi2<NW, TPW, true>(acc, tij, NT, NTA, n, panel, panelx, st0, stE, stF, chi2_slot, lane, wv);
+    if (tid == 0) {
+      const double thr = mult_f * p.chi2_table[min(n, p.chi2_table_len - 1)]; // UpdaterSLAM.cpp:392-405: dof = 2m
+      p.chi2[f] = chi2;
+      p.chi2_thresh[f] = thr;
+      const bool reject = chi2 > thr;
+      *reject_slot = reject ? 1 : 0;
+      if (reject) p.status[f] = OVGPU_FEAT_CHI2_REJECTED;
+      else if (p.rows_used) atomicAdd(p.rows_used, n_out);
+    }
+    __syncthreads(); // (a full barrier: the other wavefronts' stores to the feature's rows have landed)
+    if (*reject_slot)
+      for (int64_t e = tid; e < (int64_t)n_out * LD; e += NTH) out[e] = 0.0;
+#undef TI
+#undef TJ
+  }
+}
+#endif // OVG_TU_FEATY
+
+} // namespace slamy
+} // namespace ovg

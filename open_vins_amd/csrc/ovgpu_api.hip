@@ -26,6 +26,7 @@
 #include "k_tracks.h"
 #include "k_featy.h"
 #include "k_featy_big.h"
+#include "k_slam_y.h"
 #include "k_gram.h"
 #include "k_pchol.h"
 #include "k_unwhiten.h"
