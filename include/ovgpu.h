@@ -458,7 +458,18 @@ int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, do
  *                                  update has a null space: gauge directions) — 1.2 ms host to host at 2000 features
  *   OVGPU_COMPRESS_TSQR            the reference's form, the upper-triangular Householder factor, rows = D
  *                                  (4.0 ms); also taken beyond 383 columns (255 before ABI 5) and when the
- *                                  prior block's factorisation fails.  ovgpu_last_update_route tells which one came back. */
+ *                                  prior block's factorisation fails.  ovgpu_last_update_route tells which one came back.
+ * Which kernels the default form runs, by the column count D (LD = D + 1 with the residual column, NT = ceil(LD / 16)
+ * tile columns; ovgpu_debug_option "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel" report them):
+ *   Gram matrix   D <= 255 (NT <= 16): the one-pass kernel with ceil(NT / 2) * 2 tile columns (15 at NT = 15);
+ *                 D = 352 .. 367 (NT = 23): k_gram_wide, two passes; D = 256 .. 351 and 368 .. 383: k_gram_blk, 8 x 8-tile blocks
+ *   factor        D <= 127 (NT <= 8): k_gram_pchol_blk<4, 9, 2>; D = 128 .. 223 (NT <= 14): k_gram_pchol_blk<7, 15, 4>;
+ *                 D = 224 .. 383: the rank-one k_gram_pchol<NB>, NB = ceil(LD / 32) = 8 .. 12 ("pchol_blocked" = 0: for every
+ *                 D, NB = 1 .. 12)
+ *   un-whitening  D <= 256 and the prior block factored in one launch: k_unwhiten_blk<16>; D <= 256 otherwise
+ *                 (options.no_single_launch_cholesky, "unwhiten_blocked" = 0): k_unwhiten<16>; D = 257 .. 383: k_unwhiten<24>
+ *   D >= 384      none of them: the Householder triangle, rows = D, OVGPU_COMPRESS_TSQR
+ * A batch whose every feature is rejected returns rows = 0 and OVGPU_OK. */
 int ovgpu_msckf_compress(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2,
                          double *chi2_thresh, double *p_FinG, int32_t *D_out,
                          int32_t *rows_out, int32_t *col_cov_id, double *H,
@@ -1188,6 +1199,10 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *   "last_stack_raw"          (read only) the last pipeline's Gram matrix came from the unprojected stack
  *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one,
  *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
+ *   "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel"  (read only) what the last batch pipeline launched: the Gram kernel (0 none,
+ *                             1 the one-pass kernel, 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32); mode A's pivoted factor (0 none: the
+ *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB the rank-one k_gram_pchol<NB>);
+ *                             mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>): the rule at ovgpu_msckf_compress
  *   "slam_fused"              (default 0) 1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
  *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every
  *                             landmark the batch observes is 3-dof, its longest track holds at most 62 measurements, 16 <= D, K C <= 8192,

@@ -396,6 +396,11 @@ struct ovgpu_ctx {
   int mode_a_factor = 0;          // where mode A's compressed factor comes from: 0 Householder TSQR, 2 the diagonally pivoted Cholesky factor of the whitened Gram matrix (PCHOLQR)
   bool factor_from_gram = false;  // one-shot (compress_impl): the compressed factor of mode A comes from the Gram matrix of the whitened stack
   bool last_factor_from_gram = false;
+  // read-only ovgpu_debug_option "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel": what the last batch pipeline launched
+  //   gram:     0 none, 1 k_gram_il / k_gram<NT> (launch_gram), 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32
+  //   factor:   0 none (the Householder triangle), 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB k_gram_pchol<NB>
+  //   unwhiten: 0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>
+  int last_gram_kernel = 0, last_factor_kernel = 0, last_unwhiten_kernel = 0;
   bool chol_timed_out = false;    // finish_update: a follower of the single-launch Cholesky gave up waiting; nothing was modified
   bool prior_pending = false; // the sharded update's local stage has started the prior block's factorisation on stream2
   bool prior_overlap = true; // options.no_prior_overlap == 0: the prior block is factored on the second stream

@@ -92,6 +92,12 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
   } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big, 4 k_slam_y (SLAM batches under "slam_fused")
     if (old_value) *old_value = c->last_feat_kernel;
+  } else if (n == "last_gram_kernel") { // read-only, this and the two below: what the last batch pipeline launched (api_context.inc lists the codes)
+    if (old_value) *old_value = c->last_gram_kernel;
+  } else if (n == "last_factor_kernel") {
+    if (old_value) *old_value = c->last_factor_kernel;
+  } else if (n == "last_unwhiten_kernel") {
+    if (old_value) *old_value = c->last_unwhiten_kernel;
   } else if (n == "chol_wide") { // 0: beyond 256 columns the Cholesky-with-carry runs as one launch of k_ekf_chol_step per 16 rows instead of two panels of k_chol_fused (k_chol_wide.h)
     if (old_value) *old_value = c->chol_wide ? 1 : 0;
     if (value >= 0) c->chol_wide = value != 0;

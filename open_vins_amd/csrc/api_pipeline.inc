@@ -326,6 +326,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     hipLaunchKernelGGL(gram32::k_gram_f32_reduce, dim3(slots, 4), dim3(256), 0, c->stream, (const int32_t *)c->gram32_tiles.p, Gw,
                        (const float *)c->gram32_part.p, c->gram_G.p, LG);
     HIPCHK(hipGetLastError());
+    c->last_gram_kernel = 5;
     return factor ? set_err(OVGPU_ERR_CAPACITY, "the fp32 Gram variant feeds the on-device update only") : OVGPU_OK;
   }
   if (c->last_stack_raw) { // the unprojected stack, region by region (k_gram.h: k_gram_regions), the dropped rows' region subtracted in the reduction
@@ -341,6 +342,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     hipLaunchKernelGGL(gram::k_gram_regions_reduce, dim3(NP, 256 / gram::RR_E), dim3(gram::RR_E * gram::RR_G), 0, c->stream, NT, D, c->raw_rs,
                        (const gram::GramRegionWG *)c->gram_wg.p, c->gram_wg_n, (const double *)c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
+    c->last_gram_kernel = 4;
     return factor ? enqueue_gram_factor(c) : OVGPU_OK;
   }
   gram::GramParams g;
@@ -357,6 +359,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     hipLaunchKernelGGL(gram::k_gram_wide_win<7>, dim3(Gw), dim3(256), gram::gram_lds_bytes(), c->stream, g);
     hipLaunchKernelGGL(gram::k_gram_reduce, dim3(NP), dim3(1024), 0, c->stream, NT, Gw, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
+    c->last_gram_kernel = 3;
     return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: up to 383 columns, k_gram_pchol<9 .. 12>)
   }
   if (NT > gram::GR_NT || c->gram_fp32) { // more than 255 columns (configs[4]), or its fp32 variant: 8 x 8-tile blocks of the grid, one block pair per blockIdx.y
@@ -373,6 +376,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     else hipLaunchKernelGGL(gram::k_gram_blk<false>, dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes(), c->stream, g, NB);
     hipLaunchKernelGGL(gram::k_gram_blk_reduce, dim3(gram::GB_T * gram::GB_T, pairs), dim3(256), 0, c->stream, NB, NT, G, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
+    c->last_gram_kernel = 2;
     return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: up to 383 columns, k_gram_pchol<9 .. 12>)
   }
   switch ((NT + 1) / 2) {
@@ -390,6 +394,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   }
   hipLaunchKernelGGL(gram::k_gram_reduce, dim3(NP), dim3(1024), 0, c->stream, NT, G, c->gram_part.p, c->gram_G.p);
   HIPCHK(hipGetLastError());
+  c->last_gram_kernel = 1;
   return factor ? enqueue_gram_factor(c) : OVGPU_OK;
 }
 
@@ -406,6 +411,7 @@ static int enqueue_gram_factor(ovgpu_ctx *c) {
     if (NTf <= 8) launch_gram_pchol_blk<4, 9, 2>(c->stream, D, LD, LG, c->gram_G.p, c->Rws.p, c->gram_dropped.p, tol);
     else launch_gram_pchol_blk<7, 15, 4>(c->stream, D, LD, LG, c->gram_G.p, c->Rws.p, c->gram_dropped.p, tol);
     HIPCHK(hipGetLastError());
+    c->last_factor_kernel = NTf <= 8 ? 1 : 2;
     return OVGPU_OK;
   }
   switch ((LD + 31) / 32) {
@@ -424,6 +430,7 @@ static int enqueue_gram_factor(ovgpu_ctx *c) {
   default: return set_err(OVGPU_ERR_CAPACITY, "the pivoted Gram factor holds at most 383 Jacobian columns");
   }
   HIPCHK(hipGetLastError());
+  c->last_factor_kernel = 32 + (LD + 31) / 32;
   return OVGPU_OK;
 }
 
@@ -793,6 +800,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && b.F > 0 && (c->LD + 15) / 16 <= gram::GR_NT_BLK &&
                            (stages & STAGE_EKF) == 0 && (stages & STAGE_LOCAL) != 0 && c->whiten && !c->gram_fp32 && !slam; // (the SLAM stack is short: its mode A stays Householder)
   c->factor_from_gram = false, c->last_factor_from_gram = factor_gram;
+  c->last_gram_kernel = c->last_factor_kernel = c->last_unwhiten_kernel = 0;
   c->force_tsqr = false;
   // The prior block's factorisation needs nothing from the measurements: it runs on the second stream next to the
   // triangulation.  With the whitened stack (default) the per-feature kernel reads its factor L, so it joins before that kernel;
@@ -845,6 +853,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
           hipLaunchKernelGGL(k_unwhiten<24>, dim3((c->D + 15) / 16), dim3(64), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
                              (const int32_t *)nullptr, (const int32_t *)c->flags.p);
         HIPCHK(hipGetLastError());
+        c->last_unwhiten_kernel = (c->D + 15) / 16 > 16 ? 3 : (c->unwhiten_blocked && c->prior_uinv ? 1 : 2);
       }
     } else {
       rc = enqueue_compress(c);
