@@ -1229,6 +1229,9 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *   "gram_interleaved"        0: k_gram instead of k_gram_il (staging not interleaved with the matrix instructions)
  *   "gram_read_ahead"         (default 1) k_gram_regions reads the operands of a 4-row step during the products of the step before; 0: every step
  *                             opens with its own reads (as k_gram_il).  The same products in the same order: the same Gram matrix bit for bit
+ *   "featy_chains"            (default 1) k_feat_y takes the run list of the unprojected stack from k_batch_layout's table and requests the next
+ *                             slot's record and status a feature ahead; 0: the kernel without either (the run list derived per feature). The same
+ *                             loads, products and stores: the results are equal bit for bit.
  *   "gram_blocks_only"        1: always the 8 x 8-tile block form of the Gram kernel (k_gram_blk)
  *   "fuse_chol_inputs"        0: round 2's k_tf_gather / k_tf_abh assemble the factorisations' inputs
  *   "featy_skip"              DEVELOPER BUILD ONLY (-DOVG_FEAT_ABLATE; the shipped library answers OVGPU_ERR_INVALID): bit mask

@@ -323,6 +323,7 @@ struct ovgpu_ctx {
   // the unprojected stack of the Gram route (ovgpu_types.h: RawStack; k_gram.h: k_gram_regions)
   bool raw_enable = true;          // ovgpu_debug_option "raw_stack"
   bool gram_read_ahead = true;     // k_gram_regions<PF>: operand reads a k-step ahead (ovgpu_debug_option "gram_read_ahead")
+  bool featy_chains = true;        // k_feat_y<.., CH>: the run table, the next slot requested a feature ahead (ovgpu_debug_option "featy_chains"; k_featy.h)
   int raw_work_const = 12;         // per-row cost of a region beside its tiles, in tiles (ovgpu_debug_option "raw_work_const"; see raw_stack_layout)
   bool raw_veto = false;           // this pipeline's stack feeds mode A's factorisation: projected rows (api_pipeline.inc)
   bool raw_one_region = false;     // (developer experiment, ovgpu_debug_option "raw_stack" = 2: every row in the top region)
@@ -333,7 +334,7 @@ struct ovgpu_ctx {
   int64_t raw_base[RAW_MAXCLS + 1] = {0}, raw_rows[RAW_MAXCLS + 1] = {0};
   std::vector<uint8_t> h_cls_of_clone;
   DevBuf<uint8_t> cls_of_clone;
-  DevBuf<int32_t> raw_featbase, raw_dst;
+  DevBuf<int32_t> raw_featbase, raw_dst, raw_runs; // raw_runs: per feature FY_RUNREC records of 16 bytes (k_batch_layout, for k_feat_y<.., CH = true>)
   DevBuf<double> Hraw;
   DevBuf<gram::GramRegionWG> gram_wg; // one record per workgroup of k_gram_regions
   int gram_wg_n = 0, gram_wg_tiles = 0;

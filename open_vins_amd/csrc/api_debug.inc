@@ -78,6 +78,9 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "gram_read_ahead") { // 0: k_gram_regions opens every k-step with its own operand reads (k_gram.h: gram_il_loop without PF) — same products in the same order, the same bits
     if (old_value) *old_value = c->gram_read_ahead ? 1 : 0;
     if (value >= 0) c->gram_read_ahead = value != 0;
+  } else if (n == "featy_chains") { // 0: k_feat_y as it was before the run table and the requests ahead (k_featy.h: CH = false) — same products in the same order, the same bits
+    if (old_value) *old_value = c->featy_chains ? 1 : 0;
+    if (value >= 0) c->featy_chains = value != 0;
   } else if (n == "raw_work_const") {
     if (old_value) *old_value = c->raw_work_const;
     if (value >= 0) c->raw_work_const = (int)value;

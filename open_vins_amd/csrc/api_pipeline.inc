@@ -37,10 +37,10 @@ static int enqueue_triangulate(ovgpu_ctx *c, const double *seed_pA = nullptr, co
 // one launch of the fused per-feature kernel in the given shape (k_featy.h): as many workgroups per CU as its registers (OCC) and its
 // LDS block allow, the features dealt round-robin over them
 extern "C++" {
-template <int NW, int TPW, int OCC, bool F32, int CB>
+template <int NW, int TPW, int OCC, bool F32, int CB, bool CH = false>
 static int launch_featy(ovgpu_ctx *c, const SysParams &p, const double *sr, const int32_t *sm, const double *sV, const double *stq, const int32_t *sin, const int32_t *ssl) {
   static bool attr = false;
-  auto kern = feat::k_feat_y<NW, TPW, OCC, F32, CB>;
+  auto kern = feat::k_feat_y<NW, TPW, OCC, F32, CB, CH>;
   if (!attr) {
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
     attr = true;
@@ -51,7 +51,7 @@ static int launch_featy(ovgpu_ctx *c, const SysParams &p, const double *sr, cons
   if (lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_CAPACITY, "k_feat_y: track too long for its LDS block");
   const int per_cu = std::max(1, std::min(std::max(1, 4 * OCC / NW), (int)((size_t)c->lds_limit / lds))); // OCC wavefronts per SIMD, four SIMDs
   const int grid = std::max(1, std::min(batch_of(c).F, c->num_cu * per_cu));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl, (const int32_t *)c->raw_runs.p);
   return OVGPU_OK;
 }
 } // extern "C++"
@@ -171,9 +171,9 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
       } else {
         int rcl;
         if (c->feat_variant == 1 && p.Hbig32) rcl = launch_featy<4, 9, 2, true, 64>(c, p, sr, sm, sV, stq, sin, ssl);
-        else if (c->feat_variant == 1) rcl = launch_featy<4, 9, 2, false, 64>(c, p, sr, sm, sV, stq, sin, ssl);
+        else if (c->feat_variant == 1) rcl = c->featy_chains ? launch_featy<4, 9, 2, false, 64, true>(c, p, sr, sm, sV, stq, sin, ssl) : launch_featy<4, 9, 2, false, 64>(c, p, sr, sm, sV, stq, sin, ssl);
         else if (p.Hbig32) rcl = launch_featy<8, 17, 1, true, 64>(c, p, sr, sm, sV, stq, sin, ssl);
-        else rcl = launch_featy<8, 17, 1, false, 64>(c, p, sr, sm, sV, stq, sin, ssl);
+        else rcl = c->featy_chains ? launch_featy<8, 17, 1, false, 64, true>(c, p, sr, sm, sV, stq, sin, ssl) : launch_featy<8, 17, 1, false, 64>(c, p, sr, sm, sV, stq, sin, ssl);
         if (rcl != OVGPU_OK) return rcl;
       }
       HIPCHK(hipGetLastError());

@@ -538,10 +538,14 @@ static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
     while (fpw_want < std::min(c->layout_fpw, (int)feat::BL_FPW) && (F + fpw_want - 1) / fpw_want > 250) fpw_want *= 2;
     const int fpw = fast ? std::max(1, std::min<int>(fpw_want, (int)((48 * 1024) / lds_one))) : 1;
     const size_t lds = fast ? (size_t)fpw * lds_one : 0;
+    const bool raw_tabs = fast && c->raw_tables_ok;
+    RawStack rw; // the regions' constants for the run table (raw_stack_layout has run)
+    for (int k = 0; k <= RAW_NEG; k++) rw.base[k] = c->raw_base[k], rw.ld[k] = c->raw_ld[k], rw.rcol[k] = c->raw_rcol[k];
     hipLaunchKernelGGL(feat::k_batch_layout, dim3((F + fpw - 1) / fpw), dim3(fast ? feat::BL_NTH * fpw : 64), lds, c->stream, F, m_max, c->D, (const int32_t *)b.meas_offsets, (const uint16_t *)b.meas_cc,
                        (const int32_t *)c->clone_col.p, (const int32_t *)c->calib_col.p, (const int32_t *)c->intr_col.p, anchors ? c->anchor_pre.p : (int32_t *)nullptr,
                        fast ? c->fs_meas_feat.p : (int32_t *)nullptr, fast ? c->fs_pos.p : (int32_t *)nullptr, lists ? c->fs_inst.p : (int32_t *)nullptr, c->feat_nt_max, cb, c->C, c->K,
-                       (const uint8_t *)c->cls_of_clone.p, (const int32_t *)c->raw_featbase.p, (fast && c->raw_tables_ok) ? c->raw_dst.p : (int32_t *)nullptr);
+                       (const uint8_t *)c->cls_of_clone.p, (const int32_t *)c->raw_featbase.p, raw_tabs ? c->raw_dst.p : (int32_t *)nullptr,
+                       raw_tabs ? c->raw_runs.p : (int32_t *)nullptr, rw);
     HIPCHK(hipGetLastError());
   }
   c->inst_cb = lists ? cb : 0, c->inst_D = c->D;
@@ -747,6 +751,7 @@ static int raw_stack_layout(ovgpu_ctx *c, const uint16_t *cc) {
   HIPCHK(c->Hraw.reserve((size_t)std::max<int64_t>(total, 1)));
   HIPCHK(c->raw_featbase.reserve(fb.size()));
   HIPCHK(c->raw_dst.reserve((size_t)M));
+  HIPCHK(c->raw_runs.reserve((size_t)F * feat::FY_RUNREC * 4));
   HIPCHK(upload_deferred(c, c->raw_featbase.p, fb.data(), sizeof(int32_t) * fb.size()));
   // workgroups: one per compute unit, every live region at least one, the rest by work
   const int G = std::max(c->num_cu, live);

@@ -130,6 +130,7 @@ __global__ void __launch_bounds__(256) k_feat_rows_anchored(SysParams p, FeatSto
 constexpr int FY_INST = 24;           // instances per tile row: <= 8 clones + 8 extrinsic + 8 intrinsic blocks
 constexpr int FY_ISTR = 32;           // ints per tile row in the instance table: [0] count, [1] last non-zero column, [8 ..] instances
 constexpr int FY_IOFF = 8;
+constexpr int FY_RUNREC = RAW_MAXCLS + 1; // 16-byte records per feature in the run table of the unprojected stack (k_batch_layout): the runs, then the count
 // Round 4: the wavefront also finishes what needs nothing but the reflectors — the RESIDUAL column of the feature's stacked rows
 // (rows 3.. of Q^T r; never whitened) and the residual bound of the gate, |Q2^T r|^2 / s^2 (tq[8 f + 6]).  (The instance lists of the
 // feature's tile rows, built behind that until round 5, depend on the batch alone: k_batch_layout below, once per batch.)
@@ -253,12 +254,18 @@ constexpr int BL_NTH = 128, BL_TR = BL_NTH / 24; // threads per feature; tile ro
 // dispatched on the second stream a few microseconds later, sixteen wavefronts of 128 registers that need a compute unit to THEMSELVES — sat
 // in the queue until this kernel had drained (its kernel 97 us instead of ~80, the per-feature kernel 20 us behind the reflectors).  250
 // workgroups leave six compute units untouched, as k_triangulate's workgroups of eight features do since round 5.
+//   raw_runs       (with raw_dst) the feature's runs of rows in the unprojected stack, what k_feat_y<.., CH = true> stores and zeroes by: FY_RUNREC records of
+//                  16 bytes per feature, last region first — (first row | one past the last << 16, stride | residual column << 16, first element lo, hi) —
+//                  and the count in the first word of record RAW_MAXCLS.  The clone-major ranks ascend through the regions, so a region's share is ONE run: rows
+//                  2 lo .. 2 hi - 1 of the feature, lo = its measurements in the regions below, from the per-region counts the key loop leaves in LDS (fire-and-forget
+//                  LDS atomics next to the keys: nothing joins the ranking's chain).  `rw` carries the regions' first elements, strides and residual columns
+//                  (raw_stack_layout runs before this kernel); k_feat_y<.., CH = false> derives the list per feature behind three barriers, as every launch did before.
 constexpr int BL_FPW = 8;
 __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_max, int D, const int32_t *__restrict__ meas_offsets, const uint16_t *__restrict__ meas_cc,
                                                       const int32_t *__restrict__ clone_col, const int32_t *__restrict__ calib_col, const int32_t *__restrict__ intr_col,
                                                       int32_t *__restrict__ anchor_pre, int32_t *__restrict__ meas_feat, int32_t *__restrict__ pos, int32_t *__restrict__ inst,
                                                       int nt_max, int cb, int C, int K, const uint8_t *__restrict__ cls_of_clone, const int32_t *__restrict__ featbase,
-                                                      int32_t *__restrict__ raw_dst) {
+                                                      int32_t *__restrict__ raw_dst, int32_t *__restrict__ raw_runs, RawStack rw) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
   // a group of min(blockDim.x, BL_NTH) threads per feature (the anchors-only launch: one wavefront, one feature per workgroup)
   const int gth = min((int)blockDim.x, BL_NTH), grp = threadIdx.x / gth;
@@ -271,7 +278,9 @@ __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_m
   __shared__ int tab_clone[1024], tab_calib[64], tab_intr[64];
   __shared__ uint8_t tab_cls[1024];
   __shared__ int grp_nt[BL_FPW];
+  __shared__ __attribute__((aligned(16))) int cls_cnt[BL_FPW][RAW_MAXCLS]; // the feature's measurements per region
   if (pos) {
+    if (raw_runs && tid < RAW_MAXCLS) cls_cnt[grp][tid] = 0;
     for (int i = threadIdx.x; i < C; i += blockDim.x) tab_clone[i] = clone_col[i];
     if (raw_dst)
       for (int i = threadIdx.x; i < C; i += blockDim.x) tab_cls[i] = cls_of_clone[i];
@@ -321,6 +330,7 @@ __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_m
       const int code = meas_cc[m0 + i], cam = code >> 10;
       key = (tab_clone[code & 1023] << 8) | cam;
       meas_feat[m0 + i] = f;
+      if (raw_runs) atomicAdd(&cls_cnt[grp][tab_cls[code & 1023]], 1);
       if (inst) cand[i] = tab_calib[cam], kept[i] = tab_intr[cam]; // (parked in the candidate tables, free until the barrier below)
     }
     keys[i] = key;
@@ -346,6 +356,25 @@ __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_m
     if (inst) {
       const int c1 = cand[i], c2 = kept[i];
       cols3[3 * rank] = mykey >> 8, cols3[3 * rank + 1] = c1, cols3[3 * rank + 2] = c2;
+    }
+  }
+  if (raw_runs && active && tid >= BL_NTH - FY_RUNREC) { // the run table: the group's LAST threads, one per region and one for the count (the ranking above is the first threads' work)
+    const int k = BL_NTH - 1 - tid;
+    const i32x4 ca = *reinterpret_cast<const i32x4 *>(&cls_cnt[grp][0]), cb4 = *reinterpret_cast<const i32x4 *>(&cls_cnt[grp][4]);
+    const int cn[RAW_MAXCLS] = {ca.x, ca.y, ca.z, ca.w, cb4.x, cb4.y, cb4.z, cb4.w};
+    int lo = 0, mine = 0, above = 0, nr = 0;
+#pragma unroll
+    for (int j = 0; j < RAW_MAXCLS; j++) lo += j < k ? cn[j] : 0, mine = j == k ? cn[j] : mine, above += j > k && cn[j] > 0, nr += cn[j] > 0;
+    i32x4 *rt = reinterpret_cast<i32x4 *>(raw_runs) + (size_t)f * FY_RUNREC;
+    if (k == RAW_MAXCLS) rt[RAW_MAXCLS] = i32x4{nr, 0, 0, 0};
+    else if (mine > 0) {
+      int64_t base = rw.base[0];
+      int ld = rw.ld[0], rcol = rw.rcol[0];
+#pragma unroll
+      for (int q = 1; q < RAW_MAXCLS; q++)
+        if (k == q) base = rw.base[q], ld = rw.ld[q], rcol = rw.rcol[q];
+      const int64_t off = base + (int64_t)(featbase[f * RAW_MAXCLS + k] + 2 * lo) * ld;
+      rt[above] = i32x4{(2 * lo) | ((2 * (lo + mine)) << 16), ld | (rcol << 16), (int)(uint32_t)(uint64_t)off, (int)(uint32_t)((uint64_t)off >> 32)};
     }
   }
   if (!inst) return;
@@ -561,10 +590,25 @@ __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)
 // goes through the scalar cache, and the thread-per-column form this replaces (Jacobian values as scalar operands, 100+ scalar
 // registers per measurement, 229 of them spilled) spent 44 % of the kernel in its sweep.
 // ---------------------------------------------------------------------------------------------------
-template <int NW, int TPW, int OCC, bool F32OUT = false, int CB = FY_CB>
+//
+// CH ("chains", ovgpu_debug_option "featy_chains" = 1, the default; float64 stack only): dependent memory round trips that nothing of the workgroup's
+// own hides are taken off the head of the slot loop — the SAME loads, products and stores otherwise, the same bits:
+//   - the run list of the unprojected stack comes from k_batch_layout's table (runsG: 16 bytes per lane, lane j run j) instead of being derived per
+//     feature behind three barriers and a serial section of one thread;
+//   - the slot record of the workgroup's NEXT feature is requested during this one, and its status behind it; T, the bound, the threshold, the runs
+//     and the reflectors' DMA leave together at the head of the slot loop, nothing of them is waited for before the first sweep's own loads are out;
+//   - the bound's verdict (skip_gate) is taken where the first SYRK needs it, behind the first sweep's barrier.
+// CH = false is the kernel as it was: the other side of the bit comparison (tests/test_gpu_featy_chains.py).  What was built, measured and left out
+// (a sweep's first operands requested by the sweep before it, [r | H_f] in one request) is in DESIGN.md section 4.2.
+template <int NW, int TPW, int OCC, bool F32OUT = false, int CB = FY_CB, bool CH = false>
 __global__ void __launch_bounds__(64 * NW, OCC)
     k_feat_y(SysParams p, int nt_max, int nta_max, const double *__restrict__ rowsG, const int32_t *__restrict__ minfoG, const double *__restrict__ VG,
-             const double *__restrict__ tqG, const int32_t *__restrict__ instG, const int32_t *__restrict__ slotsG) {
+             const double *__restrict__ tqG, const int32_t *__restrict__ instG, const int32_t *__restrict__ slotsG, const int32_t *__restrict__ runsG) {
+  static_assert(!(CH && F32OUT), "the chains form is built for the float64 stack");
+  // the parts that hold a register through the whole feature (the runs in four registers, the next status, the bound kept for the late verdict): the
+  // four-wavefront shape has the room (240 registers, no scratch); the eight-wavefront shape spills already, takes the runs from the table per call and
+  // keeps the rest as it was — its scratch stays at the 232 bytes it had
+  constexpr bool CHX = CH && NW == 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NTH = 64 * NW;
   constexpr int LS = CB + 2;      // row stride of the LDS block (FY_LS at 64 columns)
@@ -613,24 +657,71 @@ __global__ void __launch_bounds__(64 * NW, OCC)
     const long long tn = clock64();            \
     p.dbg[220 + (i)] += tn - tlast, tlast = tn; \
   }
+// ... and a counter behind a drained wait: the time until a sweep's first operands are there (slots 7 / 8: the first / the second run of a sweep)
+#define FEAT_TW(i)                                                  \
+  if (prof) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+  FEAT_T(i)
 #else
 #define FEAT_T(i)
+#define FEAT_TW(i)
 #endif
 
   // Static schedule (round 4): slot = blockIdx.x, + gridDim.x, ..  over the features sorted by descending track length — the
   // workgroups' shares differ by one short track at most — and everything a feature's prologue used to look up in a chain (slot ->
   // feature -> offsets -> rows) is ONE 32-byte record per slot (FeatSlot, written by the host with the batch).  No atomic, no
   // dependent scalar loads between two features.
+  // CH: the record of the slot the loop takes next, requested a feature ahead, and (CHX) that feature's status behind it (the first ones: here).  A status
+  // changes under this kernel's hands only when the feature's OWN workgroup rejects it: the one read a feature early is the one read at its head.
+  int nrec[6] = {0, 0, 0, 0, 0, 0}, nstatus = 0;
+  if (CH && (int)blockIdx.x < p.F) {
+    const int32_t *rec = slotsG + (size_t)8 * blockIdx.x;
+#pragma unroll
+    for (int q = 0; q < 6; q++) nrec[q] = rec[q];
+    if (CHX) nstatus = p.status[nrec[0]];
+  }
   for (int slot = blockIdx.x; slot < p.F; slot += gridDim.x) {
     lds_barrier(); // the previous feature's LDS is fully consumed
     const int32_t *rec = slotsG + (size_t)8 * slot;
-    const int f = __builtin_amdgcn_readfirstlane(rec[0]);
-    const int m0 = __builtin_amdgcn_readfirstlane(rec[1]);
-    const int m = __builtin_amdgcn_readfirstlane(rec[2]);
-    const int n_out = __builtin_amdgcn_readfirstlane(rec[3]); // 2m - 3 (0 when m < 2)
-    const int64_t orow0 = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(rec[5]) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane(rec[4]));
+    const int f = __builtin_amdgcn_readfirstlane(CH ? nrec[0] : rec[0]);
+    const int m0 = __builtin_amdgcn_readfirstlane(CH ? nrec[1] : rec[1]);
+    const int m = __builtin_amdgcn_readfirstlane(CH ? nrec[2] : rec[2]);
+    const int n_out = __builtin_amdgcn_readfirstlane(CH ? nrec[3] : rec[3]); // 2m - 3 (0 when m < 2)
+    const int64_t orow0 = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(CH ? nrec[5] : rec[5]) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane(CH ? nrec[4] : rec[4]));
     const StackRows<F32OUT> out(p, orow0);
-    if (raw) { // where the feature's measurements sit in the unprojected stack: clone-major positions ascend through the regions, a region's share is one run of rows
+    // CH: everything the feature's head needs leaves here in one go — its status, the factor T with the gate's bound, the runs of the unprojected stack
+    // (lane j: run j, the count in lane RAW_MAXCLS) and, below, the reflectors' DMA; nothing of it is waited for before the first sweep's own loads are out
+    const int n = 2 * m;
+    int status_f = 0;
+    i32x4 rr = {0, 0, 0, 0};
+    double T00, T01, T02, T11, T12, T22, bound, thr;
+    // the factor T, the gate's bound (k_feat_vt) and threshold; the reflectors -> LDS (DMA path: no registers, and nothing waits for them before the first
+    // sweep is done)
+    auto head_loads = [&]() {
+      const double *tq = tqG + (size_t)8 * f;
+      T00 = tq[0], T01 = tq[1], T02 = tq[2], T11 = tq[3], T12 = tq[4], T22 = tq[5];
+      bound = tq[6];
+      thr = p.opt.chi2_multipler * p.chi2_table[min(max(n - 3, 0), p.chi2_table_len - 1)]; // UpdaterMSCKF.cpp:216-222
+      const int nchunk = (24 * n + 1023) >> 10; // 1 KiB per wavefront and instruction; a lane past the end re-reads the last 16 bytes
+      const char *src = reinterpret_cast<const char *>(VG + (size_t)6 * m0); // V[a][k] = VG[6 m0 + 3 a + k]
+      for (int ch = wv; ch < nchunk; ch += NW) {
+        const int off = min(1024 * ch + 16 * lane, 24 * n - 16);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + off),
+                                         (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(Vl) + 1024 * ch), 16, 0, 0);
+      }
+    };
+    const bool has_next = slot + (int)gridDim.x < p.F;
+    if (CH) {
+      status_f = CHX ? nstatus : p.status[f];
+      if (raw && CHX) rr = reinterpret_cast<const i32x4 *>(runsG)[(size_t)f * FY_RUNREC + min(lane, RAW_MAXCLS)];
+      head_loads();
+    }
+    // CH: the record of the workgroup's next slot, a whole feature ahead of its use (no load beyond the table)
+    if (CH && has_next) {
+      const int32_t *nx = slotsG + (size_t)8 * (slot + gridDim.x);
+#pragma unroll
+      for (int q = 0; q < 6; q++) nrec[q] = nx[q];
+    }
+    if (raw && !CH) { // where the feature's measurements sit in the unprojected stack: clone-major positions ascend through the regions, a region's share is one run of rows
       if (tid < RAW_MAXCLS) clsbeg[tid] = -1;
       lds_barrier(); // (the table of the feature before is consumed: the barrier at the head of the loop)
       if (tid < m) {
@@ -657,8 +748,9 @@ __global__ void __launch_bounds__(64 * NW, OCC)
     // the feature's runs of rows: fn(first row, one past the last, first element, stride, residual column), all in scalar registers
     // (lane j fetches run j: ONE LDS round trip per call, the runs then come out of the lanes by v_readlane — a read per run was a round trip per run)
     auto raw_runs = [&](auto fn) {
-      const int nr = __builtin_amdgcn_readfirstlane(*nruns);
-      const i32x4 rr = runs[lane & (RAW_MAXCLS - 1)];
+      if (CH && !CHX) rr = reinterpret_cast<const i32x4 *>(runsG)[(size_t)f * FY_RUNREC + min(lane, RAW_MAXCLS)]; // (requested per call: its wait lies behind the call's own LDS reads)
+      if (!CH) rr = runs[lane & (RAW_MAXCLS - 1)];
+      const int nr = CH ? __builtin_amdgcn_readlane(rr.x, RAW_MAXCLS) : __builtin_amdgcn_readfirstlane(*nruns);
 #pragma unroll 1
       for (int j = 0; j < nr; j++) {
         const int ab = __builtin_amdgcn_readlane(rr.x, j), ls = __builtin_amdgcn_readlane(rr.y, j);
@@ -680,14 +772,16 @@ __global__ void __launch_bounds__(64 * NW, OCC)
         for (int c = lane; c < ldn; c += 64) row[c] = 0.0;
       }
     };
-    if (p.status[f] != OVGPU_FEAT_USED) { // failed before the gate: its rows of the stack are zero
+    if (!CH) status_f = p.status[f];
+    if (status_f != OVGPU_FEAT_USED) { // failed before the gate: its rows of the stack are zero
       if (raw) raw_zero();
       else
         for (int64_t e = tid; e < (int64_t)n_out * out.ld; e += NTH) out.zero(e);
+      if (CHX && has_next) nstatus = p.status[nrec[0]]; // (requested behind the first sweep otherwise)
       continue;
     }
     // NT: tile rows that hold rows of Y (swept, factored); NTA: tile rows of the gate matrix with its four augmented rows
-    const int n = 2 * m, NT = (n + 15) >> 4, NTA = (n + 4 + 15) >> 4, NTT = NTA * (NTA + 1) / 2;
+    const int NT = (n + 15) >> 4, NTA = (n + 4 + 15) >> 4, NTT = NTA * (NTA + 1) / 2;
     // this wavefront's tiles: linear index t = s NW + wv over the upper triangle column by column
     int tij[TPW]; // (j << 8) | i, or -1 for an unused slot
     d4 acc[TPW];
@@ -708,30 +802,18 @@ __global__ void __launch_bounds__(64 * NW, OCC)
 #define TJ(s) (tij[s] >> 8)
     const double *frow = rowsG + (size_t)m0 * RS;   // this feature's records in the row store
     const int32_t *finfo = minfoG + (size_t)8 * m0;
-    const double *fV = VG + (size_t)6 * m0;         // V[a][k] = fV[3 a + k]
-    const double T00 = tqG[(size_t)8 * f], T01 = tqG[(size_t)8 * f + 1], T02 = tqG[(size_t)8 * f + 2], T11 = tqG[(size_t)8 * f + 3],
-                 T12 = tqG[(size_t)8 * f + 4], T22 = tqG[(size_t)8 * f + 5];
 
-    // ------------------------------------------------------------------ prologue: reflectors -> LDS (DMA path: no registers, and
-    // nothing waits for them before the first sweep is done), the tile rows' last columns; the residual column of the stack and the
-    // gate's bound were left by k_feat_vt
-    {
-      const int nchunk = (24 * n + 1023) >> 10; // 1 KiB per wavefront and instruction; a lane past the end re-reads the last 16 bytes
-      const char *src = reinterpret_cast<const char *>(fV);
-      for (int ch = wv; ch < nchunk; ch += NW) {
-        const int off = min(1024 * ch + 16 * lane, 24 * n - 16);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + off),
-                                         (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(Vl) + 1024 * ch), 16, 0, 0);
-      }
-    }
+    // ------------------------------------------------------------------ prologue: T, the bound and the reflectors' DMA (CH: requested above), the tile
+    // rows' last columns; the residual column of the stack and the gate's bound were left by k_feat_vt
+    if (!CH) head_loads();
     const int32_t *finst = instG + (size_t)f * nt_max * FY_ISTR; // per tile row: count, last non-zero column, block starts, instances (k_feat_vt)
     if (tid < NT) rowlim[tid] = finst[(size_t)tid * FY_ISTR + 1];
     out.pad(tid, NTH, n_out, LD);
-    const double bound = tqG[(size_t)8 * f + 6];
-    const double thr = p.opt.chi2_multipler * p.chi2_table[min(n - 3, p.chi2_table_len - 1)]; // UpdaterMSCKF.cpp:216-222
     // (1 - 1e-9): the bound is a float64 sum of ~100 squares and the reference's own chi2 carries ~1e-12 of rounding: a feature
-    // this close to the threshold takes the full gate
-    const bool skip_gate = __builtin_amdgcn_readfirstlane((int)(!p.opt.gate_always_factor && bound <= thr * (1.0 - 1e-9))) != 0;
+    // this close to the threshold takes the full gate.  CH: the verdict is first needed by the first SYRK and taken there (bound_b: opaque to the
+    // compiler behind the first sweep's barrier, so that the comparison — a wait for the bound — is not hoisted in front of the sweep's own loads)
+    auto gate_skipped = [&](double b) { return __builtin_amdgcn_readfirstlane((int)(!p.opt.gate_always_factor && b <= thr * (1.0 - 1e-9))) != 0; };
+    bool skip_gate = CHX ? false : gate_skipped(bound);
     FEAT_T(0)
 
     // ------------------------------------------------------------------ the column blocks
@@ -781,6 +863,7 @@ __global__ void __launch_bounds__(64 * NW, OCC)
           double bc[2 * NCT], bn[2 * NCT];
           int code = code_at(e_a), code_n = code_at(min(e_a + 1, e_b - 1));
           load_b(code, bc);
+          FEAT_TW(NCT == NCTB ? 8 : 7)
 #pragma unroll 1
           for (int e = e_a; e < e_b; e++) {
             load_b(code_n, bn); // in flight while this instance's products run (TWO instances ahead, a third operand set: 0.439 -> 0.454 ms of stage time)
@@ -805,9 +888,16 @@ __global__ void __launch_bounds__(64 * NW, OCC)
         for (int ct = 0; ct < NCTB; ct++)
 #pragma unroll
           for (int q = 0; q < 4; q++) Yb[(size_t)(16 * i + g + 4 * q) * LS + 16 * ct + cl] = ay[ct][q];
+        FEAT_T(1)
       }
       if (kb == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the reflectors' DMA (issued in the prologue) has landed
       lds_barrier();
+      if (CHX && kb == 0 && has_next) nstatus = p.status[nrec[0]]; // (the next slot's record is there: this barrier waited for it)
+      if (CHX && kb == 0) {
+        double bound_b = bound;
+        asm volatile("" : "+v"(bound_b));
+        skip_gate = gate_skipped(bound_b);
+      }
       FEAT_T(1)
       // ---- V^T Y per column (lane = (row parity, column), the rows dealt to the wavefronts)
       if (!(FY_SKIP(p) & 2)) {
@@ -958,6 +1048,7 @@ __global__ void __launch_bounds__(64 * NW, OCC)
     FEAT_T(5)
   }
 #undef FEAT_T
+#undef FEAT_TW
 #undef TI
 #undef TJ
 }
@@ -966,15 +1057,17 @@ __global__ void __launch_bounds__(64 * NW, OCC)
 // ovgpu_featy_tu.hip instantiates them, ovgpu_api.hip declares them extern.
 //   <4, 9, 2, *, 64>   tracks of up to 62 observations (36 tiles), two workgroups per CU — the headline shape
 //   <8, 17, 1, *, 64>  up to 126 observations (136 tiles), one workgroup per CU
+// The last argument is CH (the head of k_feat_y): the float64 shapes carry both forms, the float32 stack the one without.
 // (OCC is __launch_bounds__' second argument: wavefronts per SIMD.  Round 5's occupancy experiments <4, 9, 3, *, 32>, <8, 5, 4, *, 32> and the
 // wavefront-per-feature kernel were measured slower — profiles/r05_b_feature_kernel_shapes_ab.txt — and left the tree in round 6, as did
 // round 6's own <8, 17, 1, *, 32>: 32-column blocks remove the 8-wavefront shape's spills and cost more in barriers than the spills did,
 // 7.26 against 6.61 ms of stage time at configs[3] on one GPU, profiles/r06_a_featy_8wave_32_column_blocks_ab.txt.)
 #define OVG_FEATY_SHAPES(X)                                                                                                     \
-  X(4, 9, 2, false, 64) X(4, 9, 2, true, 64) X(8, 17, 1, false, 64) X(8, 17, 1, true, 64)
+  X(4, 9, 2, false, 64, false) X(4, 9, 2, true, 64, false) X(8, 17, 1, false, 64, false) X(8, 17, 1, true, 64, false) \
+  X(4, 9, 2, false, 64, true) X(8, 17, 1, false, 64, true)
 #define OVG_FEATY_ARGS                                                                                                                           \
   SysParams, int, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__, const double *__restrict__, \
-      const int32_t *__restrict__, const int32_t *__restrict__
+      const int32_t *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__
 
 } // namespace feat
 } // namespace ovg

@@ -48,7 +48,7 @@
 // only declared, so that their launches below bind to those definitions.
 namespace ovg {
 namespace feat {
-#define X(NW, TPW, OCC, F32, CB) extern template __global__ void k_feat_y<NW, TPW, OCC, F32, CB>(OVG_FEATY_ARGS);
+#define X(NW, TPW, OCC, F32, CB, CH) extern template __global__ void k_feat_y<NW, TPW, OCC, F32, CB, CH>(OVG_FEATY_ARGS);
 OVG_FEATY_SHAPES(X)
 #undef X
 extern template __global__ void k_feat_y_big<8, 17, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,

@@ -25,7 +25,7 @@
 
 namespace ovg {
 namespace feat {
-#define X(NW, TPW, OCC, F32, CB) template __global__ void k_feat_y<NW, TPW, OCC, F32, CB>(OVG_FEATY_ARGS);
+#define X(NW, TPW, OCC, F32, CB, CH) template __global__ void k_feat_y<NW, TPW, OCC, F32, CB, CH>(OVG_FEATY_ARGS);
 OVG_FEATY_SHAPES(X)
 #undef X
 template __global__ void k_feat_y_big<8, 17, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
