@@ -573,7 +573,8 @@ int ovgpu_set_active_landmarks(ovgpu_ctx *ctx, int32_t n, const int32_t *lm_inde
  * With ovgpu_debug_option "slam_fused" = 1 (default 0) a batch whose landmarks are all 3-dof and whose
  * longest track holds at most 62 measurements takes its per-feature stage as ONE fused kernel
  * (S0 = Y Y^T + sigma^2 I from the whitened rows Y = H L the stack holds anyway): the same update to
- * rounding, this entry and ovgpu_slam_update_chunked alike.                                */
+ * rounding, this entry and ovgpu_slam_update_chunked alike.  At level 2 a batch that observes
+ * single-depth landmarks takes it as well (the bearing's projection inside the same kernel).  */
 int ovgpu_slam_update(ovgpu_ctx *ctx, const int32_t *lm_index, int32_t *feat_status,
                       double *chi2, double *chi2_thresh, double *dx, double *P_out,
                       double *lm_out, ovgpu_update_stats *stats);
@@ -1199,18 +1200,28 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *   "last_stack_raw"          (read only) the last pipeline's Gram matrix came from the unprojected stack
  *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one,
  *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
+ *                             (k_slam_y<false>: no single-depth landmark observed), 5 k_slam_y<true>, the same kernel with the projection of
+ *                             single-depth landmarks ("slam_fused" = 2)
  *   "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel"  (read only) what the last batch pipeline launched: the Gram kernel (0 none,
  *                             1 the one-pass kernel, 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32); mode A's pivoted factor (0 none: the
  *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB the rank-one k_gram_pchol<NB>);
  *                             mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>): the rule at ovgpu_msckf_compress
- *   "slam_fused"              (default 0) 1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
+ *   "slam_fused"              (default 0) a level; the read-back returns it (values above 2 are taken as 2).
+ *                             1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
  *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every
  *                             landmark the batch observes is 3-dof, its longest track holds at most 62 measurements, 16 <= D, K C <= 8192,
  *                             options.no_fast_feature_kernel is 0 and the update takes the whitened (Gram) route; per-feature sigma_pix /
  *                             chi2_multipler do not disqualify.  Everything else keeps the general kernel: a batch with a single-depth landmark,
  *                             the Householder route (compress_route = OVGPU_COMPRESS_TSQR, more than 383 columns, the repeat after a failed prior
- *                             pivot), ovgpu_slam_compress, the delayed initialisation.  Takes effect with the next ovgpu_set_features
- *   "slam_fused_batches"      counter: batch pipelines that took k_slam_y, once per update — the pipelines of an attempt the library repeats (through the
+ *                             pivot), ovgpu_slam_compress, the delayed initialisation.
+ *                             2: level 1, and a batch that observes a single-depth landmark (OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) takes
+ *                             k_slam_y<true> when the remaining terms hold (longest track <= 62, 16 <= D, K C <= 8192, no_fast_feature_kernel 0, the
+ *                             whitened route): per feature of such a landmark the two reflectors of its bearing columns are applied to the rows
+ *                             of [Y | r] on their way to the stack (2m - 2 rows) and the gate is r^T S0^-1 r - g^T G^-1 g at dof 2m - 2, from the
+ *                             same sweep; a batch that observes none takes k_slam_y<false> as at level 1, with the same bits.  The fall-backs
+ *                             of level 1 stay.  Takes effect with the next ovgpu_set_features (a batch over landmarks of both sizes is laid out
+ *                             again when a SLAM call names its landmarks: the level in force at that call decides)
+ *   "slam_fused_batches"      counter: batch pipelines that took k_slam_y (either instantiation), once per update — the pipelines of an attempt the library repeats (through the
  *                             Householder route after a failed prior pivot, with the step-wise Cholesky after a time-out) are not counted; a value >= 0 sets it
  *   "anchored_fast"           (default 1) batches of an anchored feat_rep_msckf take the fused per-feature kernels: 48-double records with
  *                             H_f = A dl at the p_FinG the anchor gives and no anchor blocks, which the nullspace projection annihilates

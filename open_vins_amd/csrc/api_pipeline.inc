@@ -190,12 +190,14 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   if (p.slam && p.Lw && f_one < 0 && c->slam_fused_ok) {
     static bool attr_s = false;
     if (!attr_s) {
-      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
       attr_s = true;
     }
     if (p.m_max > slamy::SLY_MMAX || c->slamy_lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_INVALID, "internal: k_slam_y was selected for a batch it does not hold");
-    c->last_feat_kernel = 4, c->slam_fused_batches++, c->slam_fused_attempt++;
-    hipLaunchKernelGGL(slamy::k_slam_y, dim3(std::max(1, std::min(b.F, c->num_cu))), dim3(64 * slamy::SLY_NW), c->slamy_lds, c->stream, p);
+    c->last_feat_kernel = c->slam_fused_proj ? 5 : 4, c->slam_fused_batches++, c->slam_fused_attempt++;
+    if (c->slam_fused_proj) hipLaunchKernelGGL(slamy::k_slam_y<true>, dim3(std::max(1, std::min(b.F, c->num_cu))), dim3(64 * slamy::SLY_NW), c->slamy_lds, c->stream, p);
+    else hipLaunchKernelGGL(slamy::k_slam_y<false>, dim3(std::max(1, std::min(b.F, c->num_cu))), dim3(64 * slamy::SLY_NW), c->slamy_lds, c->stream, p);
     HIPCHK(hipGetLastError());
     return OVGPU_OK;
   }

@@ -655,19 +655,23 @@ static int size_feature_stage(ovgpu_ctx *c) {
     }
   }
   c->lm_fast_ok = c->L > 0 && c->feat_variant != 0 && c->featy_ok;
-  // ---- SLAM batches: the fused per-feature kernel k_slam_y (k_slam_y.h) behind ovgpu_debug_option "slam_fused".  Eligible: every landmark the
-  // batch observes is 3-dof (a batch that holds a single-depth landmark keeps the general kernel as a whole: its two reflectors stay there; a
-  // batch of a mixed-dof state whose landmarks are not named yet is laid out again once they are, slam_prepare), the longest track within the
-  // kernel's bound, and the fused kernels' limits on the state.  Per-feature sigma / multiplier do not disqualify (ArUco corners).
-  c->slam_fused_ok = false, c->slamy_lds = 0;
+  // ---- SLAM batches: the fused per-feature kernel k_slam_y (k_slam_y.h) behind ovgpu_debug_option "slam_fused", a level.  Eligible at level 1:
+  // every landmark the batch observes is 3-dof (a batch that holds a single-depth landmark keeps the general kernel as a whole: its two
+  // reflectors stay there), the longest track within the kernel's bound, and the fused kernels' limits on the state.  At level 2 a batch that
+  // observes a single-depth landmark takes k_slam_y<true>, the instantiation with the projection, on the same terms and its own LDS carve; a
+  // batch that observes none takes k_slam_y<false> as at level 1.  A batch of a mixed-dof state whose landmarks are not named yet is laid out
+  // again once they are (slam_prepare).  Per-feature sigma / multiplier do not disqualify (ArUco corners).
+  c->slam_fused_ok = false, c->slam_fused_proj = false, c->slamy_lds = 0;
   if (slam_rows && c->slam_fused && !c->no_feat_kernel && c->L > 0 && m_max <= slamy::SLY_MMAX && c->D >= 16 && c->K * c->C <= 8192) {
-    bool dof3 = lm_uniform_dof(c) == 3;
-    if (!dof3 && lm_uniform_dof(c) == 0 && (int)b.h_feat_lm.size() == F) {
-      dof3 = true;
+    const int udof = lm_uniform_dof(c);
+    bool dof3 = udof == 3, named = udof != 0;
+    if (udof == 0 && (int)b.h_feat_lm.size() == F) {
+      dof3 = true, named = true;
       for (int f = 0; f < F; f++) dof3 = dof3 && lm_dof(c->h_lm_rep[b.h_feat_lm[f]]) == 3;
     }
-    const size_t lds = slamy::slamy_lds_layout(std::max(m_max, 1)).total;
-    if (dof3 && lds <= (size_t)c->lds_limit) c->slam_fused_ok = true, c->slamy_lds = lds;
+    const bool proj = named && !dof3 && c->slam_fused >= 2;
+    const size_t lds = slamy::slamy_lds_layout(std::max(m_max, 1), proj).total;
+    if ((dof3 || proj) && lds <= (size_t)c->lds_limit) c->slam_fused_ok = true, c->slam_fused_proj = proj, c->slamy_lds = lds;
   }
   if (c->feat_variant) { // row store of the fast path
     const int M = std::max(b.M, 1);

@@ -474,24 +474,27 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // acc / tij: this wavefront's tiles; panel: 2 x nta_max tiles of LDS (Y, then X); st0: 128 doubles, stE / stF: 256 each; slot: one double.
 // NT = tile rows that hold rows of S0, NTA = tile rows of M.  Returns chi2 in every lane; ends with the workgroup synchronised.
 // ---------------------------------------------------------------------------------------------------
-// RES_ONLY (k_slam_y.h: a landmark that lives in the state has no projection): R = [r | 0 0 0], the statistic is r^T S0^-1 r = -C_00 alone and G = 0 is never solved
-template <bool RES_ONLY = false>
-__device__ __forceinline__ double gate_corner_chi2(const d4 &t, int q, int coff) { // C = rows 4 q .. 4 q + 3, columns coff .. coff + 3 of the tile (q, coff wave-uniform)
+// MODE 1 (k_slam_y.h: a landmark that lives in the state has no projection): R = [r | 0 0 0], the statistic is r^T S0^-1 r = -C_00 alone and G = 0 is never solved
+// MODE 2 (k_slam_y<true>): MODE 1 unless `two` (wave-uniform) is set — a single-depth landmark, R = [r | H_b | 0]: the fourth row and column of C are zero and
+//         the 3 x 3 solve takes the identity entry k_system_t puts at G22 (k_system.h: "two projected columns")
+// MODE 0 (the default, k_feat_y): R = [r | H_f]
+template <int MODE = 0>
+__device__ __forceinline__ double gate_corner_chi2(const d4 &t, int q, int coff, bool two = false) { // C = rows 4 q .. 4 q + 3, columns coff .. coff + 3 of the tile (q, coff wave-uniform)
   double v = t[0];
 #pragma unroll
   for (int u = 1; u < 4; u++) v = q == u ? t[u] : v;
-  if (RES_ONLY) return -bcast_lane(v, coff);
+  if (MODE == 1 || (MODE == 2 && !two)) return -bcast_lane(v, coff);
   const double c00 = bcast_lane(v, coff), c01 = bcast_lane(v, coff + 1), c02 = bcast_lane(v, coff + 2), c03 = bcast_lane(v, coff + 3);
   const double c11 = bcast_lane(v, 16 + coff + 1), c12 = bcast_lane(v, 16 + coff + 2), c13 = bcast_lane(v, 16 + coff + 3);
   const double c22 = bcast_lane(v, 32 + coff + 2), c23 = bcast_lane(v, 32 + coff + 3), c33 = bcast_lane(v, 48 + coff + 3);
-  const M3 Gm{-c11, -c12, -c13, -c12, -c22, -c23, -c13, -c23, -c33};
+  const M3 Gm{-c11, -c12, -c13, -c12, -c22, -c23, -c13, -c23, MODE == 2 ? 1.0 : -c33};
   const V3 gv{-c01, -c02, -c03};
   const V3 x = colpiv_qr_solve3(Gm, gv);
   return -c00 - dot(gv, x);
 }
-template <int NW, int TPW, bool RES_ONLY = false>
+template <int NW, int TPW, int MODE = 0>
 __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)[TPW], int NT, int NTA, int n, double *panel, double *panelx, double *st0, double *stE,
-                                                double *stF, double *slot, int lane, int wv) {
+                                                double *stF, double *slot, int lane, int wv, bool two = false) {
   const int g = lane >> 4, cl = lane & 15;
   const int n4 = (n + 3) & ~3;
   const bool shared = NTA == NT; // the augmented rows share S0's last tile
@@ -514,7 +517,7 @@ __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)
         if (NW == 4) __builtin_amdgcn_s_setprio(3);
         const int nblk = min(4, (n4 - 16 * k) >> 2);
         diag_tile_ldl_blk(av, ev, fv, st0, lane, nblk);
-        if (last) *slot = gate_corner_chi2<RES_ONLY>(av, nblk, 4 * nblk);
+        if (last) *slot = gate_corner_chi2<MODE>(av, nblk, 4 * nblk, two);
         else {
 #pragma unroll
           for (int q = 0; q < 4; q++) stE[cl * 16 + g + 4 * q] = ev[q], stF[cl * 16 + g + 4 * q] = fv[q]; // accumulator layout -> the A operand's order
@@ -567,7 +570,7 @@ __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)
 #pragma unroll
       for (int s = 0; s < TPW; s++)
         if (s == slot_t) av = acc[s];
-      *slot = gate_corner_chi2<RES_ONLY>(av, 0, 0);
+      *slot = gate_corner_chi2<MODE>(av, 0, 0, two);
     }
   }
   lds_barrier();

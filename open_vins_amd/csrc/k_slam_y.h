@@ -26,11 +26,12 @@
 //              last column lies left of the output tile meets zeros of L only (lower triangular) and is skipped.             | barrier
 //     store    rows 0 .. 2m-1 of oscale Y -> the stack (coalesced: a wavefront writes 512 contiguous bytes of a row)
 //     SYRK     every wavefront: its tiles (i, j) of S0 += Y_i Y_j^T over the block's slabs of 8 columns                      | barrier
-//   gate       M = [S0 + s_f^2 I, r; r^T, 0] (identity on the padding) eliminated by feat::gate_ldl_chi2<.., RES_ONLY>: chi2 = r^T S0^-1 r is the
+//   gate       M = [S0 + s_f^2 I, r; r^T, 0] (identity on the padding) eliminated by feat::gate_ldl_chi2<.., MODE 1>: chi2 = r^T S0^-1 r is the
 //              corner entry alone — the three columns k_feat_y gives H_f stay zero and nothing is divided by them
 //   outputs    k_system_t's for nproj == 0: chi2, chi2_thresh, status = CHI2_REJECTED / atomicAdd(rows_used, 2m) (an integer), and a rejected
 //              feature — or one that did not arrive as USED — leaves its rows of the stack exactly zero.
 // Every sum has a fixed order: two runs on the same inputs return the same bits.
+// k_slam_y<true> adds the projection of single-depth landmarks, feature by feature (the comment at the kernel); k_slam_y<false> is the above.
 #pragma once
 #include "k_featy.h"
 
@@ -50,10 +51,10 @@ constexpr int SLY_INST = 27; // instances per tile row: <= 8 clone + 8 extrinsic
 constexpr int SLY_ISTR = 32; // ints per tile row in the instance table: [0] count, [1 ..] (width << 16) | first column
 
 struct SlamYLds {
-  size_t yb, rows, minfo, hq, stage, inst, misc, total;
+  size_t yb, rows, minfo, hq, stage, inst, misc, vq, hb1, zp, total;
 };
-// m_max: longest track of the batch (<= SLY_MMAX)
-__host__ __device__ inline SlamYLds slamy_lds_layout(int m_max) {
+// m_max: longest track of the batch (<= SLY_MMAX); proj: the carve of k_slam_y<true> (the reflectors V, the saved second bearing column, the partial sums of z)
+__host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = false) {
   SlamYLds L;
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -70,19 +71,33 @@ __host__ __device__ inline SlamYLds slamy_lds_layout(int m_max) {
   L.stage = take((128 + 2 * 256) * sizeof(double)); // the gate's diagonal-tile stage: scratch, E, F
   L.inst = take((size_t)nt * SLY_ISTR * sizeof(int));
   L.misc = take(4 * sizeof(double));
+  L.vq = L.hb1 = L.zp = o;
+  if (proj) {
+    L.vq = take((size_t)2 * m_max * 3 * sizeof(double));      // V of sys_hf_householder: [2 m][3], the third column the unit vector of a column that stays
+    L.hb1 = take((size_t)2 * m_max * sizeof(double));          // H_f[:, 1] as the records gave it (the first reflector is applied to it in place)
+    L.zp = take((size_t)SLY_NW * SLY_CB * sizeof(double));     // V^T Y of the block in four row quarters: [quarter][k][column]
+  }
   L.total = o;
   return L;
 }
 
 #ifndef OVG_TU_FEATY
-__global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
+// PROJ ("with projection"): a feature whose landmark is ANCHORED_INVERSE_DEPTH_SINGLE has its two bearing columns H_b = H_f[:, 0:2] projected out
+// (UpdaterSLAM.cpp:338-341, :371-379; k_system_t's nproj == 2): the records are those of ANCHORED_MSCKF_INVERSE_DEPTH, the landmark's instance is
+// (lm_col, width 1) with the UNREFLECTED depth column H_f[:, 2] — the two reflectors of H_b act on whole rows of [Y | r] afterwards — and per block
+// z = T^T V^T Y (2 x 64 dot products over the 2m rows, four row quarters summed in a fixed order) gives the stack its rows 2 .. 2m-1 of
+// Y - V z as rows 0 .. 2m-3.  The SYRK keeps reading the unprojected block: with S0 = Y Y^T + s_f^2 I the statistic of the projected rows is
+// r^T S0^-1 r - g^T G^-1 g, g = H_b^T S0^-1 r, G = H_b^T S0^-1 H_b — the Schur complement gate_ldl_chi2 returns for R = [r | H_b | 0] with the identity
+// entry at the corner's G22 — against the threshold at dof 2m - 2.  A 3-dof feature of such a batch does what it does in k_slam_y<false>.
+// k_slam_y<false> is the kernel as it was: batches that observe no single-depth landmark take it and return the bits they returned.
+template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NW = SLY_NW, TPW = SLY_TPW, NTH = 64 * SLY_NW, RS = SLY_RS, LS = SLY_LS, CB = SLY_CB;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, cl = lane & 15;
   const int D = p.D, LD = p.LD;
-  const SlamYLds lo = slamy_lds_layout(p.m_max);
+  const SlamYLds lo = slamy_lds_layout(p.m_max, PROJ);
   double *Yb = reinterpret_cast<double *>(smem + lo.yb);
   const int nta_max = (2 * p.m_max + 4 + 15) >> 4;
   double *panel = Yb, *panelx = Yb + (size_t)nta_max * 256;
@@ -93,6 +108,7 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
   int *inst = reinterpret_cast<int *>(smem + lo.inst);
   double *chi2_slot = reinterpret_cast<double *>(smem + lo.misc);
   int *reject_slot = reinterpret_cast<int *>(chi2_slot + 1);
+  double *Vq = reinterpret_cast<double *>(smem + lo.vq), *hb1 = reinterpret_cast<double *>(smem + lo.hb1), *zp = reinterpret_cast<double *>(smem + lo.zp); // PROJ only
   const int nblk = (D + CB - 1) / CB;
 
   for (int slot = p.f_begin + blockIdx.x; slot < p.f_end; slot += gridDim.x) {
@@ -112,7 +128,10 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
     // ------------------------------------------------------------------ (a0) representation Jacobian, as k_system_t (UpdaterHelper.cpp:32-190)
     V3 p_FinG = load_v3(p.p_FinG + 3 * f);
     const int lm_id = p.feat_lm[f], lm_col = p.feat_lmcol[f];
-    const int rep_f = p.lm_rep[lm_id]; // a 3-dof representation: the host keeps batches with a single-depth landmark on the general kernel
+    const int rep_l = p.lm_rep[lm_id]; // <false>: a 3-dof representation — the host keeps batches with a single-depth landmark off this instantiation
+    const bool single = PROJ && rep_l == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE;
+    const int rep_f = single ? OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH : rep_l; // the single depth takes the Jacobians of the MSCKF inverse depth (UpdaterSLAM.cpp:338-341)
+    if (PROJ && single && m < 2) continue; // (no row to give: n_out = 0; k_slam_gather flags such a track OVGPU_FEAT_TOO_FEW_MEAS and it never gets here)
     const bool relative = rep_is_relative(rep_f);
     const double sig2_f = p.feat_sigma ? p.feat_sigma[f] * p.feat_sigma[f] : p.opt.sigma_pix_sq;
     const double mult_f = p.feat_chi2mult ? p.feat_chi2mult[f] : p.opt.chi2_multipler;
@@ -146,8 +165,30 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
     __syncthreads();
     const int anc_ccol = relative ? p.clone_col[anchor_clone] : -1;
     const int anc_pcol = (relative && p.opt.do_calib_pose) ? p.calib_col[anchor_cam] : -1;
-    // the residual column of the stack
-    for (int a = tid; a < n; a += NTH) out[(int64_t)a * LD + D] = oscale * rows[(size_t)(a >> 1) * RS + RO_RES + (a & 1)];
+    if (PROJ && single) {
+      // the two reflectors of H_b and their T by one wavefront, arithmetic as k_system_t's (sys_hf_householder, nproj = 2); it applies the first reflector
+      // to H_f[:, 1] in the records: the column is saved and put back, the gate and nothing else reads H_b afterwards.  z_r = T^T V^T r -> hq[61], hq[62]
+      if (wv == 0) {
+        for (int r = lane; r < n; r += 64) hb1[r] = rows[(size_t)(r >> 1) * RS + RO_HF + 3 * (r & 1) + 1];
+        sys_hf_householder(rows, RS, Vq, hq, n, 2, lane);
+        double y0 = 0.0, y1 = 0.0;
+        for (int r = lane; r < n; r += 64) {
+          const double rr = rows[(size_t)(r >> 1) * RS + RO_RES + (r & 1)];
+          y0 = fma(Vq[(size_t)3 * r], rr, y0), y1 = fma(Vq[(size_t)3 * r + 1], rr, y1);
+        }
+        y0 = wave_sum(y0), y1 = wave_sum(y1);
+        if (lane == 0) hq[61] = hq[3] * y0, hq[62] = hq[4] * y0 + hq[6] * y1;
+        for (int r = lane; r < n; r += 64) rows[(size_t)(r >> 1) * RS + RO_HF + 3 * (r & 1) + 1] = hb1[r];
+      }
+      __syncthreads();
+      // the residual column of the stack: rows 2 .. n-1 of r - V z_r
+      const double zr0 = hq[61], zr1 = hq[62];
+      for (int a = 2 + tid; a < n; a += NTH)
+        out[(int64_t)(a - 2) * LD + D] = oscale * (rows[(size_t)(a >> 1) * RS + RO_RES + (a & 1)] - (Vq[(size_t)3 * a] * zr0 + Vq[(size_t)3 * a + 1] * zr1));
+    } else {
+      // the residual column of the stack
+      for (int a = tid; a < n; a += NTH) out[(int64_t)a * LD + D] = oscale * rows[(size_t)(a >> 1) * RS + RO_RES + (a & 1)];
+    }
     // the instance list of every tile row: the distinct first columns of the blocks its rows touch (blocks are disjoint column ranges: the
     // first column identifies one), in registers; one thread per tile row
     if (tid < NT) {
@@ -164,7 +205,7 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
       }
       cand[24] = anc_ccol >= 0 ? (anc_ccol | (6 << 16)) : -1;
       cand[25] = anc_pcol >= 0 ? (anc_pcol | (6 << 16)) : -1;
-      cand[26] = lm_col >= 0 ? (lm_col | (3 << 16)) : -1;
+      cand[26] = lm_col >= 0 ? (lm_col | ((single ? 1 : 3) << 16)) : -1; // a single depth: its one column carries H_f[:, 2]
       int *il = inst + tid * SLY_ISTR;
       int cnt = 0;
 #pragma unroll
@@ -212,7 +253,7 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
         const double hI0 = rd[RO_CINTR + 8 * par + g], hI1 = rd[RO_CINTR + 8 * par + 4 + g];
         const double hA0 = relative ? rd[RO_ANC + 6 * par + g] : 0.0, hA1 = relative ? rd[RO_ANC + 6 * par + g1] : 0.0;
         const double hQ0 = relative ? rd[RO_ACAL + 6 * par + g] : 0.0, hQ1 = relative ? rd[RO_ACAL + 6 * par + g1] : 0.0;
-        const double hF0 = rd[RO_HF + 3 * par + min(g, 2)];
+        const double hF0 = rd[RO_HF + 3 * par + (single ? 2 : min(g, 2))];
         d4 ay[4];
         bool okc[4];
         int cc[4];
@@ -256,8 +297,22 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
           for (int q = 0; q < 4; q++) Yb[(size_t)(16 * i + g + 4 * q) * LS + 16 * ct + cl] = ay[ct][q];
       }
       lds_barrier();
-      // ---- rows of oscale Y -> the stack
-      {
+      if (PROJ && single) {
+        // ---- V^T Y of the block: wavefront wv takes reflector wv & 1 over the row quarter wv >> 1 (32 rows), lane = column                  | barrier
+        const int k = wv & 1, r0 = 32 * (wv >> 1), r1 = min(r0 + 32, n);
+        double y = 0.0;
+        for (int a = r0; a < r1; a++) y = fma(Vq[(size_t)3 * a + k], Yb[(size_t)a * LS + lane], y);
+        zp[wv * CB + lane] = y;
+        lds_barrier();
+        // ---- rows 2 .. n-1 of oscale (Y - V z), z = T^T V^T Y -> rows 0 .. n-3 of the stack
+        const double y0 = ((zp[lane] + zp[2 * CB + lane]) + zp[4 * CB + lane]) + zp[6 * CB + lane];
+        const double y1 = ((zp[CB + lane] + zp[3 * CB + lane]) + zp[5 * CB + lane]) + zp[7 * CB + lane];
+        const double z0 = hq[3] * y0, z1 = hq[4] * y0 + hq[6] * y1; // T00, T01, T11 (sys_hf_householder)
+        const int c = c_lo + lane;
+        if (c < D)
+          for (int a = 2 + wv; a < n; a += NW) out[(int64_t)(a - 2) * LD + c] = oscale * (Yb[(size_t)a * LS + lane] - (Vq[(size_t)3 * a] * z0 + Vq[(size_t)3 * a + 1] * z1));
+      } else {
+        // ---- rows of oscale Y -> the stack
         const int c = c_lo + lane;
         if (c < D)
           for (int a = wv; a < n; a += NW) out[(int64_t)a * LD + c] = oscale * Yb[(size_t)a * LS + lane];
@@ -292,6 +347,7 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
           double v = acc[s][q];
           if (a == b) v = a < n ? v + sig2_f : ((a >= n4 && a < n4 + 4) ? 0.0 : 1.0);
           else if (a < n && b == n4) v = rows[(size_t)(a >> 1) * RS + RO_RES + (a & 1)];
+          else if (PROJ && single && a < n && (b == n4 + 1 || b == n4 + 2)) v = rows[(size_t)(a >> 1) * RS + RO_HF + 3 * (a & 1) + b - n4 - 1]; // H_b
           acc[s][q] = v;
         }
       } else if (TI(s) == TJ(s)) {
@@ -300,9 +356,9 @@ __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
           if (g + 4 * q == cl) acc[s][q] += sig2_f;
       }
     }
-    const double chi2 = feat::gate_ldl_chi2<NW, TPW, true>(acc, tij, NT, NTA, n, panel, panelx, st0, stE, stF, chi2_slot, lane, wv);
+    const double chi2 = feat::gate_ldl_chi2<NW, TPW, PROJ ? 2 : 1>(acc, tij, NT, NTA, n, panel, panelx, st0, stE, stF, chi2_slot, lane, wv, single);
     if (tid == 0) {
-      const double thr = mult_f * p.chi2_table[min(n, p.chi2_table_len - 1)]; // UpdaterSLAM.cpp:392-405: dof = 2m
+      const double thr = mult_f * p.chi2_table[min(single ? n - 2 : n, p.chi2_table_len - 1)]; // UpdaterSLAM.cpp:392-405: dof = 2m (2m - 2 behind the projection)
       p.chi2[f] = chi2;
       p.chi2_thresh[f] = thr;
       const bool reject = chi2 > thr;

@@ -3,7 +3,8 @@ kernel of the headline shape (feat::k_feat_y<4, 11, 2>, both stack precisions) a
 in the tree and stores every output; `compare <a.npz> <b.npz>` compares two such files bit for bit.  Used when a build changes
 nothing but instruction ORDER (a scheduler strategy, ovgpu_featy_tu.hip): no tolerance applies, and no oracle time is spent
 (tools/gpu_bitcompare.sh swaps the library files on one box).  `dump` also runs the entries that read the resident feature batch on
-small seeded landmark states (batch_scenarios below): used when a change is meant to touch host code only."""
+small seeded landmark states (batch_scenarios below): used when a change is meant to touch host code only.  `fused <out.npz> <level>` runs
+SLAM updates with ovgpu_debug_option "slam_fused" at that level (fused_scenarios below): two builds must agree bit for bit at a level both know."""
 import sys
 
 import numpy as np
@@ -124,6 +125,28 @@ def batch_scenarios(out):
     print("batch scenarios:", len(out) - n0, "arrays", flush=True)
 
 
+def fused_scenarios(path, level):
+    """ovgpu_slam_update and ovgpu_slam_update_chunked with "slam_fused" = level: fifteen landmarks of the five 3-dof representations (every batch
+    takes k_slam_y<false> from level 1 on), and twelve of all six (k_system_t at level 1, k_slam_y<true> at level 2)."""
+    from open_vins_amd import capi, synth
+    from open_vins_amd.updater import UpdaterMSCKF
+    opts = capi.default_options(chi2_multipler=1.0)
+    out = {}
+    for tag, reps in (("3dof", (0, 1, 2, 3, 4) * 3), ("six", REPS6 * 2)):
+        p = synth.make_slam_problem(2, L=len(reps), lm_rep=np.array(reps, np.int32), seed=3)
+        for entry in ("update", "chunked"):
+            up = UpdaterMSCKF(opts, device=0)
+            up.debug_option("slam_fused", level)
+            up.set_slam_problem(p)
+            res = up.slam_update() if entry == "update" else up.slam_update_chunked(p.lm_index, [0, 5, 5, p.F])
+            res.update(up.get_state(P=False))
+            res["kernel"], res["fused_batches"] = up.debug_option("last_feature_kernel"), up.debug_option("slam_fused_batches")
+            put(out, f"{tag}.{entry}", res)
+            print(tag, entry, "level", level, "kernel", res["kernel"], "fused pipelines", res["fused_batches"], flush=True)
+            up.close()
+    np.savez(path, **out)
+
+
 def prepare(path):
     """The problems are generated once (CPU work: here, not on the GPU box's clock) and travel as a pickle."""
     import pickle
@@ -184,6 +207,8 @@ def compare(a, b):
 if __name__ == "__main__":
     if sys.argv[1] == "prepare":
         prepare(sys.argv[2])
+    elif sys.argv[1] == "fused":
+        fused_scenarios(sys.argv[2], int(sys.argv[3]))
     elif sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     else:

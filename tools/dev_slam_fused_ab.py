@@ -1,19 +1,22 @@
 """What the fused per-feature kernel of the SLAM update (csrc/k_slam_y.h, ovgpu_debug_option "slam_fused") is worth: the tree's library against
 another build of it on one box.
 
-    time [--reps 30] [--rounds 3] [--lib-a PATH] [--tag NAME] [--tag-a NAME] [--cases slam,chunked] [--out FILE.jsonl]
+    time [--reps 30] [--rounds 3] [--lib-a PATH] [--tag NAME] [--tag-a NAME] [--cases slam,chunked] [--state 3dof|mixed] [--level-a1 0] [--level-b 1] [--out FILE.jsonl]
                     leg A runs on the library --lib-a names (the parent commit's build; without it: the tree's with the switch untouched), leg A' on
-                    the tree's with "slam_fused" = 0, leg B on the tree's with "slam_fused" = 1.  A case whose leg B counted no fused pipeline
-                    ("slam_fused_batches") or whose other legs counted one is an error, not a row.  Cases, timed host to host:
+                    the tree's with "slam_fused" = --level-a1 (0), leg B on the tree's with "slam_fused" = --level-b (1): the switch is a level, an
+                    integer.  A leg whose count of fused pipelines ("slam_fused_batches") is not what its level and the state say — some at level 1
+                    on the 3-dof state and at level 2 on either, none otherwise — is an error, not a row.  Cases, timed host to host:
                       slam     ovgpu_slam_update, 30 clones stereo, L = 50 landmarks of the five 3-dof representations in turn, a batch of 25 features
                                under their own active set (D = 283); ovgpu_set_active_landmarks / ovgpu_set_features are part of the frame, the state
                                upload is not; ms_total of the last frame is recorded next to the host-to-host time
                       chunked  ovgpu_slam_update_chunked, L = 100, a batch of 100 in four chunks of 25 (ovgpu_set_features is part of the frame)
-                    (DESIGN.md section 7's rows hold a single-depth landmark in every sixth place; a batch that holds one keeps the general kernel as
-                    a whole, so the landmarks here are the five 3-dof representations: 3 more columns per former single-depth landmark.)
+                    (DESIGN.md section 7's rows hold a single-depth landmark in every sixth place; at level 1 a batch that holds one keeps the general
+                    kernel as a whole, so the landmarks of --state 3dof are the five 3-dof representations: 3 more columns per former single-depth
+                    landmark.  --state mixed is the table's own state, the six representations in turn: --level-a1 1 --level-b 2 times the parent's
+                    library, this one at level 1 — k_system_t, as the parent — and this one at level 2, k_slam_y<true>.)
                     The legs take turns frame by frame, `rounds` repetitions of `reps` frames; a row per (case, leg) with the median of every
                     round, the median of those and their spread (max - min), and a summary row: A' against A's spread, A - B against the largest spread.
-    trace [--case slam] [--leg B] [--calls 10] [--lib-a PATH]
+    trace [--case slam] [--leg B] [--calls 10] [--lib-a PATH] [--state 3dof|mixed] [--level-a1 0] [--level-b 1]
                     the frames of one leg alone, for a rocprofv3 --kernel-trace --stats run of its own"""
 import argparse
 import ctypes as C
@@ -49,19 +52,22 @@ def bind(capi, path):
 class Leg:
     """one context and its frame: prepare() is not timed, frame() is"""
 
-    def __init__(self, capi, synth, lib, case, kind, fused):
-        """fused: 1 / 0 sets "slam_fused", None leaves the library alone (another build, which does not know the name)"""
+    def __init__(self, capi, synth, lib, case, kind, fused, state="3dof"):
+        """fused: an integer sets "slam_fused" to that level, None leaves the library alone (another build, which may not know the name)"""
         self.lib, self.kind, self.case, self.ctx = lib, kind, case, C.c_void_p()
         opts = capi.default_options(chi2_multipler=1.0)
         assert lib.ovgpu_create(C.byref(opts), 0, C.byref(self.ctx)) == 0
         self.knows = fused is not None
+        self.expect_fused = fused is not None and (fused >= 2 or (fused >= 1 and state == "3dof"))
         if fused is not None:
             self.ok(lib.ovgpu_debug_option(self.ctx, b"slam_fused", int(fused), None), "ovgpu_debug_option")
         self.ip = lambda a: a.ctypes.data_as(capi.c_int32_p)
         self.dp = lambda a: a.ctypes.data_as(capi.c_double_p)
         L, F = (50, 25) if case == "slam" else (100, 100)
         reps5 = [capi.REP_GLOBAL_3D, capi.REP_ANCHORED_3D, capi.REP_GLOBAL_FULL_INVERSE_DEPTH, capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, capi.REP_ANCHORED_FULL_INVERSE_DEPTH]
-        reps = np.array((reps5 * ((L + 4) // 5))[:L], np.int32)
+        reps6 = [capi.REP_GLOBAL_3D, capi.REP_ANCHORED_3D, capi.REP_GLOBAL_3D, capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, capi.REP_GLOBAL_FULL_INVERSE_DEPTH,
+                 capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE]  # DESIGN.md section 7's rows (tools/dev_chol_wide_ab.py, tools/dev_slam_chunked_ab.py)
+        reps = np.array((reps5 * ((L + 4) // 5))[:L] if state == "3dof" else (reps6 * ((L + 5) // 6))[:L], np.int32)
         full = synth.make_slam_problem(2, L=L, lm_rep=reps, seed=3)
         prob = full.subset(np.arange(F))
         prob.lm_index = np.ascontiguousarray(np.arange(F), dtype=np.int32)
@@ -117,7 +123,7 @@ def make_legs(a, case, which=LEGS):
     import torch  # noqa: F401  (capi.load: torch's HIP runtime first)
     from open_vins_amd import capi, synth
     lib, lib_a = capi.load(), bind(capi, a.lib_a)
-    return {k: Leg(capi, synth, lib_a if k == "A" else lib, case, k, fused={"A": None, "A'": 0, "B": 1}[k]) for k in which}
+    return {k: Leg(capi, synth, lib_a if k == "A" else lib, case, k, fused={"A": None, "A'": a.level_a1, "B": a.level_b}[k], state=a.state) for k in which}
 
 
 def spread(v):
@@ -143,10 +149,10 @@ def timed(a):
                 med[k].append(float(np.median(t[k])))
         A, A1, B = legs["A"], legs["A'"], legs["B"]
         counts = {k: leg.fused_count() for k, leg in legs.items()}
-        if counts["B"] == 0 or counts["A"] or counts["A'"]:
+        if any((counts[k] > 0) != leg.expect_fused for k, leg in legs.items()):
             raise RuntimeError(f"case {case}: fused pipelines per leg {counts} — nothing was compared")
         for k, leg in legs.items():
-            row = dict(case=case, leg=k, D=leg.D, build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k],
+            row = dict(case=case, state=a.state, leg=k, level=({"A": None, "A'": a.level_a1, "B": a.level_b}[k]), D=leg.D, build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k],
                        ms_median=float(np.median(med[k])), ms_spread=spread(med[k]), fused_pipelines=counts[k])
             if case == "slam":
                 row["ms_total_device"], row["n_used"] = float(leg.stats.ms_total), int(leg.stats.n_used)
@@ -156,7 +162,7 @@ def timed(a):
             print(json.dumps(row), flush=True)
         mA, mA1, mB = (float(np.median(med[k])) for k in LEGS)
         big = max(spread(med["A"]), spread(med["B"]))
-        row = dict(case=case + "_summary", D=B.D, A_minus_A1_ms=mA - mA1, spread_of_A_ms=spread(med["A"]), A1_within_the_spread_of_A=bool(abs(mA - mA1) <= spread(med["A"])),
+        row = dict(case=case + "_summary", state=a.state, D=B.D, A_minus_A1_ms=mA - mA1, spread_of_A_ms=spread(med["A"]), A1_within_the_spread_of_A=bool(abs(mA - mA1) <= spread(med["A"])),
                    A_minus_B_ms=mA - mB, largest_spread_of_A_and_B_ms=big, B_faster_than_A_by_more_than_the_spread=bool(mA - mB > big),
                    dx_rel_A_to_B=float(np.linalg.norm(A.dx - B.dx) / max(np.linalg.norm(B.dx), 1e-300)), P_rel_A_to_B=float(np.linalg.norm(A.P - B.P) / np.linalg.norm(B.P)),
                    A1_equals_A_bitwise=bool(np.array_equal(A.dx, A1.dx) and np.array_equal(A.P, A1.P)))
@@ -176,7 +182,7 @@ def trace(a):
         leg.prepare()
         leg.frame()
     n = leg.fused_count()
-    if (n > 0) != (a.leg == "B"):
+    if (n > 0) != leg.expect_fused:
         raise RuntimeError(f"leg {a.leg} counted {n} fused pipelines")
     print(f"{a.calls} frames of leg {a.leg}, case {a.case}, D = {leg.D}, {n} fused pipelines")
     leg.close()
@@ -198,6 +204,10 @@ def main():
     r.add_argument("--leg", choices=LEGS, default="B")
     r.add_argument("--calls", type=int, default=10)
     r.add_argument("--lib-a", default=None)
+    for q in (t, r):
+        q.add_argument("--state", choices=("3dof", "mixed"), default="3dof")
+        q.add_argument("--level-a1", type=int, default=0)
+        q.add_argument("--level-b", type=int, default=1)
     a = ap.parse_args()
     {"time": timed, "trace": trace}[a.cmd](a)
 
