@@ -1202,6 +1202,12 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
  *                             (k_slam_y<false>: no single-depth landmark observed), 5 k_slam_y<true>, the same kernel with the projection of
  *                             single-depth landmarks ("slam_fused" = 2)
+ *   "sys_lds_limit" / "sys_m_lds_max" / "sys_rows_global" / "sys_row_stride" / "sys_lds_bytes"  (read only) the general per-feature kernel's
+ *                             LDS carve for the batch in force, as sized with the last ovgpu_set_features (or the entry point that laid the batch out):
+ *                             the byte limit of a workgroup's LDS; the largest track length whose gate matrix is LDS-resident (longer tracks of
+ *                             the batch keep theirs in a per-workgroup global workspace); 1 when the Jacobian records of a feature live in a global
+ *                             workspace too (k_system_t<true>: the longest track's records do not fit LDS next to the T chunk), else 0; the doubles
+ *                             per Jacobian record (48; 72 once an anchored representation is in force); the launch's dynamic LDS size in bytes
  *   "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel"  (read only) what the last batch pipeline launched: the Gram kernel (0 none,
  *                             1 the one-pass kernel, 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32); mode A's pivoted factor (0 none: the
  *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB the rank-one k_gram_pchol<NB>);

@@ -117,6 +117,16 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->tsqr_last_tree;
   } else if (n == "tsqr_last_qh") { // 16 / 28 / 32: quads per register array of the merge kernels; 0: k_qr_append, or no merge
     if (old_value) *old_value = c->tsqr_last_qh;
+  } else if (n == "sys_lds_limit") { // read-only, this and the four below: the general per-feature kernel's LDS carve for the batch in force (size_feature_stage, api_state.inc) — the byte limit it was carved under
+    if (old_value) *old_value = c->lds_limit;
+  } else if (n == "sys_m_lds_max") { // the largest track length whose gate matrix is LDS-resident; longer tracks of the batch keep theirs in the per-workgroup global workspace
+    if (old_value) *old_value = c->m_lds_max;
+  } else if (n == "sys_rows_global") { // 1: the Jacobian records live in a global workspace (k_system_t<true>), 0: in LDS
+    if (old_value) *old_value = c->sys_rows_global ? 1 : 0;
+  } else if (n == "sys_row_stride") { // doubles per Jacobian record: 48, or 72 once an anchored representation is in force
+    if (old_value) *old_value = c->row_stride;
+  } else if (n == "sys_lds_bytes") { // the dynamic LDS size of the kernel's launch
+    if (old_value) *old_value = (int64_t)c->sys_lds_bytes;
   } else if (n == "chol_timeouts") { // read-only counter: updates repeated with the step-wise Cholesky after a follower timed out
     if (old_value) *old_value = c->chol_timeouts;
   } else {

@@ -1691,7 +1691,7 @@ def test_tracks_beyond_254_observations_are_gated(Updater, oracle):
     panel routine held 512 rows: OVGPU_ERR_CAPACITY): now the panel takes the trapezoid 512 rows at a time (k_system.h) and the
     statistic, the threshold and the update are the oracle's."""
     prob = synth.make_problem(2, F=3)
-    q = _with_a_long_first_track(prob, 280)  # (the row store of the general kernel: 160 KB of LDS hold ~290 records next to a 208-column chunk)
+    q = _with_a_long_first_track(prob, 280)  # (the row store of the general kernel: 160 KB of LDS hold 294 records of 48 doubles next to a 208-column chunk, tests/system_shapes.py)
     out, ref = _check_given(Updater, oracle, q, capi.default_options(chi2_multipler=1.0, gate_always_factor=1), tol_dx=1e-7, tol_p=1e-8)
     assert np.isfinite(out["chi2"][0]) and out["chi2_thresh"][0] > 600.0  # chi2_95(557) = 613.0: beyond the reference's table of 500
 
