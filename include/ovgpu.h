@@ -574,7 +574,8 @@ int ovgpu_set_active_landmarks(ovgpu_ctx *ctx, int32_t n, const int32_t *lm_inde
  * longest track holds at most 62 measurements takes its per-feature stage as ONE fused kernel
  * (S0 = Y Y^T + sigma^2 I from the whitened rows Y = H L the stack holds anyway): the same update to
  * rounding, this entry and ovgpu_slam_update_chunked alike.  At level 2 a batch that observes
- * single-depth landmarks takes it as well (the bearing's projection inside the same kernel).  */
+ * single-depth landmarks takes it as well (the bearing's projection inside the same kernel); at
+ * level 3 so does a batch whose longest track holds 63 to 126 measurements.  */
 int ovgpu_slam_update(ovgpu_ctx *ctx, const int32_t *lm_index, int32_t *feat_status,
                       double *chi2, double *chi2_thresh, double *dx, double *P_out,
                       double *lm_out, ovgpu_update_stats *stats);
@@ -1201,7 +1202,8 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one,
  *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
  *                             (k_slam_y<false>: no single-depth landmark observed), 5 k_slam_y<true>, the same kernel with the projection of
- *                             single-depth landmarks ("slam_fused" = 2)
+ *                             single-depth landmarks ("slam_fused" = 2), 6 / 7 the long shapes of k_slam_y<false> / k_slam_y<true>: a batch whose
+ *                             longest track holds 63 to 126 measurements ("slam_fused" = 3)
  *   "sys_lds_limit" / "sys_m_lds_max" / "sys_rows_global" / "sys_row_stride" / "sys_lds_bytes"  (read only) the general per-feature kernel's
  *                             LDS carve for the batch in force, as sized with the last ovgpu_set_features (or the entry point that laid the batch out):
  *                             the byte limit of a workgroup's LDS; the largest track length whose gate matrix is LDS-resident (longer tracks of
@@ -1212,7 +1214,7 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             1 the one-pass kernel, 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32); mode A's pivoted factor (0 none: the
  *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB the rank-one k_gram_pchol<NB>);
  *                             mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>): the rule at ovgpu_msckf_compress
- *   "slam_fused"              (default 0) a level; the read-back returns it (values above 2 are taken as 2).
+ *   "slam_fused"              (default 0) a level; the read-back returns it (values above 3 are taken as 3).
  *                             1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
  *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every
  *                             landmark the batch observes is 3-dof, its longest track holds at most 62 measurements, 16 <= D, K C <= 8192,
@@ -1225,7 +1227,13 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             whitened route): per feature of such a landmark the two reflectors of its bearing columns are applied to the rows
  *                             of [Y | r] on their way to the stack (2m - 2 rows) and the gate is r^T S0^-1 r - g^T G^-1 g at dof 2m - 2, from the
  *                             same sweep; a batch that observes none takes k_slam_y<false> as at level 1, with the same bits.  The fall-backs
- *                             of level 1 stay.  Takes effect with the next ovgpu_set_features (a batch over landmarks of both sizes is laid out
+ *                             of level 1 stay.
+ *                             3: level 2, and a batch whose longest track holds 63 to 126 measurements takes the long shape of the kernel — the
+ *                             same algebra on 16 tile rows of the gate matrix (2 m + 4 <= 256 rows) and column blocks of 32 — when the remaining
+ *                             terms hold (16 <= D, K C <= 8192, no_fast_feature_kernel 0, the whitened route, its LDS carve within the workgroup's
+ *                             limit): "last_feature_kernel" 6 without, 7 with a single-depth landmark observed.  A batch of at most 62 takes the
+ *                             shapes of level 2 with their bits (4 / 5); 127 measurements and beyond, and every fall-back of levels 1 and 2, keep
+ *                             the general kernel.  Takes effect with the next ovgpu_set_features (a batch over landmarks of both sizes is laid out
  *                             again when a SLAM call names its landmarks: the level in force at that call decides)
  *   "slam_fused_batches"      counter: batch pipelines that took k_slam_y (either instantiation), once per update — the pipelines of an attempt the library repeats (through the
  *                             Householder route after a failed prior pivot, with the step-wise Cholesky after a time-out) are not counted; a value >= 0 sets it

@@ -203,13 +203,14 @@ struct ovgpu_ctx {
   // is a landmark-free state's and so is every kernel of the MSCKF update
   bool lm_empty_set = false;      // L > 0 and ovgpu_set_active_landmarks(ctx, NULL, 0) holds (layout_columns)
   bool lm_fast_ok = false;        // ... and the resident batch was laid out for the fused per-feature kernels under it (set_row_layout)
-  int last_feat_kernel = 0;       // per-feature kernel of the last batch pipeline: 0 the general one (k_system.h), else the fused shape that ran (feat_variant; 4: k_slam_y<false>, 5: k_slam_y<true>)
+  int last_feat_kernel = 0;       // per-feature kernel of the last batch pipeline: 0 the general one (k_system.h), else the fused shape that ran (feat_variant; 4: k_slam_y<false>, 5: k_slam_y<true>; 6 / 7: their long shapes, 63 .. 126 observations)
   bool anchored_fast = true;      // ovgpu_debug_option "anchored_fast": batches of an anchored feat_rep_msckf are laid out for the fused per-feature kernels too (set_row_layout)
   bool lm_fast_on = false;        // ovgpu_msckf_update_lm is running: the one entry that takes them with landmarks resident (enqueue_system)
   // the fused per-feature kernel of UpdaterSLAM::update (k_slam_y.h), behind a switch that is off by default
-  int slam_fused = 0;             // ovgpu_debug_option "slam_fused", a level: 0 off; 1 SLAM batches whose observed landmarks are all 3-dof are laid out for k_slam_y<false>; 2 also the ones that observe a single-depth landmark, for k_slam_y<true> (size_feature_stage)
-  bool slam_fused_ok = false;     // ... and the batch in force is one it holds: the landmarks observed as the level asks, longest track <= SLY_MMAX, D >= 16, K C <= 8192
-  bool slam_fused_proj = false;   // ... with a single-depth landmark among them: k_slam_y<true> and its LDS carve (level 2 only)
+  int slam_fused = 0;             // ovgpu_debug_option "slam_fused", a level: 0 off; 1 SLAM batches whose observed landmarks are all 3-dof are laid out for k_slam_y<false>; 2 also the ones that observe a single-depth landmark, for k_slam_y<true>; 3 also the batches whose longest track holds 63 .. 126 observations, for the long shapes (size_feature_stage)
+  bool slam_fused_ok = false;     // ... and the batch in force is one it holds: the landmarks observed as the level asks, longest track <= SLY_MMAX (SLY_MMAX_L at level 3), D >= 16, K C <= 8192
+  bool slam_fused_proj = false;   // ... with a single-depth landmark among them: k_slam_y<true> and its LDS carve (levels 2 and 3)
+  bool slam_fused_long = false;   // ... with a track of 63 .. 126 observations: the long shape k_slam_y<.., 17, 32, 126> and its carve (level 3 only)
   size_t slamy_lds = 0;           // its LDS bytes for the batch in force
   int64_t slam_fused_batches = 0; // ovgpu_debug_option "slam_fused_batches": pipelines that took k_slam_y, counted once per update: the pipelines of an attempt that update_with_fallbacks repeats (Householder route, step-wise Cholesky) are taken off again
   int slam_fused_attempt = 0;     // ... of them, the ones of the update attempt that is running (update_with_fallbacks)

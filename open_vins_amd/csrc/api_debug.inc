@@ -41,9 +41,9 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "anchored_fast") { // 0: batches of an anchored feat_rep_msckf keep the general kernel (the routing before k_feat_rows_anchored); takes effect with the next ovgpu_set_features
     if (old_value) *old_value = c->anchored_fast ? 1 : 0;
     if (value >= 0) c->anchored_fast = value != 0;
-  } else if (n == "slam_fused") { // a level.  1: SLAM batches of 3-dof landmarks take the fused per-feature kernel k_slam_y<false> on the whitened route (k_slam_y.h); 2 (and above): batches that observe a single-depth landmark take k_slam_y<true> as well; default 0; reads back the level; takes effect with the next ovgpu_set_features
+  } else if (n == "slam_fused") { // a level.  1: SLAM batches of 3-dof landmarks take the fused per-feature kernel k_slam_y<false> on the whitened route (k_slam_y.h); 2: batches that observe a single-depth landmark take k_slam_y<true> as well; 3 (and above): batches whose longest track holds 63 .. 126 observations take the long shapes as well; default 0; reads back the level; takes effect with the next ovgpu_set_features
     if (old_value) *old_value = c->slam_fused;
-    if (value >= 0) c->slam_fused = (int)std::min<int64_t>(value, 2);
+    if (value >= 0) c->slam_fused = (int)std::min<int64_t>(value, 3);
   } else if (n == "slam_fused_batches") { // reads the count of batch pipelines that took k_slam_y, once per update (the pipelines of a repeated attempt — Householder route, step-wise Cholesky — are not counted); a value >= 0 sets it
     if (old_value) *old_value = c->slam_fused_batches;
     if (value >= 0) c->slam_fused_batches = value;
@@ -93,7 +93,7 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = t;
   } else if (n == "stack_is_f32") { // read-only: the last pipeline stored the stack as floats and ran k_gram_f32 (options.gram_fp32)
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
-  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big, 4 k_slam_y<false> / 5 k_slam_y<true>, with the projection of single-depth landmarks (SLAM batches under "slam_fused")
+  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big, 4 k_slam_y<false> / 5 k_slam_y<true>, with the projection of single-depth landmarks (SLAM batches under "slam_fused"), 6 / 7 the long shapes of the two (63 .. 126 observations, "slam_fused" = 3)
     if (old_value) *old_value = c->last_feat_kernel;
   } else if (n == "last_gram_kernel") { // read-only, this and the two below: what the last batch pipeline launched (api_context.inc lists the codes)
     if (old_value) *old_value = c->last_gram_kernel;

@@ -192,12 +192,19 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     if (!attr_s) {
       (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
       (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
       attr_s = true;
     }
-    if (p.m_max > slamy::SLY_MMAX || c->slamy_lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_INVALID, "internal: k_slam_y was selected for a batch it does not hold");
-    c->last_feat_kernel = c->slam_fused_proj ? 5 : 4, c->slam_fused_batches++, c->slam_fused_attempt++;
-    if (c->slam_fused_proj) hipLaunchKernelGGL(slamy::k_slam_y<true>, dim3(std::max(1, std::min(b.F, c->num_cu))), dim3(64 * slamy::SLY_NW), c->slamy_lds, c->stream, p);
-    else hipLaunchKernelGGL(slamy::k_slam_y<false>, dim3(std::max(1, std::min(b.F, c->num_cu))), dim3(64 * slamy::SLY_NW), c->slamy_lds, c->stream, p);
+    const bool lng = c->slam_fused_long;
+    const dim3 sgrid(std::max(1, std::min(b.F, c->num_cu))), sblock(64 * slamy::SLY_NW);
+    if (p.m_max > (lng ? slamy::SLY_MMAX_L : slamy::SLY_MMAX) || (lng && p.m_max <= slamy::SLY_MMAX) ||
+        slamy::slamy_lds_layout(p.m_max, c->slam_fused_proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total > c->slamy_lds || c->slamy_lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_INVALID, "internal: k_slam_y was selected for a batch it does not hold");
+    c->last_feat_kernel = (lng ? 6 : 4) + (c->slam_fused_proj ? 1 : 0), c->slam_fused_batches++, c->slam_fused_attempt++;
+    if (lng && c->slam_fused_proj) hipLaunchKernelGGL((slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>), sgrid, sblock, c->slamy_lds, c->stream, p);
+    else if (lng) hipLaunchKernelGGL((slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>), sgrid, sblock, c->slamy_lds, c->stream, p);
+    else if (c->slam_fused_proj) hipLaunchKernelGGL(slamy::k_slam_y<true>, sgrid, sblock, c->slamy_lds, c->stream, p);
+    else hipLaunchKernelGGL(slamy::k_slam_y<false>, sgrid, sblock, c->slamy_lds, c->stream, p);
     HIPCHK(hipGetLastError());
     return OVGPU_OK;
   }

@@ -661,8 +661,11 @@ static int size_feature_stage(ovgpu_ctx *c) {
   // observes a single-depth landmark takes k_slam_y<true>, the instantiation with the projection, on the same terms and its own LDS carve; a
   // batch that observes none takes k_slam_y<false> as at level 1.  A batch of a mixed-dof state whose landmarks are not named yet is laid out
   // again once they are (slam_prepare).  Per-feature sigma / multiplier do not disqualify (ArUco corners).
-  c->slam_fused_ok = false, c->slam_fused_proj = false, c->slamy_lds = 0;
-  if (slam_rows && c->slam_fused && !c->no_feat_kernel && c->L > 0 && m_max <= slamy::SLY_MMAX && c->D >= 16 && c->K * c->C <= 8192) {
+  // Level 3 is level 2 with one addition: a batch whose longest track holds 63 .. 126 observations takes the long shape (16 tile rows, column
+  // blocks of 32) on the same terms and its own carve; a batch of at most 62 takes the shapes of level 2.
+  c->slam_fused_ok = false, c->slam_fused_proj = false, c->slam_fused_long = false, c->slamy_lds = 0;
+  const int slamy_mmax = c->slam_fused >= 3 ? slamy::SLY_MMAX_L : slamy::SLY_MMAX;
+  if (slam_rows && c->slam_fused && !c->no_feat_kernel && c->L > 0 && m_max <= slamy_mmax && c->D >= 16 && c->K * c->C <= 8192) {
     const int udof = lm_uniform_dof(c);
     bool dof3 = udof == 3, named = udof != 0;
     if (udof == 0 && (int)b.h_feat_lm.size() == F) {
@@ -670,8 +673,9 @@ static int size_feature_stage(ovgpu_ctx *c) {
       for (int f = 0; f < F; f++) dof3 = dof3 && lm_dof(c->h_lm_rep[b.h_feat_lm[f]]) == 3;
     }
     const bool proj = named && !dof3 && c->slam_fused >= 2;
-    const size_t lds = slamy::slamy_lds_layout(std::max(m_max, 1), proj).total;
-    if ((dof3 || proj) && lds <= (size_t)c->lds_limit) c->slam_fused_ok = true, c->slam_fused_proj = proj, c->slamy_lds = lds;
+    const bool lng = m_max > slamy::SLY_MMAX;
+    const size_t lds = slamy::slamy_lds_layout(std::max(m_max, 1), proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total;
+    if ((dof3 || proj) && lds <= (size_t)c->lds_limit) c->slam_fused_ok = true, c->slam_fused_proj = proj, c->slam_fused_long = lng, c->slamy_lds = lds;
   }
   if (c->feat_variant) { // row store of the fast path
     const int M = std::max(b.M, 1);

@@ -32,6 +32,8 @@
 //              feature — or one that did not arrive as USED — leaves its rows of the stack exactly zero.
 // Every sum has a fixed order: two runs on the same inputs return the same bits.
 // k_slam_y<true> adds the projection of single-depth landmarks, feature by feature (the comment at the kernel); k_slam_y<false> is the above.
+// Two shapes (the template parameters at the kernel): tracks of up to 62 observations on 8 tile rows of the gate matrix and blocks of 64 columns, as described
+// above; tracks of 63 .. 126 on 16 tile rows and blocks of 32 columns ("slam_fused" = 3), where a wavefront holds two rows of the block per pass of a store.
 #pragma once
 #include "k_featy.h"
 
@@ -41,20 +43,25 @@ namespace slamy {
 using feat::d4;
 using feat::lds_barrier;
 
-constexpr int SLY_MMAX = 62; // the longest track the kernel holds: 2 m + 4 rows of the augmented gate matrix in 8 tile rows, 36 tiles of its upper triangle
+constexpr int SLY_MMAX = 62; // the longest track the short shape holds: 2 m + 4 rows of the augmented gate matrix in 8 tile rows, 36 tiles of its upper triangle
 constexpr int SLY_NW = 8;    // wavefronts per workgroup: one tile row of the sweep each at the bound
 constexpr int SLY_TPW = 5;   // gate tiles per wavefront: 36 <= 8 x 5
 constexpr int SLY_RS = 72;   // doubles per record (RO_* of k_system.h, anchor blocks included)
 constexpr int SLY_CB = 64;   // columns per block
-constexpr int SLY_LS = SLY_CB + 2;
+// the long shape, 63 .. 126 observations: 16 tile rows, 136 tiles of the upper triangle (feat::gate_ldl_chi2<8, 17, ..>, the template k_feat_y<8, 17, 1>
+// instantiates), column blocks of 32 — the block of Y and the records of 126 measurements do not fit LDS side by side at 64
+constexpr int SLY_MMAX_L = 126;
+constexpr int SLY_TPW_L = 17; // 136 = 8 x 17
+constexpr int SLY_CB_L = 32;
 constexpr int SLY_INST = 27; // instances per tile row: <= 8 clone + 8 extrinsic + 8 intrinsic blocks, anchor clone, anchor extrinsics, landmark
 constexpr int SLY_ISTR = 32; // ints per tile row in the instance table: [0] count, [1 ..] (width << 16) | first column
 
 struct SlamYLds {
   size_t yb, rows, minfo, hq, stage, inst, misc, vq, hb1, zp, total;
 };
-// m_max: longest track of the batch (<= SLY_MMAX); proj: the carve of k_slam_y<true> (the reflectors V, the saved second bearing column, the partial sums of z)
-__host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = false) {
+// m_max: longest track of the batch (<= SLY_MMAX at cb = SLY_CB, <= SLY_MMAX_L at cb = SLY_CB_L); proj: the carve with the projection (the reflectors V, the
+// saved second bearing column, the partial sums of z); cb: columns per block.  The single source of the carve for host and device.
+__host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = false, int cb = SLY_CB) {
   SlamYLds L;
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -63,7 +70,7 @@ __host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = fals
     return at;
   };
   const int nt = (2 * m_max + 15) >> 4, nta = (2 * m_max + 4 + 15) >> 4;
-  const size_t blk = (size_t)16 * nt * SLY_LS * sizeof(double), pan = (size_t)2 * nta * 256 * sizeof(double);
+  const size_t blk = (size_t)16 * nt * (cb + 2) * sizeof(double), pan = (size_t)2 * nta * 256 * sizeof(double);
   L.yb = take(blk > pan ? blk : pan); // the block of Y; afterwards the gate's row panel, twice
   L.rows = take((size_t)m_max * SLY_RS * sizeof(double));
   L.minfo = take((size_t)m_max * 8 * sizeof(int));
@@ -75,7 +82,11 @@ __host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = fals
   if (proj) {
     L.vq = take((size_t)2 * m_max * 3 * sizeof(double));      // V of sys_hf_householder: [2 m][3], the third column the unit vector of a column that stays
     L.hb1 = take((size_t)2 * m_max * sizeof(double));          // H_f[:, 1] as the records gave it (the first reflector is applied to it in place)
-    L.zp = take((size_t)SLY_NW * SLY_CB * sizeof(double));     // V^T Y of the block in four row quarters: [quarter][k][column]
+    // V^T Y of the block: [quarter][k][column] in four row quarters at 64 columns; [wavefront][k][column] in eight segments of 32 rows at 32 columns — 4096 bytes
+    // either way.  The long shape has no room for them next to the records (224 bytes over the limit at 126 observations): zp lives inside the column-block
+    // loop only and the gate's stage behind it only, they share the stage's space.
+    if (cb == SLY_CB) L.zp = take((size_t)SLY_NW * SLY_CB * sizeof(double));
+    else L.zp = L.stage;
   }
   L.total = o;
   return L;
@@ -90,14 +101,23 @@ __host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = fals
 // r^T S0^-1 r - g^T G^-1 g, g = H_b^T S0^-1 r, G = H_b^T S0^-1 H_b — the Schur complement gate_ldl_chi2 returns for R = [r | H_b | 0] with the identity
 // entry at the corner's G22 — against the threshold at dof 2m - 2.  A 3-dof feature of such a batch does what it does in k_slam_y<false>.
 // k_slam_y<false> is the kernel as it was: batches that observe no single-depth landmark take it and return the bits they returned.
-template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
+// TPW / CB / MMAX: the shape — <.., 5, 64, 62> as it was, <.., 17, 32, 126> the long one (the same algebra and the same order of every sum a track of either
+// shape takes, except z's partial sums, eight segments of 32 rows where the short shape has four quarters).  At 32 columns a wavefront holds two rows of a
+// block at once in the per-column phases: lane = (row half hp, column), as k_feat_y does at its 32-column blocks.
+template <bool PROJ, int TPW = SLY_TPW, int CB = SLY_CB, int MMAX = SLY_MMAX> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(SysParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NW = SLY_NW, TPW = SLY_TPW, NTH = 64 * SLY_NW, RS = SLY_RS, LS = SLY_LS, CB = SLY_CB;
+  constexpr int NW = SLY_NW, NTH = 64 * SLY_NW, RS = SLY_RS, LS = CB + 2;
+  constexpr int NCTB = CB / 16; // column tiles per block
+  constexpr int HP = 64 / CB;   // rows a wavefront holds at once in the per-column phases
+  static_assert(CB == 64 || CB == 32, "column blocks of 64 or 32");
+  static_assert(((2 * MMAX + 4 + 15) >> 4) * (((2 * MMAX + 4 + 15) >> 4) + 1) / 2 <= NW * TPW, "the gate's upper triangle exceeds the wavefronts' tiles");
+  static_assert(2 * MMAX <= 32 * NW, "z's row segments do not cover the track");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, cl = lane & 15;
   const int D = p.D, LD = p.LD;
-  const SlamYLds lo = slamy_lds_layout(p.m_max, PROJ);
+  const int colb = lane & (CB - 1), hp = lane / CB;
+  const SlamYLds lo = slamy_lds_layout(p.m_max, PROJ, CB);
   double *Yb = reinterpret_cast<double *>(smem + lo.yb);
   const int nta_max = (2 * p.m_max + 4 + 15) >> 4;
   double *panel = Yb, *panelx = Yb + (size_t)nta_max * 256;
@@ -119,7 +139,7 @@ template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(Sys
     const int n_out = (int)(p.row_off[f + 1] - orow0); // 2m
     __syncthreads(); // the previous feature's LDS is fully consumed
     double *out = p.Hbig + orow0 * LD;
-    if (p.status[f] != OVGPU_FEAT_USED || m > SLY_MMAX) { // failed before the gate: its rows of the stack are zero (m > SLY_MMAX: the host never sends such a batch)
+    if (p.status[f] != OVGPU_FEAT_USED || m > MMAX) { // failed before the gate: its rows of the stack are zero (m > MMAX: the host never sends such a batch)
       for (int64_t e = tid; e < (int64_t)n_out * LD; e += NTH) out[e] = 0.0;
       continue;
     }
@@ -254,11 +274,11 @@ template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(Sys
         const double hA0 = relative ? rd[RO_ANC + 6 * par + g] : 0.0, hA1 = relative ? rd[RO_ANC + 6 * par + g1] : 0.0;
         const double hQ0 = relative ? rd[RO_ACAL + 6 * par + g] : 0.0, hQ1 = relative ? rd[RO_ACAL + 6 * par + g1] : 0.0;
         const double hF0 = rd[RO_HF + 3 * par + (single ? 2 : min(g, 2))];
-        d4 ay[4];
-        bool okc[4];
-        int cc[4];
+        d4 ay[NCTB];
+        bool okc[NCTB];
+        int cc[NCTB];
 #pragma unroll
-        for (int ct = 0; ct < 4; ct++) {
+        for (int ct = 0; ct < NCTB; ct++) {
           ay[ct] = d4{0.0, 0.0, 0.0, 0.0};
           okc[ct] = c_lo + 16 * ct + cl < D;
           cc[ct] = min(c_lo + 16 * ct + cl, D - 1); // clamped address, masked value
@@ -281,7 +301,7 @@ template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(Sys
           a1 = 4 + g < w ? a1 : 0.0;
           const double *L0 = p.Lw + (size_t)min(fc + g, D - 1) * D, *L1 = p.Lw + (size_t)min(fc + 4 + g, D - 1) * D;
 #pragma unroll
-          for (int ct = 0; ct < 4; ct++) {
+          for (int ct = 0; ct < NCTB; ct++) {
             if (fc + w - 1 < c_lo + 16 * ct || c_lo + 16 * ct >= D) continue; // (wave-uniform)
             const double b0 = okc[ct] ? L0[cc[ct]] : 0.0;
             FEAT_MFMA(a0, b0, ay[ct]);
@@ -292,30 +312,53 @@ template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW) k_slam_y(Sys
           }
         }
 #pragma unroll
-        for (int ct = 0; ct < 4; ct++)
+        for (int ct = 0; ct < NCTB; ct++)
 #pragma unroll
           for (int q = 0; q < 4; q++) Yb[(size_t)(16 * i + g + 4 * q) * LS + 16 * ct + cl] = ay[ct][q];
       }
       lds_barrier();
       if (PROJ && single) {
-        // ---- V^T Y of the block: wavefront wv takes reflector wv & 1 over the row quarter wv >> 1 (32 rows), lane = column                  | barrier
-        const int k = wv & 1, r0 = 32 * (wv >> 1), r1 = min(r0 + 32, n);
-        double y = 0.0;
-        for (int a = r0; a < r1; a++) y = fma(Vq[(size_t)3 * a + k], Yb[(size_t)a * LS + lane], y);
-        zp[wv * CB + lane] = y;
-        lds_barrier();
-        // ---- rows 2 .. n-1 of oscale (Y - V z), z = T^T V^T Y -> rows 0 .. n-3 of the stack
-        const double y0 = ((zp[lane] + zp[2 * CB + lane]) + zp[4 * CB + lane]) + zp[6 * CB + lane];
-        const double y1 = ((zp[CB + lane] + zp[3 * CB + lane]) + zp[5 * CB + lane]) + zp[7 * CB + lane];
-        const double z0 = hq[3] * y0, z1 = hq[4] * y0 + hq[6] * y1; // T00, T01, T11 (sys_hf_householder)
-        const int c = c_lo + lane;
-        if (c < D)
-          for (int a = 2 + wv; a < n; a += NW) out[(int64_t)(a - 2) * LD + c] = oscale * (Yb[(size_t)a * LS + lane] - (Vq[(size_t)3 * a] * z0 + Vq[(size_t)3 * a + 1] * z1));
+        if constexpr (CB == 64) {
+          // ---- V^T Y of the block: wavefront wv takes reflector wv & 1 over the row quarter wv >> 1 (32 rows), lane = column                  | barrier
+          const int k = wv & 1, r0 = 32 * (wv >> 1), r1 = min(r0 + 32, n);
+          double y = 0.0;
+          for (int a = r0; a < r1; a++) y = fma(Vq[(size_t)3 * a + k], Yb[(size_t)a * LS + lane], y);
+          zp[wv * CB + lane] = y;
+          lds_barrier();
+          // ---- rows 2 .. n-1 of oscale (Y - V z), z = T^T V^T Y -> rows 0 .. n-3 of the stack
+          const double y0 = ((zp[lane] + zp[2 * CB + lane]) + zp[4 * CB + lane]) + zp[6 * CB + lane];
+          const double y1 = ((zp[CB + lane] + zp[3 * CB + lane]) + zp[5 * CB + lane]) + zp[7 * CB + lane];
+          const double z0 = hq[3] * y0, z1 = hq[4] * y0 + hq[6] * y1; // T00, T01, T11 (sys_hf_householder)
+          const int c = c_lo + lane;
+          if (c < D)
+            for (int a = 2 + wv; a < n; a += NW) out[(int64_t)(a - 2) * LD + c] = oscale * (Yb[(size_t)a * LS + lane] - (Vq[(size_t)3 * a] * z0 + Vq[(size_t)3 * a + 1] * z1));
+        } else {
+          // ---- V^T Y of the block: wavefront wv takes the rows 32 wv .. 32 wv + 31, lane = (reflector hp, column): 8 x 32 rows hold n <= 252                | barrier
+          const int r0 = 32 * wv, r1 = min(r0 + 32, n);
+          double y = 0.0;
+          for (int a = r0; a < r1; a++) y = fma(Vq[(size_t)3 * a + hp], Yb[(size_t)a * LS + colb], y);
+          zp[wv * 2 * CB + lane] = y; // [wv][hp][colb]
+          lds_barrier();
+          // ---- rows 2 .. n-1 of oscale (Y - V z) -> rows 0 .. n-3 of the stack; the eight segments summed first to last
+          double y0 = zp[colb], y1 = zp[CB + colb];
+#pragma unroll
+          for (int w8 = 1; w8 < NW; w8++) y0 += zp[w8 * 2 * CB + colb], y1 += zp[w8 * 2 * CB + CB + colb];
+          const double z0 = hq[3] * y0, z1 = hq[4] * y0 + hq[6] * y1; // T00, T01, T11 (sys_hf_householder)
+          const int c = c_lo + colb;
+          if (c < D)
+            for (int a = 2 + HP * wv + hp; a < n; a += HP * NW) out[(int64_t)(a - 2) * LD + c] = oscale * (Yb[(size_t)a * LS + colb] - (Vq[(size_t)3 * a] * z0 + Vq[(size_t)3 * a + 1] * z1));
+        }
       } else {
         // ---- rows of oscale Y -> the stack
-        const int c = c_lo + lane;
-        if (c < D)
-          for (int a = wv; a < n; a += NW) out[(int64_t)a * LD + c] = oscale * Yb[(size_t)a * LS + lane];
+        if constexpr (CB == 64) {
+          const int c = c_lo + lane;
+          if (c < D)
+            for (int a = wv; a < n; a += NW) out[(int64_t)a * LD + c] = oscale * Yb[(size_t)a * LS + lane];
+        } else { // a wavefront writes two rows' 256 contiguous bytes
+          const int c = c_lo + colb;
+          if (c < D)
+            for (int a = HP * wv + hp; a < n; a += HP * NW) out[(int64_t)a * LD + c] = oscale * Yb[(size_t)a * LS + colb];
+        }
       }
       // ---- SYRK: S0 tiles += Y_i Y_j^T over the block's slabs of 8 columns (columns >= D of the block hold zeros)
       const int nsl = min(CB / 8, (D - 1 - c_lo) / 8 + 1);

@@ -1,7 +1,7 @@
 """What the fused per-feature kernel of the SLAM update (csrc/k_slam_y.h, ovgpu_debug_option "slam_fused") is worth: the tree's library against
 another build of it on one box.
 
-    time [--reps 30] [--rounds 3] [--lib-a PATH] [--tag NAME] [--tag-a NAME] [--cases slam,chunked] [--state 3dof|mixed] [--level-a1 0] [--level-b 1] [--out FILE.jsonl]
+    time [--reps 30] [--rounds 3] [--lib-a PATH] [--tag NAME] [--tag-a NAME] [--cases slam,chunked] [--state 3dof|mixed|long] [--level-a1 0] [--level-b 1] [--out FILE.jsonl]
                     leg A runs on the library --lib-a names (the parent commit's build; without it: the tree's with the switch untouched), leg A' on
                     the tree's with "slam_fused" = --level-a1 (0), leg B on the tree's with "slam_fused" = --level-b (1): the switch is a level, an
                     integer.  A leg whose count of fused pipelines ("slam_fused_batches") is not what its level and the state say — some at level 1
@@ -13,10 +13,13 @@ another build of it on one box.
                     (DESIGN.md section 7's rows hold a single-depth landmark in every sixth place; at level 1 a batch that holds one keeps the general
                     kernel as a whole, so the landmarks of --state 3dof are the five 3-dof representations: 3 more columns per former single-depth
                     landmark.  --state mixed is the table's own state, the six representations in turn: --level-a1 1 --level-b 2 times the parent's
-                    library, this one at level 1 — k_system_t, as the parent — and this one at level 2, k_slam_y<true>.)
+                    library, this one at level 1 — k_system_t, as the parent — and this one at level 2, k_slam_y<true>.
+                    --state long is the four-camera rig: 30 clones x 4 cameras, the six representations in turn, every track as the rig sees it, up
+                    to 120 observations (D = 303 for a batch of 25).  --level-a1 2 --level-b 3 times the parent's library, this one at level 2 —
+                    k_system_t for every batch whose longest track exceeds 62 — and this one at level 3, the long shapes of k_slam_y.)
                     The legs take turns frame by frame, `rounds` repetitions of `reps` frames; a row per (case, leg) with the median of every
                     round, the median of those and their spread (max - min), and a summary row: A' against A's spread, A - B against the largest spread.
-    trace [--case slam] [--leg B] [--calls 10] [--lib-a PATH] [--state 3dof|mixed] [--level-a1 0] [--level-b 1]
+    trace [--case slam] [--leg B] [--calls 10] [--lib-a PATH] [--state 3dof|mixed|long] [--level-a1 0] [--level-b 1]
                     the frames of one leg alone, for a rocprofv3 --kernel-trace --stats run of its own"""
 import argparse
 import ctypes as C
@@ -59,6 +62,8 @@ class Leg:
         assert lib.ovgpu_create(C.byref(opts), 0, C.byref(self.ctx)) == 0
         self.knows = fused is not None
         self.expect_fused = fused is not None and (fused >= 2 or (fused >= 1 and state == "3dof"))
+        if state == "long":  # every batch holds a 120-observation track: fused at level 3 alone
+            self.expect_fused = fused is not None and fused >= 3
         if fused is not None:
             self.ok(lib.ovgpu_debug_option(self.ctx, b"slam_fused", int(fused), None), "ovgpu_debug_option")
         self.ip = lambda a: a.ctypes.data_as(capi.c_int32_p)
@@ -68,10 +73,13 @@ class Leg:
         reps6 = [capi.REP_GLOBAL_3D, capi.REP_ANCHORED_3D, capi.REP_GLOBAL_3D, capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, capi.REP_GLOBAL_FULL_INVERSE_DEPTH,
                  capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE]  # DESIGN.md section 7's rows (tools/dev_chol_wide_ab.py, tools/dev_slam_chunked_ab.py)
         reps = np.array((reps5 * ((L + 4) // 5))[:L] if state == "3dof" else (reps6 * ((L + 5) // 6))[:L], np.int32)
-        full = synth.make_slam_problem(2, L=L, lm_rep=reps, seed=3)
+        if state == "long":
+            reps = np.array((reps6 * ((L + 5) // 6))[:L], np.int32)
+        full = synth.make_slam_problem(2, L=L, lm_rep=reps, seed=3, **(dict(C=30, K=4) if state == "long" else {}))
         prob = full.subset(np.arange(F))
         prob.lm_index = np.ascontiguousarray(np.arange(F), dtype=np.int32)
         self.lm = prob.lm_index
+        self.m_max = int(np.diff(prob.meas_offsets).max())
         self.first = np.arange(0, F + 1, 25, dtype=np.int32)
         n = len(self.first) - 1
         self.st, self.x2, self.thr, self.lmo = np.zeros(F, np.int32), np.zeros(F), np.zeros(F), np.zeros((L, 3))
@@ -152,7 +160,7 @@ def timed(a):
         if any((counts[k] > 0) != leg.expect_fused for k, leg in legs.items()):
             raise RuntimeError(f"case {case}: fused pipelines per leg {counts} — nothing was compared")
         for k, leg in legs.items():
-            row = dict(case=case, state=a.state, leg=k, level=({"A": None, "A'": a.level_a1, "B": a.level_b}[k]), D=leg.D, build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k],
+            row = dict(case=case, state=a.state, m_max=leg.m_max, leg=k, level=({"A": None, "A'": a.level_a1, "B": a.level_b}[k]), D=leg.D, build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k],
                        ms_median=float(np.median(med[k])), ms_spread=spread(med[k]), fused_pipelines=counts[k])
             if case == "slam":
                 row["ms_total_device"], row["n_used"] = float(leg.stats.ms_total), int(leg.stats.n_used)
@@ -205,7 +213,7 @@ def main():
     r.add_argument("--calls", type=int, default=10)
     r.add_argument("--lib-a", default=None)
     for q in (t, r):
-        q.add_argument("--state", choices=("3dof", "mixed"), default="3dof")
+        q.add_argument("--state", choices=("3dof", "mixed", "long"), default="3dof")
         q.add_argument("--level-a1", type=int, default=0)
         q.add_argument("--level-b", type=int, default=1)
     a = ap.parse_args()
