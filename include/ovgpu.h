@@ -1199,7 +1199,7 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             (ovgpu_msckf_compress), the fp32 variant, the Householder route and batches assembled by ovgpu_tracks_to_features
  *                             always stack projected rows.  ("raw_work_const": the region work model's constant; 2: one region, developer experiments)
  *   "last_stack_raw"          (read only) the last pipeline's Gram matrix came from the unprojected stack
- *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline: 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one,
+ *   "last_feature_kernel"     (read only) per-feature kernel of the last batch pipeline (enum FeatKernel, csrc/api_context.inc): 0 the general one, 1 / 2 the one-pass fused shapes, 3 the block-row one,
  *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
  *                             (k_slam_y<false>: no single-depth landmark observed), 5 k_slam_y<true>, the same kernel with the projection of
  *                             single-depth landmarks ("slam_fused" = 2), 6 / 7 the long shapes of k_slam_y<false> / k_slam_y<true>: a batch whose

@@ -110,6 +110,39 @@ struct EventPair {
 
 enum { CTRL_FLAGS = 1, CTRL_ROWS = 2, CTRL_COUNTER = 4, CTRL_PROG0 = 8, CTRL_PROG1 = 16, CTRL_INTS = 64, CHOL_PROG_STRIDE = 24 };
 
+// The per-feature kernels.  The values are the codes ovgpu_debug_option "last_feature_kernel" reports (include/ovgpu.h): this is their one list.
+enum FeatKernel : int {
+  FK_GENERAL = 0,         // k_system_t (k_system.h): every batch can end up here
+  FK_FEATY_4 = 1,         // k_feat_y<4, 9> (k_featy.h), the MSCKF fast path's one-pass kernel
+  FK_FEATY_8 = 2,         // k_feat_y<8, 17>
+  FK_FEATY_BIG = 3,       // k_feat_y_big (k_featy_big.h): gate matrices beyond a compute unit's registers, block row by block row
+  FK_SLAMY = 4,           // k_slam_y<false> (k_slam_y.h): SLAM batches under ovgpu_debug_option "slam_fused"
+  FK_SLAMY_PROJ = 5,      // k_slam_y<true>: with the projection of single-depth landmarks
+  FK_SLAMY_LONG = 6,      // the long shapes of the two: 63 .. 126 observations ("slam_fused" = 3)
+  FK_SLAMY_LONG_PROJ = 7,
+};
+
+// What the batch in force and the switches at layout time determine about the per-feature stage: a value, made by plan_feature_stage
+// (api_state.inc) and kept as c->plan; enqueue_system's selector (api_pipeline.inc) picks the launch from it and the launch-time switches.
+struct FeatPlan {
+  // the general kernel's carve (k_system.h) — always filled in: a single feature (f_one >= 0), the routes without L and per-feature sigma on an
+  // MSCKF batch end up there whatever else the batch was laid out for
+  bool rows_global = false;   // k_system_t<true>: the longest track's Jacobian records do not fit LDS and live in c->sys_rows_ws
+  int m_lds_max = 0;          // the longest track whose gate matrix is LDS-resident; longer ones keep theirs in c->gate_ws
+  size_t sys_lds = 0;         // its dynamic LDS bytes
+  int sys_grid = 1;
+  int64_t gate_ws_stride = 0; // doubles per workgroup of c->gate_ws; 0: no track needs it
+  // the fused kernel of the MSCKF fast path the batch was laid out for (FK_FEATY_4 / _8 / _BIG), or FK_GENERAL: none
+  FeatKernel msckf = FK_GENERAL;
+  int nt = 0, nta = 0;        // tile rows of the longest track (2 m rows) and of its gate matrix (2 m + 4 rows)
+  int nw() const { return msckf == FK_FEATY_4 ? 4 : 8; } // wavefronts per workgroup
+  bool lm_fast_ok = false;    // ... with landmarks resident under the empty active set: ovgpu_msckf_update_lm may take it (lm_fast_on)
+  // the fused kernel a SLAM batch was laid out for (FK_SLAMY ..), or FK_GENERAL: none — and its LDS bytes
+  FeatKernel slam = FK_GENERAL;
+  size_t slam_lds = 0;
+  const char *error = nullptr; // no kernel holds the batch's longest track (OVGPU_ERR_CAPACITY)
+};
+
 struct LoopComm;
 // ---- one launch instead of one copy per array (round 6) ---------------------------------------------------------------------------
 // ovgpu_set_state + ovgpu_set_features hand over ~20 arrays per frame, most of them a few hundred bytes.  As one hipMemcpyAsync each they
@@ -202,16 +235,12 @@ struct ovgpu_ctx {
   // ovgpu_msckf_update_lm: resident landmarks that have NO column (the empty active set) are extra rows of P, as the IMU block is — the column map
   // is a landmark-free state's and so is every kernel of the MSCKF update
   bool lm_empty_set = false;      // L > 0 and ovgpu_set_active_landmarks(ctx, NULL, 0) holds (layout_columns)
-  bool lm_fast_ok = false;        // ... and the resident batch was laid out for the fused per-feature kernels under it (set_row_layout)
-  int last_feat_kernel = 0;       // per-feature kernel of the last batch pipeline: 0 the general one (k_system.h), else the fused shape that ran (feat_variant; 4: k_slam_y<false>, 5: k_slam_y<true>; 6 / 7: their long shapes, 63 .. 126 observations)
+  FeatPlan plan;                  // the per-feature stage of the batch in force (size_feature_stage)
+  FeatKernel last_feat_kernel{FK_GENERAL}; // ovgpu_debug_option "last_feature_kernel": what the last batch pipeline was laid out for and ran
   bool anchored_fast = true;      // ovgpu_debug_option "anchored_fast": batches of an anchored feat_rep_msckf are laid out for the fused per-feature kernels too (set_row_layout)
   bool lm_fast_on = false;        // ovgpu_msckf_update_lm is running: the one entry that takes them with landmarks resident (enqueue_system)
   // the fused per-feature kernel of UpdaterSLAM::update (k_slam_y.h), behind a switch that is off by default
-  int slam_fused = 0;             // ovgpu_debug_option "slam_fused", a level: 0 off; 1 SLAM batches whose observed landmarks are all 3-dof are laid out for k_slam_y<false>; 2 also the ones that observe a single-depth landmark, for k_slam_y<true>; 3 also the batches whose longest track holds 63 .. 126 observations, for the long shapes (size_feature_stage)
-  bool slam_fused_ok = false;     // ... and the batch in force is one it holds: the landmarks observed as the level asks, longest track <= SLY_MMAX (SLY_MMAX_L at level 3), D >= 16, K C <= 8192
-  bool slam_fused_proj = false;   // ... with a single-depth landmark among them: k_slam_y<true> and its LDS carve (levels 2 and 3)
-  bool slam_fused_long = false;   // ... with a track of 63 .. 126 observations: the long shape k_slam_y<.., 17, 32, 126> and its carve (level 3 only)
-  size_t slamy_lds = 0;           // its LDS bytes for the batch in force
+  int slam_fused = 0;             // ovgpu_debug_option "slam_fused", a level: 0 off; 1 SLAM batches whose observed landmarks are all 3-dof are laid out for k_slam_y<false>; 2 also the ones that observe a single-depth landmark, for k_slam_y<true>; 3 also the batches whose longest track holds 63 .. 126 observations, for the long shapes (plan_feature_stage)
   int64_t slam_fused_batches = 0; // ovgpu_debug_option "slam_fused_batches": pipelines that took k_slam_y, counted once per update: the pipelines of an attempt that update_with_fallbacks repeats (Householder route, step-wise Cholesky) are taken off again
   int slam_fused_attempt = 0;     // ... of them, the ones of the update attempt that is running (update_with_fallbacks)
   // device-resident FeatureDatabase (ovgpu_tracks_*)
@@ -309,13 +338,8 @@ struct ovgpu_ctx {
   bool whiten = true;           // options.gram_no_whiten == 0: the stack is whitened by the prior BEFORE its Gram matrix is formed
   bool gram_is_whitened = false; // c->gram_G / the Gram buffer handed out by the last local stage is the whitened stack's
   bool prior_on_side = false;   // the pending prior-block factorisation runs on stream2 (ev_join marks its end)
-  int feat_variant = 0;         // MSCKF fast path of the per-feature stage (k_feat.h) for this batch: 0 none, 1 <4,11>, 2 <8,17>
-  int feat_nt_max = 0;
-  // the fused form of the fast path (k_featy.h): rows, projection, stack and gate in one kernel, gate matrix as a SYRK of the whitened rows
-  bool featy_ok = false;         // this batch fits it
+  // the fused form of the MSCKF fast path (k_featy.h): rows, projection, stack and gate in one kernel, gate matrix as a SYRK of the whitened rows
   int featy_skip = 0;              // ovgpu_debug_option "featy_skip": ablation bit mask (timing experiments only)
-  int featy_grid = 0;
-  size_t featy_lds = 0;
   DevBuf<double> fs_tq;
   DevBuf<int32_t> fs_inst;
   DevBuf<double> featyb_ws;        // k_featy_big.h: row panels of the earlier passes, per workgroup
@@ -368,7 +392,6 @@ struct ovgpu_ctx {
   bool no_chol_pipe = false;   // options.no_single_launch_cholesky
   int tri_waves = 0;           // features per workgroup of k_triangulate; 0 = by the batch (enqueue_triangulate); ovgpu_debug_option "tri_waves" forces 1 .. 16
   int feat_shape = 0;          // options.feature_kernel_shape
-  int feat_nta_max = 0;        // tile rows of the longest track's gate matrix (2 m + 4 rows)
   PinBuf<unsigned char> up_arena; // page-locked upload arena of ovgpu_set_state / ovgpu_set_features (upload_staged)
   PinBuf<unsigned char> down_arena; // page-locked landing zone of the results (status, chi2, p_FinG, dx, P'): asynchronous copies, one synchronisation, memcpy to the caller
   size_t up_off = 0, up_want = 8u << 20;
@@ -415,12 +438,7 @@ struct ovgpu_ctx {
   bool speculative_prior = true; // ovgpu_debug_option "speculative_prior": ovgpu_set_features starts that factorisation (api_pipeline.inc: enqueue_speculative_prior)
   DevBuf<int32_t> gram_dropped;
   DevView<int32_t> rows_used; // rows of accepted features, counted by k_system
-  int sys_grid = 1;
-  int64_t gate_ws_stride = 0;
-  bool sys_rows_global = false;    // k_system_t<true>: the longest track's Jacobian records do not fit LDS
-  DevBuf<double> sys_rows_ws;      // ... its per-workgroup record workspace
-  int m_lds_max = 0;
-  size_t sys_lds_bytes = 0;
+  DevBuf<double> sys_rows_ws;      // k_system_t<true> (plan.rows_global): its per-workgroup record workspace
   int row_stride = 48;
 
   // ---- timing

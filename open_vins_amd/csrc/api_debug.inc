@@ -93,7 +93,7 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = t;
   } else if (n == "stack_is_f32") { // read-only: the last pipeline stored the stack as floats and ran k_gram_f32 (options.gram_fp32)
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
-  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline — 0 the general one (k_system.h), 1 / 2 k_feat_y<4, 9> / <8, 17>, 3 k_feat_y_big, 4 k_slam_y<false> / 5 k_slam_y<true>, with the projection of single-depth landmarks (SLAM batches under "slam_fused"), 6 / 7 the long shapes of the two (63 .. 126 observations, "slam_fused" = 3)
+  } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline, a FeatKernel (api_context.inc lists the codes)
     if (old_value) *old_value = c->last_feat_kernel;
   } else if (n == "last_gram_kernel") { // read-only, this and the two below: what the last batch pipeline launched (api_context.inc lists the codes)
     if (old_value) *old_value = c->last_gram_kernel;
@@ -117,16 +117,16 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->tsqr_last_tree;
   } else if (n == "tsqr_last_qh") { // 16 / 28 / 32: quads per register array of the merge kernels; 0: k_qr_append, or no merge
     if (old_value) *old_value = c->tsqr_last_qh;
-  } else if (n == "sys_lds_limit") { // read-only, this and the four below: the general per-feature kernel's LDS carve for the batch in force (size_feature_stage, api_state.inc) — the byte limit it was carved under
+  } else if (n == "sys_lds_limit") { // read-only, this and the four below: the general per-feature kernel's LDS carve for the batch in force (FeatPlan, plan_feature_stage in api_state.inc) — the byte limit it was carved under
     if (old_value) *old_value = c->lds_limit;
   } else if (n == "sys_m_lds_max") { // the largest track length whose gate matrix is LDS-resident; longer tracks of the batch keep theirs in the per-workgroup global workspace
-    if (old_value) *old_value = c->m_lds_max;
+    if (old_value) *old_value = c->plan.m_lds_max;
   } else if (n == "sys_rows_global") { // 1: the Jacobian records live in a global workspace (k_system_t<true>), 0: in LDS
-    if (old_value) *old_value = c->sys_rows_global ? 1 : 0;
+    if (old_value) *old_value = c->plan.rows_global ? 1 : 0;
   } else if (n == "sys_row_stride") { // doubles per Jacobian record: 48, or 72 once an anchored representation is in force
     if (old_value) *old_value = c->row_stride;
   } else if (n == "sys_lds_bytes") { // the dynamic LDS size of the kernel's launch
-    if (old_value) *old_value = (int64_t)c->sys_lds_bytes;
+    if (old_value) *old_value = (int64_t)c->plan.sys_lds;
   } else if (n == "chol_timeouts") { // read-only counter: updates repeated with the step-wise Cholesky after a follower timed out
     if (old_value) *old_value = c->chol_timeouts;
   } else {

@@ -34,27 +34,97 @@ static int enqueue_triangulate(ovgpu_ctx *c, const double *seed_pA = nullptr, co
   return OVGPU_OK;
 }
 
-// one launch of the fused per-feature kernel in the given shape (k_featy.h): as many workgroups per CU as its registers (OCC) and its
-// LDS block allow, the features dealt round-robin over them
-extern "C++" {
-template <int NW, int TPW, int OCC, bool F32, int CB, bool CH = false>
-static int launch_featy(ovgpu_ctx *c, const SysParams &p, const double *sr, const int32_t *sm, const double *sV, const double *stq, const int32_t *sin, const int32_t *ssl) {
-  static bool attr = false;
-  auto kern = feat::k_feat_y<NW, TPW, OCC, F32, CB, CH>;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-    attr = true;
+// ---- the per-feature stage: the kernel is picked once (select_feat_kernel) and launched in one place (launch_feat_kernel)
+struct FeatLaunch {
+  FeatKernel kernel = FK_GENERAL; // the kernel that runs
+  FeatKernel code = FK_GENERAL;   // ... and what "last_feature_kernel" reports: the kernel the batch was laid out for ("featy_big" runs
+                                  // k_feat_y_big on a batch laid out for a one-pass shape, which keeps that shape's code)
+  bool f32 = false; // the stack leaves as floats (options.gram_fp32): k_feat_y<.., F32 = true>, k_feat_y_big<8, 17, true>
+  bool ch = false;  // k_feat_y<.., CH = true>: the run table, the next slot requested a feature ahead ("featy_chains")
+  bool alt = false; // the kernel's other shape: k_feat_y_big<8, 5> ("featy_big" = 2), k_system_t<true> (Jacobian records in global memory)
+  int cb = 0;       // columns per block of the fused MSCKF kernels' sweep; 0: another kernel
+  size_t lds = 0;   // dynamic LDS bytes, by the kernel header's own layout function
+  int grid = 1;
+  int err = OVGPU_OK;
+  const char *msg = nullptr;
+};
+// one row of launch_feat_kernel's switch per instantiation
+static constexpr int feat_key(FeatKernel k, bool f32 = false, bool ch = false, bool alt = false) { return 8 * k + (f32 ? 1 : 0) + (ch ? 2 : 0) + (alt ? 4 : 0); }
+
+// The kernel of this launch: from the plan of the batch in force (F features), what p asks for — L (the whitened route; never with f_one >= 0),
+// SLAM rows, per-feature sigma / multiplier —, f_one, and the launch-time switches "featy_big", "featy_chains", options.gram_fp32 and lm_fast_on.
+static FeatLaunch select_feat_kernel(const ovgpu_ctx *c, const SysParams &p, int F, int f_one) {
+  const FeatPlan &pl = c->plan;
+  const size_t limit = (size_t)c->lds_limit;
+  FeatLaunch s;
+  size_t need; // what the batch in force takes of the kernel's LDS, against s.lds: what the batch was laid out for
+  // the MSCKF fast path: whitened output, one noise level (k_feat.h); a global representation, or an anchored one on its own record kernel
+  // (with landmarks resident — the empty active set, set_row_layout — only for ovgpu_msckf_update_lm: every other entry keeps the general kernel)
+  if (p.Lw && pl.msckf != FK_GENERAL && (c->L == 0 || (c->lm_fast_on && pl.lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
+    s.code = pl.msckf, s.kernel = featy_block_rows(c) ? FK_FEATY_BIG : pl.msckf, s.cb = featy_block_cols(c);
+    if (s.kernel == FK_FEATY_BIG) { // block row by block row (k_featy_big.h), one workgroup per CU; <8, 5> has no float32 twin
+      s.alt = c->featy_big == 2, s.f32 = c->want_stack_f32 && !s.alt;
+      s.lds = feat::featyb_lds_layout(pl.nt, 8).total;
+      s.grid = std::max(1, std::min(F, c->num_cu));
+      s.err = OVGPU_ERR_CAPACITY, s.msg = "k_feat_y_big: track too long for its LDS block";
+    } else { // as many workgroups per CU as its registers (<4, 9, 2>: two; <8, 17, 1>: one) and its LDS block allow, the features dealt round-robin over them
+      s.f32 = c->want_stack_f32, s.ch = !s.f32 && c->featy_chains;
+      s.lds = feat::featy_lds_layout(pl.nt, pl.nta, pl.nw(), s.cb).total;
+      const int per_cu = std::max(1, std::min(s.kernel == FK_FEATY_4 ? 2 : 1, (int)(limit / s.lds)));
+      s.grid = std::max(1, std::min(F, c->num_cu * per_cu));
+      s.err = OVGPU_ERR_INVALID, s.msg = "internal: the MSCKF fast path was selected for a batch the fused kernel does not hold";
+    }
+    need = s.lds;
+  } else if (p.slam && p.Lw && pl.slam != FK_GENERAL) {
+    // UpdaterSLAM::update on the whitened route, a batch laid out for it under ovgpu_debug_option "slam_fused": the fused kernel (k_slam_y.h).
+    // Everything else — the Householder repeat and the other routes without L, the delayed initialisation, a batch it does not hold — keeps k_system_t.
+    const bool lng = pl.slam >= FK_SLAMY_LONG, proj = pl.slam == FK_SLAMY_PROJ || pl.slam == FK_SLAMY_LONG_PROJ;
+    s.code = s.kernel = pl.slam;
+    need = slamy::slamy_lds_layout(p.m_max, proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total, s.lds = pl.slam_lds;
+    s.grid = std::max(1, std::min(F, c->num_cu));
+    s.err = OVGPU_ERR_INVALID, s.msg = "internal: k_slam_y was selected for a batch it does not hold";
+  } else {
+    s.alt = pl.rows_global, s.lds = need = pl.sys_lds, s.grid = f_one >= 0 ? 1 : pl.sys_grid;
   }
-  const int nt = c->feat_nt_max, nta = c->feat_nta_max;
-  if (nta * (nta + 1) / 2 > NW * TPW) return set_err(OVGPU_ERR_INVALID, "internal: the fused kernel's shape does not hold this batch's longest track");
-  const size_t lds = feat::featy_lds_layout(nt, nta, NW, CB).total;
-  if (lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_CAPACITY, "k_feat_y: track too long for its LDS block");
-  const int per_cu = std::max(1, std::min(std::max(1, 4 * OCC / NW), (int)((size_t)c->lds_limit / lds))); // OCC wavefronts per SIMD, four SIMDs
-  const int grid = std::max(1, std::min(batch_of(c).F, c->num_cu * per_cu));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl, (const int32_t *)c->raw_runs.p);
-  return OVGPU_OK;
+  if (need <= s.lds && s.lds <= limit) s.err = OVGPU_OK, s.msg = nullptr; // (else: the batch in force is not the one the plan was made for)
+  return s;
+}
+
+extern "C++" {
+// KERN, its maximum dynamic LDS raised to the context's limit before its first launch: once per kernel and process
+template <auto KERN>
+static decltype(KERN) with_max_lds(const ovgpu_ctx *c) {
+  static const hipError_t once = hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
+  (void)once;
+  return KERN;
 }
 } // extern "C++"
+
+// The one launch of the per-feature stage: a row per instantiation (k_system_t's LDS attribute is ovgpu_create's)
+static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams &p) {
+  const dim3 grid(s.grid), slam_block(64 * slamy::SLY_NW);
+  const int nt = c->plan.nt, nta = c->plan.nta;
+  const double *sr = c->fs_rows.p, *sV = c->fs_V.p, *stq = c->fs_tq.p;
+  const int32_t *sm = c->fs_minfo.p, *sin = c->fs_inst.p, *ssl = c->fs_slots.p, *runs = c->raw_runs.p;
+  double *bws = c->featyb_ws.p;
+  switch (feat_key(s.kernel, s.f32, s.ch, s.alt)) {
+#define X(NW, TPW, OCC, F32, CB, CH) case feat_key(NW == 4 ? FK_FEATY_4 : FK_FEATY_8, F32, CH): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y<NW, TPW, OCC, F32, CB, CH>>(c)), grid, dim3(64 * NW), s.lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl, runs); break;
+    OVG_FEATY_SHAPES(X)
+#undef X
+    case feat_key(FK_FEATY_BIG): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 17>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws); break;
+    case feat_key(FK_FEATY_BIG, true): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 17, true>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws); break;
+    case feat_key(FK_FEATY_BIG, false, false, true): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 5>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws); break;
+    case feat_key(FK_SLAMY): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<false>>(c)), grid, slam_block, s.lds, c->stream, p); break;
+    case feat_key(FK_SLAMY_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true>>(c)), grid, slam_block, s.lds, c->stream, p); break;
+    case feat_key(FK_SLAMY_LONG): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
+    case feat_key(FK_SLAMY_LONG_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
+    case feat_key(FK_GENERAL, false, false, true): hipLaunchKernelGGL(k_system_t<true>, grid, dim3(SYS_NT), s.lds, c->stream, p); break;
+    case feat_key(FK_GENERAL): hipLaunchKernelGGL(k_system_t<false>, grid, dim3(SYS_NT), s.lds, c->stream, p); break;
+    default: return set_err(OVGPU_ERR_INVALID, "internal: the per-feature stage has no kernel in the shape selected");
+  }
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
 
 // f_one >= 0: only that feature, in StateHelper::initialize mode with the landmark representation init_rep
 // whiten: the rows leave as [H L | r] with L = c->Lw (the prior block's factor must be complete on this stream)
@@ -70,10 +140,10 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   p.P = c->P.p, p.p_FinG = b.pG, p.p_FinA = b.pA, p.anchor_meas = c->anchor.p;
   p.status = b.status, p.chi2 = b.chi2, p.chi2_thresh = b.chi2_thr;
   p.chi2_table = c->chi2_table.p, p.chi2_table_len = c->chi2_table_len;
-  p.row_off = b.row_off, p.Hbig = c->Hbig.p, p.ws = c->gate_ws.p, p.ws_stride = c->gate_ws_stride;
+  p.row_off = b.row_off, p.Hbig = c->Hbig.p, p.ws = c->gate_ws.p, p.ws_stride = c->plan.gate_ws_stride;
   p.Hbig32 = nullptr, p.LDF = 0;
   c->stack_is_f32 = false;
-  p.m_lds_max = c->m_lds_max, p.m_max = std::max(b.m_max, 1), p.row_stride = c->row_stride;
+  p.m_lds_max = c->plan.m_lds_max, p.m_max = std::max(b.m_max, 1), p.row_stride = c->row_stride;
   p.opt = c->dopt;
   p.dbg = c->dbg_cycles.p ? c->dbg_cycles.p : qr_dbg_buffer();
   p.slam = c->slam_rows ? 1 : 0;
@@ -91,8 +161,7 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   // the one-pass fused kernels on a batch laid out by ovgpu_set_features, float64 stack.  Decided below, once the kernel shape is known.
   p.raw.on = 0;
   c->last_stack_raw = false;
-  if (f_one < 0) c->last_feat_kernel = 0;
-  int grid = c->sys_grid;
+  if (f_one < 0) c->last_feat_kernel = FK_GENERAL;
   if (f_one < 0) HIPCHK(ctrl_zero(c, CTRL_ROWS, c->rows_used.p, 2 * sizeof(int32_t), c->stream));
   if (f_one >= 0) {
     p.order = nullptr;
@@ -101,118 +170,51 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     p.init_keep = c->init_export ? 1 : 0; // ovgpu_slam_init_systems: the host decides the gate again, rejected features are exported too
     p.opt.feat_rep = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH : init_rep; // UpdaterSLAM.cpp:151-155
     p.init_dof_less = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 2 : 0;
-    grid = 1;
   }
-  // the MSCKF fast path: whitened output, one noise level (k_feat.h); a global representation, or an anchored one on its own record kernel
-  // (with landmarks resident — the empty active set, set_row_layout — only for ovgpu_msckf_update_lm: every other entry keeps the general kernel)
-  if (p.Lw && c->feat_variant && (c->L == 0 || (c->lm_fast_on && c->lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
+  const FeatLaunch s = select_feat_kernel(c, p, b.F, f_one);
+  if (s.err != OVGPU_OK) return set_err(s.err, s.msg);
+  if (s.cb) { // the head of the MSCKF fast path
     p.row_stride = 48; // the fused kernels' records (fs_rows holds M * c->row_stride >= 48 M doubles): a 72-double stride — an anchored feat_rep_msckf, anchored
                        // landmarks, an earlier delayed initialisation — is the general kernel's alone
     HIPCHK(ctrl_zero(c, CTRL_COUNTER, c->feat_counter.p, sizeof(int32_t), c->stream));
     p.work_counter = c->feat_counter.p;
     // rows (per measurement) -> gate (needs P only) -> projected whitened rows (need L and z).  The prior block's factorisation and
     // the reflector / z kernel behind it run on the second stream NEXT TO the gate; only the output kernel waits for them.
+    // The fused form (k_featy.h): rows (clone-major) -> reflectors -> [prior block's factor L joins] -> sweep Y = H L once per feature:
+    // projected rows to the stack, gate matrix as Y Y^T + s^2 I on the matrix cores, Cholesky, chi2
     feat::FeatStore st{c->fs_rows.p, c->fs_minfo.p, c->fs_V.p, c->fs_z.p, c->fs_meas_feat.p, c->fs_w.p, c->fs_pos.p};
-    const double *sr = st.rows, *sV = st.V;
-    const int32_t *sm = st.minfo;
-    if (c->featy_ok) {
-      if (f_one < 0) c->last_feat_kernel = c->feat_variant;
-      // the fused form (k_featy.h): rows (clone-major) -> reflectors -> [prior block's factor L joins] -> sweep Y = H L once per feature:
-      // projected rows to the stack, gate matrix as Y Y^T + s^2 I on the matrix cores, Cholesky, chi2
-      static bool attr_y = false;
-      if (!attr_y) {
-        (void)hipFuncSetAttribute((const void *)feat::k_feat_vt, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-        attr_y = true;
-      }
-      if (featy_stack_f32(c, f_one)) { // options.gram_fp32: the rows leave as floats, stride 32 ceil(LD / 32) (k_gram32.h)
-        c->stack_ldf = ((c->LD + 31) / 32) * 32;
-        HIPCHK(c->Hbig32.reserve((size_t)(std::max<int64_t>(b.rows_total, 1) + 32) * c->stack_ldf));
-        // k_gram_f32 copies whole 32-row stages: the rows behind the last feature's must read as zeros
-        HIPCHK(hipMemsetAsync(c->Hbig32.p + (size_t)b.rows_total * c->stack_ldf, 0, sizeof(float) * 32 * c->stack_ldf, c->stream));
-        p.Hbig32 = c->Hbig32.p, p.LDF = c->stack_ldf;
-        c->stack_is_f32 = true;
-      }
-      if (p.opt.feat_rep >= OVGPU_REP_ANCHORED_3D) hipLaunchKernelGGL(feat::k_feat_rows_anchored, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
-      else hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
-      const bool big = c->feat_variant == 3 || c->featy_big;
-      const int cb = featy_block_cols(c, p.Hbig32 != nullptr);
-      if (c->raw_enable && c->raw_tables_ok && !c->raw_veto && !big && !p.Hbig32 && cb == feat::FY_CB) {
-        p.raw.on = 1, p.raw.ncls = c->raw_ncls, p.raw.H = c->Hraw.p, p.raw.dst = c->raw_dst.p, p.raw.j0 = c->raw_j0;
-        for (int k = 0; k <= RAW_NEG; k++) p.raw.base[k] = c->raw_base[k], p.raw.ld[k] = c->raw_ld[k], p.raw.rcol[k] = c->raw_rcol[k];
-        c->last_stack_raw = true;
-      }
-      if (c->inst_cb != cb || c->inst_D != c->D) { // (a switch thrown after the batch was laid out)
-        const int rci = enqueue_instance_lists(c, cb);
-        if (rci != OVGPU_OK) return rci;
-      }
-      hipLaunchKernelGGL(feat::k_feat_vt, dim3((b.F + 3) / 4), dim3(256), (size_t)4 * (14 * p.m_max + 64) * sizeof(double), c->stream, p, st, c->fs_tq.p);
-      if (c->prior_on_side) { // (L and the carried columns come out of one launch since round 5)
-        HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        c->prior_on_side = false; // this stream is behind the factorisation from here on: the update's second half needs no wait of its own (a wait on a
-                                  // completed event still costs the queue ~6 us in front of the second factorisation)
-      }
-      const double *stq = c->fs_tq.p;
-      const int32_t *sin = c->fs_inst.p, *ssl = c->fs_slots.p;
-      if (big) { // block row by block row (k_featy_big.h)
-        static bool attr_b = false;
-        if (!attr_b) {
-          (void)hipFuncSetAttribute((const void *)feat::k_feat_y_big<8, 17>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-          (void)hipFuncSetAttribute((const void *)feat::k_feat_y_big<8, 17, true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-          (void)hipFuncSetAttribute((const void *)feat::k_feat_y_big<8, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-          attr_b = true;
-        }
-        const int nt = c->feat_nt_max, gridb = std::max(1, std::min(b.F, c->num_cu));
-        const size_t ldsb = feat::featyb_lds_layout(nt, 8).total;
-        if (ldsb > (size_t)c->lds_limit || nt > 29) return set_err(OVGPU_ERR_CAPACITY, "k_feat_y_big: track too long for its LDS block");
-        HIPCHK(c->featyb_ws.reserve((size_t)gridb * feat::featyb_ws_doubles(nt)));
-        if (c->featy_big == 2) hipLaunchKernelGGL((feat::k_feat_y_big<8, 5>), dim3(gridb), dim3(512), ldsb, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, c->featyb_ws.p);
-        else if (p.Hbig32) hipLaunchKernelGGL((feat::k_feat_y_big<8, 17, true>), dim3(gridb), dim3(512), ldsb, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, c->featyb_ws.p);
-        else hipLaunchKernelGGL((feat::k_feat_y_big<8, 17>), dim3(gridb), dim3(512), ldsb, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, c->featyb_ws.p);
-      } else {
-        int rcl;
-        if (c->feat_variant == 1 && p.Hbig32) rcl = launch_featy<4, 9, 2, true, 64>(c, p, sr, sm, sV, stq, sin, ssl);
-        else if (c->feat_variant == 1) rcl = c->featy_chains ? launch_featy<4, 9, 2, false, 64, true>(c, p, sr, sm, sV, stq, sin, ssl) : launch_featy<4, 9, 2, false, 64>(c, p, sr, sm, sV, stq, sin, ssl);
-        else if (p.Hbig32) rcl = launch_featy<8, 17, 1, true, 64>(c, p, sr, sm, sV, stq, sin, ssl);
-        else rcl = c->featy_chains ? launch_featy<8, 17, 1, false, 64, true>(c, p, sr, sm, sV, stq, sin, ssl) : launch_featy<8, 17, 1, false, 64>(c, p, sr, sm, sV, stq, sin, ssl);
-        if (rcl != OVGPU_OK) return rcl;
-      }
-      HIPCHK(hipGetLastError());
-      return OVGPU_OK;
+    if (s.f32) { // options.gram_fp32: the rows leave as floats, stride 32 ceil(LD / 32) (k_gram32.h)
+      c->stack_ldf = ((c->LD + 31) / 32) * 32;
+      HIPCHK(c->Hbig32.reserve((size_t)(std::max<int64_t>(b.rows_total, 1) + 32) * c->stack_ldf));
+      // k_gram_f32 copies whole 32-row stages: the rows behind the last feature's must read as zeros
+      HIPCHK(hipMemsetAsync(c->Hbig32.p + (size_t)b.rows_total * c->stack_ldf, 0, sizeof(float) * 32 * c->stack_ldf, c->stream));
+      p.Hbig32 = c->Hbig32.p, p.LDF = c->stack_ldf;
+      c->stack_is_f32 = true;
     }
-    return set_err(OVGPU_ERR_INVALID, "internal: the MSCKF fast path was selected for a batch the fused kernel does not hold");
+    if (p.opt.feat_rep >= OVGPU_REP_ANCHORED_3D) hipLaunchKernelGGL(feat::k_feat_rows_anchored, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
+    else hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
+    if (c->raw_enable && c->raw_tables_ok && !c->raw_veto && s.kernel != FK_FEATY_BIG && !s.f32 && s.cb == feat::FY_CB) {
+      p.raw.on = 1, p.raw.ncls = c->raw_ncls, p.raw.H = c->Hraw.p, p.raw.dst = c->raw_dst.p, p.raw.j0 = c->raw_j0;
+      for (int k = 0; k <= RAW_NEG; k++) p.raw.base[k] = c->raw_base[k], p.raw.ld[k] = c->raw_ld[k], p.raw.rcol[k] = c->raw_rcol[k];
+      c->last_stack_raw = true;
+    }
+    if (c->inst_cb != s.cb || c->inst_D != c->D) { // (a switch thrown after the batch was laid out)
+      const int rci = enqueue_instance_lists(c, s.cb);
+      if (rci != OVGPU_OK) return rci;
+    }
+    hipLaunchKernelGGL(with_max_lds<feat::k_feat_vt>(c), dim3((b.F + 3) / 4), dim3(256), (size_t)4 * (14 * p.m_max + 64) * sizeof(double), c->stream, p, st, c->fs_tq.p);
   }
-  if (p.Lw && c->prior_on_side) { // the general kernel reads L from its first instruction on
+  if (p.Lw && c->prior_on_side) { // the general kernel and k_slam_y read L from their first instruction on, the fused MSCKF kernels behind k_feat_vt
+    // (L and the carried columns come out of one launch since round 5)
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    c->prior_on_side = false;
+    c->prior_on_side = false; // this stream is behind the factorisation from here on: the update's second half needs no wait of its own (a wait on a
+                              // completed event still costs the queue ~6 us in front of the second factorisation)
   }
-  // UpdaterSLAM::update on the whitened route, a batch laid out for it under ovgpu_debug_option "slam_fused": the fused kernel (k_slam_y.h).
-  // Everything else — the Householder repeat and the other routes without L, the delayed initialisation, a batch it does not hold — keeps k_system_t.
-  if (p.slam && p.Lw && f_one < 0 && c->slam_fused_ok) {
-    static bool attr_s = false;
-    if (!attr_s) {
-      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-      (void)hipFuncSetAttribute((const void *)slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-      attr_s = true;
-    }
-    const bool lng = c->slam_fused_long;
-    const dim3 sgrid(std::max(1, std::min(b.F, c->num_cu))), sblock(64 * slamy::SLY_NW);
-    if (p.m_max > (lng ? slamy::SLY_MMAX_L : slamy::SLY_MMAX) || (lng && p.m_max <= slamy::SLY_MMAX) ||
-        slamy::slamy_lds_layout(p.m_max, c->slam_fused_proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total > c->slamy_lds || c->slamy_lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_INVALID, "internal: k_slam_y was selected for a batch it does not hold");
-    c->last_feat_kernel = (lng ? 6 : 4) + (c->slam_fused_proj ? 1 : 0), c->slam_fused_batches++, c->slam_fused_attempt++;
-    if (lng && c->slam_fused_proj) hipLaunchKernelGGL((slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>), sgrid, sblock, c->slamy_lds, c->stream, p);
-    else if (lng) hipLaunchKernelGGL((slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>), sgrid, sblock, c->slamy_lds, c->stream, p);
-    else if (c->slam_fused_proj) hipLaunchKernelGGL(slamy::k_slam_y<true>, sgrid, sblock, c->slamy_lds, c->stream, p);
-    else hipLaunchKernelGGL(slamy::k_slam_y<false>, sgrid, sblock, c->slamy_lds, c->stream, p);
-    HIPCHK(hipGetLastError());
-    return OVGPU_OK;
-  }
-  p.rows_ws = c->sys_rows_global ? c->sys_rows_ws.p : nullptr;
-  if (c->sys_rows_global) hipLaunchKernelGGL(k_system_t<true>, dim3(grid), dim3(SYS_NT), c->sys_lds_bytes, c->stream, p);
-  else hipLaunchKernelGGL(k_system_t<false>, dim3(grid), dim3(SYS_NT), c->sys_lds_bytes, c->stream, p);
-  HIPCHK(hipGetLastError());
-  return OVGPU_OK;
+  if (s.kernel == FK_FEATY_BIG && c->plan.msckf != FK_FEATY_BIG) HIPCHK(c->featyb_ws.reserve((size_t)s.grid * feat::featyb_ws_doubles(c->plan.nt))); // ("featy_big": the batch was not laid out for it)
+  if (s.kernel >= FK_SLAMY) c->slam_fused_batches++, c->slam_fused_attempt++;
+  if (s.kernel == FK_GENERAL) p.rows_ws = s.alt ? c->sys_rows_ws.p : nullptr;
+  if (f_one < 0) c->last_feat_kernel = s.code;
+  return launch_feat_kernel(c, s, p);
 }
 
 // merges triangles Rws[0..G) pairwise until Rws[0] holds the result

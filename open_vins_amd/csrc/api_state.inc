@@ -508,18 +508,11 @@ int ovgpu_set_camera_poses(ovgpu_ctx *c, int C, int K, const double *R_GtoC, con
   return OVGPU_OK;
 }
 
-// Columns per block of the fused per-feature kernel's sweep for the resident batch (the shape enqueue_system launches), and the batch's
-// instance lists for it (k_feat_inst, k_featy.h): built when the batch is laid out; enqueue_system builds them again if a switch that
-// changes the block width was thrown in between.
-static int featy_block_cols(const ovgpu_ctx *c, bool stack_f32) {
-  const bool big = c->feat_variant == 3 || c->featy_big;
-  (void)stack_f32;
-  return big ? 32 : feat::FY_CB;
-}
-static bool featy_stack_f32(const ovgpu_ctx *c, int f_one) {
-  const bool f32_twin = (c->feat_variant == 3 || c->featy_big) ? c->featy_big != 2 : true;
-  return c->want_stack_f32 && f_one < 0 && f32_twin;
-}
+// Whether the fused MSCKF kernel of the resident batch is the block-row one (k_featy_big.h: the batch was laid out for it, or ovgpu_debug_option
+// "featy_big" forces it on a batch the one-pass kernels hold), and with it the columns per block of the sweep.  The batch's instance lists
+// (k_feat_inst, k_featy.h) are built for that width when the batch is laid out; enqueue_system builds them again if the switch was thrown in between.
+static bool featy_block_rows(const ovgpu_ctx *c) { return c->plan.msckf == FK_FEATY_BIG || c->featy_big; }
+static int featy_block_cols(const ovgpu_ctx *c) { return featy_block_rows(c) ? 32 : feat::FY_CB; }
 // The integer tables of a batch that depend on the batch and on the column map alone — with `anchors` the triangulation's anchor measurements
 // (every path), on the fast path measurement -> feature, the clone-major positions and (fused kernels) the column-block lists of the tile rows
 // for blocks of `cb` columns — (re)built by ONE launch on the context's stream (feat::k_batch_layout, k_featy.h; round 5: four launches).
@@ -529,7 +522,7 @@ static bool featy_stack_f32(const ovgpu_ctx *c, int f_one) {
 static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
   const Batch b = batch_of(c);
   const int F = b.F;
-  const bool fast = c->feat_variant != 0 && b.M > 0, lists = fast && c->featy_ok;
+  const bool fast = c->plan.msckf != FK_GENERAL && b.M > 0; // (the instance lists go with the fast path's other tables)
   if (F > 0 && (anchors || fast)) {
     const int m_max = feat::batch_layout_m_pad(std::max(b.m_max, 1));
     // features per workgroup (k_featy.h: why eight); fewer where long tracks' tables would not fit 48 KB of LDS
@@ -543,17 +536,17 @@ static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
     for (int k = 0; k <= RAW_NEG; k++) rw.base[k] = c->raw_base[k], rw.ld[k] = c->raw_ld[k], rw.rcol[k] = c->raw_rcol[k];
     hipLaunchKernelGGL(feat::k_batch_layout, dim3((F + fpw - 1) / fpw), dim3(fast ? feat::BL_NTH * fpw : 64), lds, c->stream, F, m_max, c->D, (const int32_t *)b.meas_offsets, (const uint16_t *)b.meas_cc,
                        (const int32_t *)c->clone_col.p, (const int32_t *)c->calib_col.p, (const int32_t *)c->intr_col.p, anchors ? c->anchor_pre.p : (int32_t *)nullptr,
-                       fast ? c->fs_meas_feat.p : (int32_t *)nullptr, fast ? c->fs_pos.p : (int32_t *)nullptr, lists ? c->fs_inst.p : (int32_t *)nullptr, c->feat_nt_max, cb, c->C, c->K,
+                       fast ? c->fs_meas_feat.p : (int32_t *)nullptr, fast ? c->fs_pos.p : (int32_t *)nullptr, fast ? c->fs_inst.p : (int32_t *)nullptr, c->plan.nt, cb, c->C, c->K,
                        (const uint8_t *)c->cls_of_clone.p, (const int32_t *)c->raw_featbase.p, raw_tabs ? c->raw_dst.p : (int32_t *)nullptr,
                        raw_tabs ? c->raw_runs.p : (int32_t *)nullptr, rw);
     HIPCHK(hipGetLastError());
   }
-  c->inst_cb = lists ? cb : 0, c->inst_D = c->D;
+  c->inst_cb = fast ? cb : 0, c->inst_D = c->D;
   return OVGPU_OK;
 }
 // the column-block lists again for another block width (enqueue_system: a switch that changes the sweep's block width was thrown after the layout)
 static int enqueue_instance_lists(ovgpu_ctx *c, int cb) { return enqueue_batch_layout(c, false, cb); }
-static int enqueue_batch_tables(ovgpu_ctx *c, bool anchors) { return enqueue_batch_layout(c, anchors, c->featy_ok ? featy_block_cols(c, featy_stack_f32(c, -1)) : feat::FY_CB); }
+static int enqueue_batch_tables(ovgpu_ctx *c, bool anchors) { return enqueue_batch_layout(c, anchors, c->plan.msckf != FK_GENERAL ? featy_block_cols(c) : feat::FY_CB); }
 
 // The rows a feature of m measurements stacks.  MSCKF / delayed init: 2m - 3 after the nullspace projection (UpdaterHelper.cpp:449-450); SLAM
 // update: all 2m (UpdaterSLAM.cpp:381-383) less the `proj` rows a single-depth landmark's bearing takes (UpdaterSLAM.cpp:371-379: 3 - dof).
@@ -578,83 +571,46 @@ static void track_order(const int32_t *offsets, int F, int m_max, int32_t *order
   for (int f = 0; f < F; f++) order[start[m_max - (offsets[f + 1] - offsets[f])]++] = f;
 }
 
-// Sizes the per-feature stage for the batch in force and its row layout: the per-feature kernel's LDS carve, grids, workspaces and variant, the
-// fused kernels' slot records, the stack and the TSQR leaf layout.  Reads the batch, writes none of it.
-static int size_feature_stage(ovgpu_ctx *c) {
-  const Batch b = batch_of(c);
-  const int F = b.F, m_max = b.m_max;
-  const bool slam_rows = c->slam_rows;
-  // ---- per-feature kernel: LDS carve and (for long tracks) a global gate workspace
-  size_t fixed = sys_lds_fixed_bytes(std::max(m_max, 1), c->row_stride, c->D);
-  c->sys_rows_global = false;
-  if (fixed >= (size_t)c->lds_limit) { // the records of the longest track do not fit LDS next to the T chunk: a global workspace holds them (k_system_t<true>)
-    fixed = sys_lds_fixed_bytes(std::max(m_max, 1), c->row_stride, c->D, false);
-    c->sys_rows_global = true;
+// The per-feature stage of batch b under the switches in force, as a value (FeatPlan, api_context.inc).  Pure: no HIP call, no reserve, nothing
+// written to the context.
+static FeatPlan plan_feature_stage(const ovgpu_ctx *c, const Batch &b) {
+  FeatPlan pl;
+  const int F = b.F, m_max = b.m_max, m1 = std::max(m_max, 1);
+  const size_t limit = (size_t)c->lds_limit;
+  // ---- the general kernel: LDS carve and (for long tracks) a global gate workspace
+  size_t fixed = sys_lds_fixed_bytes(m1, c->row_stride, c->D);
+  if (fixed >= limit) { // the records of the longest track do not fit LDS next to the T chunk: a global workspace holds them (k_system_t<true>)
+    fixed = sys_lds_fixed_bytes(m1, c->row_stride, c->D, false);
+    pl.rows_global = true;
   }
-  int m_lds = 0;
-  if (fixed < (size_t)c->lds_limit) {
-    const size_t avail = (size_t)c->lds_limit - fixed;
-    while (m_lds < m_max && sys_gate_doubles(m_lds + 1) * sizeof(double) <= avail) m_lds++;
-  } else {
-    return set_err(OVGPU_ERR_CAPACITY, "track too long for the per-feature kernel's LDS tables (block ids and reflectors of ~1900 observations at 208 columns)");
+  if (fixed >= limit) {
+    pl.error = "track too long for the per-feature kernel's LDS tables (block ids and reflectors of ~1900 observations at 208 columns)";
+    return pl;
   }
-  c->m_lds_max = m_lds;
-  c->sys_lds_bytes = fixed + sys_gate_doubles(m_lds) * sizeof(double);
-  c->sys_grid = std::max(1, std::min(F, c->num_cu * 4));
-  if (c->sys_rows_global) HIPCHK(c->sys_rows_ws.reserve((size_t)c->sys_grid * std::max(m_max, 1) * c->row_stride));
-  if (m_lds < m_max) {
-    c->gate_ws_stride = (int64_t)sys_gate_doubles(m_max);
-    HIPCHK(c->gate_ws.reserve((size_t)c->gate_ws_stride * c->sys_grid));
-  } else {
-    c->gate_ws_stride = 0;
-  }
-  // ---- MSCKF fast path (k_feat.h): gate matrix in registers, several workgroups per CU
-  c->feat_variant = 0;
+  while (pl.m_lds_max < m_max && sys_gate_doubles(pl.m_lds_max + 1) * sizeof(double) <= limit - fixed) pl.m_lds_max++;
+  pl.sys_lds = fixed + sys_gate_doubles(pl.m_lds_max) * sizeof(double);
+  pl.sys_grid = std::max(1, std::min(F, c->num_cu * 4));
+  pl.gate_ws_stride = pl.m_lds_max < m_max ? (int64_t)sys_gate_doubles(m_max) : 0;
+  // (its panel routine, gate_chol_panel<8> of k_system.h, holds 512 rows of the gate's trapezoid in the registers of a wavefront's lanes and takes
+  // longer trapezoids 512 rows at a time, round 5: a track's length is bounded by the block-id / reflector tables in LDS above, far beyond any
+  // window; UpdaterMSCKF.cpp:216-222's dof >= 500 is reachable)
+  // ---- MSCKF fast path (k_feat.h): the fused kernels, a block of 16 nt x 64 whitened rows in LDS instead of the row copies and the T chunk
   // (an anchored feat_rep_msckf takes it as well — k_feat_rows_anchored, k_featy.h: 48-double records whatever c->row_stride says, which stays the
   //  general kernel's; ovgpu_debug_option "anchored_fast" = 0 keeps such batches on the general kernel)
   // (resident landmarks under the empty active set have no column: the same batch, the same column map and the same kernels as without them.  The
-  //  eligibility is recorded — lm_fast_ok below — and only ovgpu_msckf_update_lm switches it on: enqueue_system, api_pipeline.inc)
-  if (!slam_rows && !c->no_feat_kernel && (c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D || c->anchored_fast) && (c->L == 0 || c->lm_empty_set) && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16) {
+  //  eligibility is recorded — lm_fast_ok — and only ovgpu_msckf_update_lm switches it on: enqueue_system, api_pipeline.inc)
+  if (!c->slam_rows && !c->no_feat_kernel && (c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D || c->anchored_fast) && (c->L == 0 || c->lm_empty_set) && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16 &&
+      (size_t)4 * (14 * m1 + 64) * sizeof(double) <= limit) { // (the last: k_feat_vt's block, in front of every one of them)
     // the gate matrix of the one-pass kernels: 2 m + 4 rows (the right-hand sides [r | H_f] are four augmented rows, k_featy.h), upper triangle
     const int nt = (2 * m_max + 15) / 16, nta = (2 * m_max + 4 + 15) / 16, tiles = nta * (nta + 1) / 2;
-    // 1: <4 wavefronts, 9 tiles each>; 2: <8, 17> (one workgroup per CU: 256 registers per lane); up to two workgroups per CU
-    int variant = tiles <= 4 * 9 ? 1 : (tiles <= 8 * 17 ? 2 : 0);
-    if (c->feat_shape == 1 && tiles <= 4 * 9) variant = 1;
-    if (c->feat_shape == 2 && tiles <= 8 * 17) variant = 2;
-    c->feat_nta_max = nta;
-    if (variant) {
-      c->feat_variant = variant, c->feat_nt_max = nt; // confirmed against the fused kernel's own limits below
-    } else if (nt <= 29 && c->feat_shape == 0 && feat::featyb_lds_layout(nt, 8).total <= (size_t)c->lds_limit) {
-      // 3: the gate matrix does not fit the registers of a compute unit: block row by block row (k_featy_big.h; no legacy form)
-      c->feat_variant = 3, c->feat_nt_max = nt;
-    }
+    // <4 wavefronts, 9 tiles each>, or <8, 17> (one workgroup per CU: 256 registers per lane) — options.feature_kernel_shape = 2 asks for it where
+    // the first would do; beyond both the gate matrix does not fit the registers of a compute unit: block row by block row (k_featy_big.h)
+    FeatKernel k = tiles <= 4 * 9 && c->feat_shape != 2 ? FK_FEATY_4 : (tiles <= 8 * 17 ? FK_FEATY_8 : FK_FEATY_BIG);
+    const bool holds = k == FK_FEATY_BIG ? nt <= 29 && c->feat_shape == 0 && feat::featyb_lds_layout(nt, 8).total <= limit
+                                         : feat::featy_lds_layout(nt, nta, k == FK_FEATY_4 ? 4 : 8, feat::FY_CB).total <= limit;
+    if (holds) pl.msckf = k, pl.nt = nt, pl.nta = nta;
   }
-  // (the general kernel's panel routine, gate_chol_panel<8> of k_system.h, holds 512 rows of the gate's trapezoid in the registers of a
-  // wavefront's lanes and takes longer trapezoids 512 rows at a time, round 5; records that do not fit LDS go to a global workspace:
-  // a track's length is bounded by the block-id / reflector tables in LDS above, far beyond any window; UpdaterMSCKF.cpp:216-222's
-  // dof >= 500 is reachable)
-  c->featy_ok = false;
-  if (c->feat_variant) { // the fused form: block of 16 nt x 64 whitened rows in LDS instead of the row copies and the T chunk
-    const int nt = c->feat_nt_max, nw = c->feat_variant == 1 ? 4 : 8;
-    const feat::FeatYLds lo = feat::featy_lds_layout(nt, c->feat_nta_max, nw, feat::FY_CB);
-    const size_t vt_lds = (size_t)4 * (14 * std::max(m_max, 1) + 64) * sizeof(double);
-    if (c->feat_variant == 3) {
-      if (vt_lds <= (size_t)c->lds_limit) {
-        c->featy_ok = true, c->featy_lds = feat::featyb_lds_layout(nt, 8).total;
-        c->featy_grid = std::max(1, std::min(F, c->num_cu));
-        HIPCHK(c->featyb_ws.reserve((size_t)c->featy_grid * feat::featyb_ws_doubles(nt)));
-      } else {
-        c->feat_variant = 0;
-      }
-    } else if (lo.total <= (size_t)c->lds_limit && vt_lds <= (size_t)c->lds_limit && c->feat_nta_max * (c->feat_nta_max + 1) / 2 <= nw * (nw == 4 ? 9 : 17)) {
-      const int per_cu = nw == 4 ? std::max(1, std::min(2, (int)((size_t)c->lds_limit / lo.total))) : 1;
-      c->featy_ok = true, c->featy_lds = lo.total;
-      c->featy_grid = std::max(1, std::min(F, c->num_cu * per_cu));
-    } else {
-      c->feat_variant = 0; // the general kernel (k_system.h)
-    }
-  }
-  c->lm_fast_ok = c->L > 0 && c->feat_variant != 0 && c->featy_ok;
+  pl.lm_fast_ok = c->L > 0 && pl.msckf != FK_GENERAL;
   // ---- SLAM batches: the fused per-feature kernel k_slam_y (k_slam_y.h) behind ovgpu_debug_option "slam_fused", a level.  Eligible at level 1:
   // every landmark the batch observes is 3-dof (a batch that holds a single-depth landmark keeps the general kernel as a whole: its two
   // reflectors stay there), the longest track within the kernel's bound, and the fused kernels' limits on the state.  At level 2 a batch that
@@ -663,9 +619,8 @@ static int size_feature_stage(ovgpu_ctx *c) {
   // again once they are (slam_prepare).  Per-feature sigma / multiplier do not disqualify (ArUco corners).
   // Level 3 is level 2 with one addition: a batch whose longest track holds 63 .. 126 observations takes the long shape (16 tile rows, column
   // blocks of 32) on the same terms and its own carve; a batch of at most 62 takes the shapes of level 2.
-  c->slam_fused_ok = false, c->slam_fused_proj = false, c->slam_fused_long = false, c->slamy_lds = 0;
   const int slamy_mmax = c->slam_fused >= 3 ? slamy::SLY_MMAX_L : slamy::SLY_MMAX;
-  if (slam_rows && c->slam_fused && !c->no_feat_kernel && c->L > 0 && m_max <= slamy_mmax && c->D >= 16 && c->K * c->C <= 8192) {
+  if (c->slam_rows && c->slam_fused && !c->no_feat_kernel && c->L > 0 && m_max <= slamy_mmax && c->D >= 16 && c->K * c->C <= 8192) {
     const int udof = lm_uniform_dof(c);
     bool dof3 = udof == 3, named = udof != 0;
     if (udof == 0 && (int)b.h_feat_lm.size() == F) {
@@ -674,13 +629,27 @@ static int size_feature_stage(ovgpu_ctx *c) {
     }
     const bool proj = named && !dof3 && c->slam_fused >= 2;
     const bool lng = m_max > slamy::SLY_MMAX;
-    const size_t lds = slamy::slamy_lds_layout(std::max(m_max, 1), proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total;
-    if ((dof3 || proj) && lds <= (size_t)c->lds_limit) c->slam_fused_ok = true, c->slam_fused_proj = proj, c->slam_fused_long = lng, c->slamy_lds = lds;
+    const size_t lds = slamy::slamy_lds_layout(m1, proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total;
+    if ((dof3 || proj) && lds <= limit) pl.slam = FeatKernel((lng ? FK_SLAMY_LONG : FK_SLAMY) + (proj ? 1 : 0)), pl.slam_lds = lds;
   }
-  if (c->feat_variant) { // row store of the fast path
+  return pl;
+}
+
+// Sizes the per-feature stage for the batch in force and its row layout: the plan above, the workspaces it implies, the fused kernels' slot
+// records, the stack and the TSQR leaf layout.  Reads the batch, writes none of it.
+static int size_feature_stage(ovgpu_ctx *c) {
+  const Batch b = batch_of(c);
+  const int F = b.F, m1 = std::max(b.m_max, 1);
+  const FeatPlan pl = plan_feature_stage(c, b);
+  if (pl.error) return set_err(OVGPU_ERR_CAPACITY, pl.error);
+  c->plan = pl;
+  if (pl.rows_global) HIPCHK(c->sys_rows_ws.reserve((size_t)pl.sys_grid * m1 * c->row_stride));
+  if (pl.gate_ws_stride) HIPCHK(c->gate_ws.reserve((size_t)pl.gate_ws_stride * pl.sys_grid));
+  if (pl.msckf == FK_FEATY_BIG) HIPCHK(c->featyb_ws.reserve((size_t)std::max(1, std::min(F, c->num_cu)) * feat::featyb_ws_doubles(pl.nt)));
+  if (pl.msckf != FK_GENERAL) { // row store of the fast path
     const int M = std::max(b.M, 1);
     HIPCHK(c->fs_tq.reserve((size_t)std::max(F, 1) * 8));
-    HIPCHK(c->fs_inst.reserve((size_t)std::max(F, 1) * std::max(c->feat_nt_max, 1) * feat::FY_ISTR));
+    HIPCHK(c->fs_inst.reserve((size_t)std::max(F, 1) * std::max(pl.nt, 1) * feat::FY_ISTR));
     HIPCHK(c->fs_rows.reserve((size_t)M * c->row_stride));
     HIPCHK(c->fs_minfo.reserve((size_t)M * 8));
     HIPCHK(c->fs_V.reserve((size_t)M * 6));

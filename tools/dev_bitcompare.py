@@ -1,5 +1,6 @@
 """Two builds of libovgpu.so must give the SAME BYTES: `dump <out.npz>` runs a list of MSCKF updates that reach the fused per-feature
-kernel of the headline shape (feat::k_feat_y<4, 11, 2>, both stack precisions) and the other per-feature kernels through the library
+kernel of the headline shape (feat::k_feat_y<4, 11, 2>, both stack precisions) and the other per-feature kernels — the ones only
+ovgpu_debug_option "featy_big" and options.feature_kernel_shape reach included — through the library
 in the tree and stores every output; `compare <a.npz> <b.npz>` compares two such files bit for bit.  Used when a build changes
 nothing but instruction ORDER (a scheduler strategy, ovgpu_featy_tu.hip): no tolerance applies, and no oracle time is spent
 (tools/gpu_bitcompare.sh swaps the library files on one box).  `dump` also runs the entries that read the resident feature batch on
@@ -13,6 +14,17 @@ sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 
 
 def shapes():
+    """(name, synth.make_problem keywords, options, ovgpu_debug_option settings made before the batch is handed over)"""
+    for name, pk, ok in default_shapes():
+        yield name, pk, ok, {}
+    # the per-feature kernels only a switch reaches: k_feat_y_big<8, 17> / <8, 5> on batches the one-pass kernel holds, k_feat_y<8, 17> on one that <4, 9> holds
+    for big in (1, 2):
+        yield f"14_clones_featy_big{big}", dict(cfg=2, F=60, C=14), {}, dict(featy_big=big)
+        yield f"mono_12_clones_featy_big{big}", dict(cfg=2, F=120, C=12, K=1), {}, dict(featy_big=big)
+    yield "cfg2_200_kernel_shape2", dict(cfg=2, F=200), dict(feature_kernel_shape=2), {}
+
+
+def default_shapes():
     from open_vins_amd import capi
     R = capi
     yield "cfg2_400", dict(cfg=2, F=400), {}
@@ -127,13 +139,16 @@ def batch_scenarios(out):
 
 def fused_scenarios(path, level):
     """ovgpu_slam_update and ovgpu_slam_update_chunked with "slam_fused" = level: fifteen landmarks of the five 3-dof representations (every batch
-    takes k_slam_y<false> from level 1 on), and twelve of all six (k_system_t at level 1, k_slam_y<true> at level 2)."""
+    takes k_slam_y<false> from level 1 on), and twelve of all six (k_system_t at level 1, k_slam_y<true> at level 2); on the four-camera rig (30 clones,
+    tracks of up to 120 observations) ten of the 3-dof representations and twelve of all six: k_system_t up to level 2, the long shapes of k_slam_y
+    (kernels 6 and 7) at level 3."""
     from open_vins_amd import capi, synth
     from open_vins_amd.updater import UpdaterMSCKF
     opts = capi.default_options(chi2_multipler=1.0)
     out = {}
-    for tag, reps in (("3dof", (0, 1, 2, 3, 4) * 3), ("six", REPS6 * 2)):
-        p = synth.make_slam_problem(2, L=len(reps), lm_rep=np.array(reps, np.int32), seed=3)
+    for tag, reps, rig in (("3dof", (0, 1, 2, 3, 4) * 3, {}), ("six", REPS6 * 2, {}), ("long_3dof", (0, 1, 2, 3, 4) * 2, dict(C=30, K=4)), ("long_six", REPS6 * 2, dict(C=30, K=4))):
+        p = synth.make_slam_problem(2, L=len(reps), lm_rep=np.array(reps, np.int32), seed=3, **rig)
+        assert not rig or int(np.diff(p.meas_offsets).max()) >= 63, "the long state holds no track of 63 observations"
         for entry in ("update", "chunked"):
             up = UpdaterMSCKF(opts, device=0)
             up.debug_option("slam_fused", level)
@@ -152,7 +167,7 @@ def prepare(path):
     import pickle
     from open_vins_amd import synth
     probs = {}
-    for name, pk, _ in shapes():
+    for name, pk, *_ in shapes():
         pk = dict(pk)
         probs[name] = synth.make_problem(pk.pop("cfg"), **pk)
     with open(path, "wb") as f:
@@ -165,13 +180,16 @@ def dump(path, problems=None):
     from open_vins_amd.updater import UpdaterMSCKF
     probs = pickle.load(open(problems, "rb")) if problems else {}
     out = {}
-    for name, pk, ok in shapes():
+    for name, pk, ok, debug in shapes():
         pk = dict(pk)
         prob = probs[name] if name in probs else synth.make_problem(pk.pop("cfg"), **pk)
         opts = capi.default_options(**{"chi2_multipler": 1.0, **ok})
         up = UpdaterMSCKF(opts, device=0)
+        for k, v in debug.items():
+            up.debug_option(k, v)
         up.set_problem(prob)
         res = up.update()
+        out[f"{name}.kernel"] = np.array([up.debug_option("last_feature_kernel")])
         for k in ("feat_status", "chi2", "chi2_thresh", "p_FinG", "dx", "P", "clone_q_p", "calib_q_p", "intrinsics"):
             if k in res:
                 out[f"{name}.{k}"] = np.ascontiguousarray(res[k])
