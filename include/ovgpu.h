@@ -1241,6 +1241,10 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             H_f = A dl at the p_FinG the anchor gives and no anchor blocks, which the nullspace projection annihilates
  *                             (k_featy.h: k_feat_rows_anchored) — the same update to rounding; 0: the general kernel with its 72-double
  *                             records, as before; takes effect with the next ovgpu_set_features
+ *   "live_allocations" / "live_allocation_bytes"  (read only) the allocations of this library still alive in the PROCESS, device and page-locked
+ *                             memory together, and their bytes as requested (a buffer of n elements counts max(n, 1) elements).  The same values
+ *                             from any context: a context that was destroyed has given back everything it held, so both return to what they
+ *                             were before it was created (tests/test_gpu_context_frees.py)
  *   "raw_gram_tile_rows"      (read only) rows x tiles summed over the regions of the resident batch: the 16 x 16 products per row k_gram_regions executes
  *   "speculative_prior"       (round 6, default 1) ovgpu_set_features starts the prior block's factorisation on the second stream, next to its own
  *                             uploads; the update joins it.  0: the factorisation starts with the update (round 5)

@@ -18,55 +18,58 @@ static int set_err(int code, const std::string &msg) {
 
 namespace {
 
-// page-locked host staging (read-backs that complete with the stream's next synchronisation instead of one blocking copy each)
-template <class T>
-struct PinBuf {
-  T *p = nullptr;
-  size_t cap = 0; // elements
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault);
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr, cap = 0;
-  }
+// The two allocation policies of OwnedBuf (dev_buf.h).  Each counts what it has handed out and not taken back, process-wide: allocations and
+// bytes as requested (ovgpu_debug_option "live_allocations" / "live_allocation_bytes" report the sums).
+struct AllocCount {
+  std::atomic<int64_t> n{0}, bytes{0};
+  void add(size_t b) { n.fetch_add(1, std::memory_order_relaxed), bytes.fetch_add((int64_t)b, std::memory_order_relaxed); }
+  void sub(size_t b) { n.fetch_sub(1, std::memory_order_relaxed), bytes.fetch_sub((int64_t)b, std::memory_order_relaxed); }
 };
+struct DeviceAlloc {
+  using Err = hipError_t;
+  static constexpr Err ok = hipSuccess;
+  static inline AllocCount live;
+  static Err alloc(void **p, size_t bytes) {
+    const Err e = hipMalloc(p, bytes);
+    if (e == hipSuccess) live.add(bytes);
+    return e;
+  }
+  static void free(void *p, size_t bytes) { (void)hipFree(p), live.sub(bytes); }
+  static Err copy(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice); }
+};
+// page-locked host staging (read-backs that complete with the stream's next synchronisation instead of one blocking copy each)
+struct PinnedAlloc {
+  using Err = hipError_t;
+  static constexpr Err ok = hipSuccess;
+  static inline AllocCount live;
+  static Err alloc(void **p, size_t bytes) {
+    const Err e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) live.add(bytes);
+    return e;
+  }
+  static void free(void *p, size_t bytes) { (void)hipHostFree(p), live.sub(bytes); }
+};
+template <class T> using DevBuf = OwnedBuf<T, DeviceAlloc>;
+template <class T> using PinBuf = OwnedBuf<T, PinnedAlloc>;
 
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0; // elements
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  // like reserve, but the first `keep` elements survive a reallocation
-  hipError_t grow(size_t n, size_t keep) {
-    if (n <= cap) return hipSuccess;
-    T *q = nullptr;
-    hipError_t e = hipMalloc((void **)&q, n * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (p && keep > 0) e = hipMemcpy(q, p, std::min(keep, cap) * sizeof(T), hipMemcpyDeviceToDevice);
-    if (p) (void)hipFree(p);
-    p = q, cap = n;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
+// Owning handles of an event and of a stream: empty until create(), destroyed with their owner, read as the plain handle.
+struct Event {
+  hipEvent_t h = nullptr;
+  Event() = default;
+  ~Event() { if (h) (void)hipEventDestroy(h); }
+  Event(const Event &) = delete;
+  Event &operator=(const Event &) = delete;
+  Event(Event &&o) noexcept : h(o.h) { o.h = nullptr; } // (the vectors of stage timers grow)
+  hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&h, flags); }
+  operator hipEvent_t() const { return h; }
+};
+struct Stream {
+  hipStream_t h = nullptr;
+  Stream() = default;
+  ~Stream() { if (h) (void)hipStreamDestroy(h); }
+  Stream(const Stream &) = delete;
+  Stream &operator=(const Stream &) = delete;
+  operator hipStream_t() const { return h; }
 };
 
 // a window into another buffer's allocation (the words of the control block): nothing to reserve, grow or release
@@ -103,7 +106,7 @@ struct Batch {
 };
 
 struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
 };
 
 } // namespace
@@ -172,7 +175,7 @@ __global__ void __launch_bounds__(256) k_upload_scatter(const unsigned char *__r
 
 struct ovgpu_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   ovgpu_options opts{};
   DevOptions dopt{};
   int lds_limit = 160 * 1024;
@@ -314,12 +317,12 @@ struct ovgpu_ctx {
                                               // compression and the cross-GPU merge alternate in the sharded update)
   int tree_G2 = 0;
   // leaf / tree overlap: the merge tree runs on a second stream next to the leaf kernel's last append
-  hipStream_t stream2 = nullptr; // (round 5: the single-launch Cholesky's carried columns are blocks of the same launch — the helper stream and the events around it are gone)
-  hipEvent_t ev_rows = nullptr;
+  Stream stream2; // (round 5: the single-launch Cholesky's carried columns are blocks of the same launch — the helper stream and the events around it are gone)
+  Event ev_rows;
   bool gram_il = true;              // ovgpu_debug_option "gram_interleaved": k_gram_il (staging between the matrix instructions) instead of k_gram
   bool gram_blocks_only = false;    // ovgpu_debug_option "gram_blocks_only": the block variant (k_gram_blk) also where k_gram_wide applies
   bool fuse_chol_inputs = true;     // ovgpu_debug_option "fuse_chol_inputs": the factorisations read their inputs at the source (no k_tf_gather / k_tf_abh)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  Event ev_fork, ev_join;
   DevBuf<int32_t> leaf_flags; // [W] panels of the last append finished by each leaf node
   int tree_overlap = -1; // -1: only when leaves and merge nodes all get a CU of their own; 0 / 1 force it (OVGPU_TSQR_OVERLAP)
   bool tree_nodes_overlap = false, tree_nodes2_overlap = false; // dependency flavour the cached trees were built with
@@ -659,19 +662,33 @@ static long long *tree_dbg_buffer() {
 #endif
 }
 
+// The kernel, with its dynamic-LDS bound raised to what the device allows on the context's device: the only place that sets the attribute.  The
+// bound is the workgroup's limit (c->lds_limit) less the kernel's own static LDS: a bound that does not fit next to static arrays is refused, and
+// the launch after it as well (none of the kernels that come through here has any today).  HIP keeps the attribute per kernel AND per device, so the latch is one per
+// kernel (this template's static) with a bit per device; the device is current at every launch site (the entry points' hipSetDevice).  Two threads
+// that meet a kernel's first launch together both set it — harmless — and nobody launches before it is set.  Devices beyond 63 have no bit: set
+// every time.
+template <auto KERN>
+static decltype(KERN) with_max_lds(const ovgpu_ctx *c) {
+  static std::atomic<uint64_t> set_on{0};
+  const uint64_t bit = (unsigned)c->device < 64 ? (uint64_t)1 << c->device : 0;
+  if (!(set_on.load(std::memory_order_acquire) & bit)) {
+    hipFuncAttributes fa{};
+    const int own = hipFuncGetAttributes(&fa, (const void *)KERN) == hipSuccess ? (int)fa.sharedSizeBytes : 0;
+    (void)hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit - own);
+    set_on.fetch_or(bit, std::memory_order_release);
+  }
+  return KERN;
+}
+
 static constexpr int QR_B = 32;  // row block of the generic fallback kernel (D + 1 > 256 columns)
 static constexpr int QR_LEAF_Q = 32; // leaf nodes fold 4 * 32 = 128 dense rows per append
 
 template <int QH, bool TRI>
 static int launch_qr_node(ovgpu_ctx *c, int nodes, const QrNodeParams &q) {
   const size_t lds = qr_node_lds_bytes(q.NT, QH);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void *)k_qr_node<QH, TRI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
   const int NW = (q.NT + 1) / 2;
-  hipLaunchKernelGGL((k_qr_node<QH, TRI>), dim3(nodes), dim3(64 * NW), lds, c->stream, q);
+  hipLaunchKernelGGL((with_max_lds<k_qr_node<QH, TRI>>(c)), dim3(nodes), dim3(64 * NW), lds, c->stream, q);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
@@ -680,13 +697,8 @@ static int launch_qr_node(ovgpu_ctx *c, int nodes, const QrNodeParams &q) {
 template <int QH>
 static int launch_qr_leaf_pw(ovgpu_ctx *c, int nodes, const QrNodeParams &q) {
   const size_t lds = pw::qr_node_lds_bytes(q.NT, QH);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void *)pw::k_qr_node<QH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
   const int NW = pw::qr_node_bulk_waves(q.NT) + 1;
-  hipLaunchKernelGGL((pw::k_qr_node<QH, false>), dim3(nodes), dim3(64 * NW), lds, c->stream, q);
+  hipLaunchKernelGGL((with_max_lds<pw::k_qr_node<QH, false>>(c)), dim3(nodes), dim3(64 * NW), lds, c->stream, q);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
@@ -695,36 +707,25 @@ static int launch_qr_leaf_pw(ovgpu_ctx *c, int nodes, const QrNodeParams &q) {
 template <int QH>
 static int launch_qr_tree(ovgpu_ctx *c, int nodes, const QrTreeParams &q, hipStream_t ts) {
   const size_t lds = qr_node_lds_bytes(q.NT, QH);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void *)k_qr_tree<QH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
   const int NW = (q.NT + 1) / 2;
-  hipLaunchKernelGGL((k_qr_tree<QH>), dim3(nodes), dim3(64 * NW), lds, ts, q);
+  hipLaunchKernelGGL((with_max_lds<k_qr_tree<QH>>(c)), dim3(nodes), dim3(64 * NW), lds, ts, q);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
 
-template <int NTC> static void launch_gram(int G, const gram::GramParams &g, hipStream_t s, bool interleaved) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void *)gram::k_gram<NTC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if constexpr (NTC <= 15) (void)hipFuncSetAttribute((const void *)gram::k_gram_il<NTC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
-  }
+template <int NTC> static void launch_gram(const ovgpu_ctx *c, int G, const gram::GramParams &g, hipStream_t s, bool interleaved) {
   // staging inside the matrix-instruction stream (k_gram_il) up to 15 tile columns (15 — BASELINE configs[3]'s 237 columns — since round 6: 30
   // accumulator tiles per wavefront instead of the 34 of the 16-column grid it used to run on, a whole tile column of zeros); with 16 the 34
   // accumulator tiles + staged elements + hoisted LDS operands exceed the 512 registers of a wavefront (1.1 KB of scratch per lane) and k_gram stays
+  auto kern = with_max_lds<gram::k_gram<NTC>>(c);
   if constexpr (NTC <= 15) {
-    if (interleaved) {
-      hipLaunchKernelGGL(gram::k_gram_il<NTC>, dim3(G), dim3(256), gram::gram_lds_bytes(), s, g);
-      return;
-    }
+    if (interleaved) kern = with_max_lds<gram::k_gram_il<NTC>>(c);
   }
-  hipLaunchKernelGGL(gram::k_gram<NTC>, dim3(G), dim3(256), gram::gram_lds_bytes(), s, g);
+  hipLaunchKernelGGL(kern, dim3(G), dim3(256), gram::gram_lds_bytes(), s, g);
 }
 
+// (this launcher keeps its own latch, once per PROCESS, and its own bound of 128 KB: the kernel has static LDS next to the dynamic part — 160 KB
+// are refused — and its move to with_max_lds is left out: DESIGN.md section 7, "Context buffers free themselves")
 template <int NB> static void launch_gram_pchol(hipStream_t s, int D, int LD, int LG, const double *G, double *out, int32_t *dropped, double tol) {
   static bool attr_done = false;
   if (!attr_done) {

@@ -127,6 +127,10 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->row_stride;
   } else if (n == "sys_lds_bytes") { // the dynamic LDS size of the kernel's launch
     if (old_value) *old_value = (int64_t)c->plan.sys_lds;
+  } else if (n == "live_allocations") { // read-only, this and the one below: what the library's buffers (OwnedBuf) hold in this PROCESS, device and page-locked memory together, whatever the context asked
+    if (old_value) *old_value = DeviceAlloc::live.n.load() + PinnedAlloc::live.n.load();
+  } else if (n == "live_allocation_bytes") { // ... in bytes as requested: max(n, 1) elements each
+    if (old_value) *old_value = DeviceAlloc::live.bytes.load() + PinnedAlloc::live.bytes.load();
   } else if (n == "chol_timeouts") { // read-only counter: updates repeated with the step-wise Cholesky after a follower timed out
     if (old_value) *old_value = c->chol_timeouts;
   } else {
@@ -211,8 +215,10 @@ int ovgpu_debug_box_probe(ovgpu_ctx *c, double *out3) { // (out3: six values, se
   if (!c || !out3) return set_err(OVGPU_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  long long *d = nullptr, h[3] = {0, 0, 0};
-  HIPCHK(hipMalloc((void **)&d, 3 * sizeof(long long)));
+  long long h[3] = {0, 0, 0};
+  DevBuf<long long> d_buf;
+  HIPCHK(d_buf.reserve(3));
+  long long *d = d_buf.p;
   for (int rep = 0; rep < 2; rep++) { // (the first launch wakes the clocks up)
     hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, s, d, 20000);
     HIPCHK(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -228,24 +234,23 @@ int ovgpu_debug_box_probe(ovgpu_ctx *c, double *out3) { // (out3: six values, se
   }
   const struct { size_t bytes; int stride; } probes[2] = {{(size_t)1 << 20, 32}, {(size_t)256 << 20, 1024}}; // 128-byte slots in 1 MB; 4 KB slots in 256 MB
   for (int k = 0; k < 2; k++) {
-    int32_t *buf = nullptr;
-    if (hipMalloc((void **)&buf, probes[k].bytes) != hipSuccess) {
+    DevBuf<int32_t> chase;
+    if (chase.reserve(probes[k].bytes / sizeof(int32_t)) != hipSuccess) {
       out3[1 + k] = 0.0;
       continue;
     }
+    int32_t *buf = chase.p;
     const int n = (int)(probes[k].bytes / (sizeof(int32_t) * probes[k].stride)), hops = 2000;
     hipLaunchKernelGGL(k_chase_init, dim3((n + 255) / 256), dim3(256), 0, s, buf, n, probes[k].stride, k == 0 ? 2731 : 24571);
     hipLaunchKernelGGL(k_chase, dim3(1), dim3(64), 0, s, (const int32_t *)buf, probes[k].stride, hops, d);
     HIPCHK(hipMemcpyAsync(h, d, 2 * sizeof(long long), hipMemcpyDeviceToHost, s));
     HIPCHK(upload_sync(c, s));
     out3[1 + k] = 10.0 * (double)h[0] / hops; // the reference counter ticks at 100 MHz
-    (void)hipFree(buf);
   }
-  (void)hipFree(d);
   { // the command processor: 200 dependent empty launches on one stream (us per launch), one launch of 65 536 empty workgroups (ns per workgroup)
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    Event e0, e1;
+    HIPCHK(e0.create());
+    HIPCHK(e1.create());
     float ms = 0.f;
     for (int i = 0; i < 20; i++) hipLaunchKernelGGL(k_probe_empty, dim3(1), dim3(64), 0, s, (int *)nullptr);
     HIPCHK(hipEventRecord(e0, s));
@@ -260,14 +265,13 @@ int ovgpu_debug_box_probe(ovgpu_ctx *c, double *out3) { // (out3: six values, se
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     out3[5] = 1e6 * ms / 65536.0;
-    (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
   }
   return OVGPU_OK;
 }
 
 int ovgpu_last_update_route(ovgpu_ctx *c) { return c ? c->last_route : -1; }
 
-uint64_t ovgpu_stream(ovgpu_ctx *c) { return c ? (uint64_t)(uintptr_t)c->stream : 0; }
+uint64_t ovgpu_stream(ovgpu_ctx *c) { return c ? (uint64_t)(uintptr_t)c->stream.h : 0; }
 
 #ifdef QR_PROFILE
 int ovgpu_debug_tree_times(long long *out1024) {

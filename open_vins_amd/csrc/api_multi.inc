@@ -66,8 +66,8 @@ int nccl_err(int rc, const char *what) {
 struct LoopComm {
   int G = 0;
   std::vector<ovgpu_ctx *> ranks;
-  std::vector<hipEvent_t> ready;
-  hipEvent_t done = nullptr;
+  std::vector<Event> ready;
+  Event done;
   DevBuf<double> sum;
 };
 struct LoopPtrs {
@@ -289,9 +289,9 @@ int ovgpu_multi_create(const ovgpu_options *opts, int n, const int *devices, ovg
   }
   if (n > 1 && repeated) { // several ranks on one device: the loop-back collective (see LoopComm)
     LoopComm *L = new LoopComm();
-    L->G = n, L->ranks = m->ctx, L->ready.resize(n, nullptr);
-    bool ok = hipEventCreateWithFlags(&L->done, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < n; i++) ok = ok && hipEventCreateWithFlags(&L->ready[i], hipEventDisableTiming) == hipSuccess;
+    L->G = n, L->ranks = m->ctx, L->ready.resize(n);
+    bool ok = L->done.create(hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < n; i++) ok = ok && L->ready[i].create(hipEventDisableTiming) == hipSuccess;
     if (!ok) {
       for (auto *x : m->ctx) ovgpu_destroy(x);
       delete L;
@@ -322,12 +322,7 @@ void ovgpu_multi_destroy(ovgpu_multi *m) {
     c->loop = nullptr;
     ovgpu_destroy(c);
   }
-  if (m->loop) {
-    for (auto e : m->loop->ready)
-      if (e) (void)hipEventDestroy(e);
-    if (m->loop->done) (void)hipEventDestroy(m->loop->done);
-    delete m->loop;
-  }
+  delete m->loop; // (every rank's streams are idle: its sum buffer and events go with it)
   delete m;
 }
 

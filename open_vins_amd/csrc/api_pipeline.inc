@@ -29,7 +29,7 @@ static int enqueue_triangulate(ovgpu_ctx *c, const double *seed_pA = nullptr, co
       }
     }
   }
-  hipLaunchKernelGGL(k_triangulate, dim3((b.F + wpb - 1) / wpb), dim3(64 * wpb), lds, c->stream, p);
+  hipLaunchKernelGGL(with_max_lds<k_triangulate>(c), dim3((b.F + wpb - 1) / wpb), dim3(64 * wpb), lds, c->stream, p);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
@@ -90,17 +90,7 @@ static FeatLaunch select_feat_kernel(const ovgpu_ctx *c, const SysParams &p, int
   return s;
 }
 
-extern "C++" {
-// KERN, its maximum dynamic LDS raised to the context's limit before its first launch: once per kernel and process
-template <auto KERN>
-static decltype(KERN) with_max_lds(const ovgpu_ctx *c) {
-  static const hipError_t once = hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-  (void)once;
-  return KERN;
-}
-} // extern "C++"
-
-// The one launch of the per-feature stage: a row per instantiation (k_system_t's LDS attribute is ovgpu_create's)
+// The one launch of the per-feature stage: a row per instantiation
 static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams &p) {
   const dim3 grid(s.grid), slam_block(64 * slamy::SLY_NW);
   const int nt = c->plan.nt, nta = c->plan.nta;
@@ -108,6 +98,8 @@ static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams
   const int32_t *sm = c->fs_minfo.p, *sin = c->fs_inst.p, *ssl = c->fs_slots.p, *runs = c->raw_runs.p;
   double *bws = c->featyb_ws.p;
   switch (feat_key(s.kernel, s.f32, s.ch, s.alt)) {
+    case feat_key(FK_GENERAL): hipLaunchKernelGGL(with_max_lds<k_system_t<false>>(c), grid, dim3(SYS_NT), s.lds, c->stream, p); break;
+    case feat_key(FK_GENERAL, false, false, true): hipLaunchKernelGGL(with_max_lds<k_system_t<true>>(c), grid, dim3(SYS_NT), s.lds, c->stream, p); break;
 #define X(NW, TPW, OCC, F32, CB, CH) case feat_key(NW == 4 ? FK_FEATY_4 : FK_FEATY_8, F32, CH): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y<NW, TPW, OCC, F32, CB, CH>>(c)), grid, dim3(64 * NW), s.lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl, runs); break;
     OVG_FEATY_SHAPES(X)
 #undef X
@@ -118,8 +110,6 @@ static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams
     case feat_key(FK_SLAMY_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true>>(c)), grid, slam_block, s.lds, c->stream, p); break;
     case feat_key(FK_SLAMY_LONG): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
     case feat_key(FK_SLAMY_LONG_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
-    case feat_key(FK_GENERAL, false, false, true): hipLaunchKernelGGL(k_system_t<true>, grid, dim3(SYS_NT), s.lds, c->stream, p); break;
-    case feat_key(FK_GENERAL): hipLaunchKernelGGL(k_system_t<false>, grid, dim3(SYS_NT), s.lds, c->stream, p); break;
     default: return set_err(OVGPU_ERR_INVALID, "internal: the per-feature stage has no kernel in the shape selected");
   }
   HIPCHK(hipGetLastError());
@@ -326,14 +316,9 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     const int64_t by_cus = std::min<int64_t>((2 * c->num_cu + P - 1) / P, (rows_total + 127) / 128);
     const int Gw = (int)std::max<int64_t>(1, std::max(by_rows, by_cus));
     HIPCHK(c->gram32_part.reserve((size_t)P * Gw * gram32::G32_NW * gram32::G32_MAXT * 1024));
-    static bool attr32 = false;
-    if (!attr32) {
-      (void)hipFuncSetAttribute((const void *)gram32::k_gram_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr32 = true;
-    }
     gram32::Gram32Params q;
     q.H = c->Hbig32.p, q.part = c->gram32_part.p, q.tiles = c->gram32_tiles.p, q.rows_total = rows_total, q.LDF = LDF, q.LD = LD;
-    hipLaunchKernelGGL(gram32::k_gram_f32, dim3(Gw, P), dim3(gram32::G32_NTH), gram32::gram32_lds_bytes(LDF), c->stream, q);
+    hipLaunchKernelGGL(with_max_lds<gram32::k_gram_f32>(c), dim3(Gw, P), dim3(gram32::G32_NTH), gram32::gram32_lds_bytes(LDF), c->stream, q);
     hipLaunchKernelGGL(gram32::k_gram_f32_reduce, dim3(slots, 4), dim3(256), 0, c->stream, (const int32_t *)c->gram32_tiles.p, Gw,
                        (const float *)c->gram32_part.p, c->gram_G.p, LG);
     HIPCHK(hipGetLastError());
@@ -342,13 +327,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   }
   if (c->last_stack_raw) { // the unprojected stack, region by region (k_gram.h: k_gram_regions), the dropped rows' region subtracted in the reduction
     HIPCHK(c->gram_part.reserve((size_t)std::max(c->gram_wg_tiles, 1) * 256));
-    static bool attr_r = false;
-    if (!attr_r) {
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_regions<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_regions<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_r = true;
-    }
-    hipLaunchKernelGGL(c->gram_read_ahead ? gram::k_gram_regions<true> : gram::k_gram_regions<false>, dim3(c->gram_wg_n), dim3(256), gram::gram_lds_bytes(), c->stream,
+    hipLaunchKernelGGL(c->gram_read_ahead ? with_max_lds<gram::k_gram_regions<true>>(c) : with_max_lds<gram::k_gram_regions<false>>(c), dim3(c->gram_wg_n), dim3(256), gram::gram_lds_bytes(), c->stream,
                        (const double *)c->Hraw.p, (const gram::GramRegionWG *)c->gram_wg.p, c->gram_part.p);
     hipLaunchKernelGGL(gram::k_gram_regions_reduce, dim3(NP, 256 / gram::RR_E), dim3(gram::RR_E * gram::RR_G), 0, c->stream, NT, D, c->raw_rs,
                        (const gram::GramRegionWG *)c->gram_wg.p, c->gram_wg_n, (const double *)c->gram_part.p, c->gram_G.p);
@@ -359,15 +338,9 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   gram::GramParams g;
   g.LD = LD, g.NT = NT, g.rows_total = rows_total, g.H = c->Hbig.p, g.part = c->gram_part.p;
   if (NT == gram::GR_NT + 7 && !c->gram_fp32 && !c->gram_blocks_only) { // configs[4]'s 23 tile columns: two passes over the stack (k_gram_wide)
-    static bool attr_w = false;
-    if (!attr_w) {
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_wide_top<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_wide_win<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_w = true;
-    }
     const int Gw = G; // (every workgroup of either kernel writes its own tiles of partial blockIdx.x)
-    hipLaunchKernelGGL(gram::k_gram_wide_top<7>, dim3(Gw), dim3(256), gram::gram_wide_top_lds_bytes(), c->stream, g);
-    hipLaunchKernelGGL(gram::k_gram_wide_win<7>, dim3(Gw), dim3(256), gram::gram_lds_bytes(), c->stream, g);
+    hipLaunchKernelGGL(with_max_lds<gram::k_gram_wide_top<7>>(c), dim3(Gw), dim3(256), gram::gram_wide_top_lds_bytes(), c->stream, g);
+    hipLaunchKernelGGL(with_max_lds<gram::k_gram_wide_win<7>>(c), dim3(Gw), dim3(256), gram::gram_lds_bytes(), c->stream, g);
     hipLaunchKernelGGL(gram::k_gram_reduce, dim3(NP), dim3(1024), 0, c->stream, NT, Gw, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
     c->last_gram_kernel = 3;
@@ -377,30 +350,24 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     const int NB = (NT + gram::GB_T - 1) / gram::GB_T, pairs = NB * (NB + 1) / 2;
     HIPCHK(c->gram_part.reserve((size_t)pairs * G * gram::GB_T * gram::GB_T * 256));
     g.part = c->gram_part.p;
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_blk<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void *)gram::k_gram_blk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done = true;
-    }
-    if (c->gram_fp32) hipLaunchKernelGGL(gram::k_gram_blk<true>, dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes() / 2, c->stream, g, NB);
-    else hipLaunchKernelGGL(gram::k_gram_blk<false>, dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes(), c->stream, g, NB);
+    if (!c->gram_fp32) hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<false>>(c), dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes(), c->stream, g, NB);
+    else hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<true>>(c), dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes() / 2, c->stream, g, NB);
     hipLaunchKernelGGL(gram::k_gram_blk_reduce, dim3(gram::GB_T * gram::GB_T, pairs), dim3(256), 0, c->stream, NB, NT, G, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
     c->last_gram_kernel = 2;
     return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: up to 383 columns, k_gram_pchol<9 .. 12>)
   }
   switch ((NT + 1) / 2) {
-  case 1: launch_gram<2>(G, g, c->stream, c->gram_il); break;
-  case 2: launch_gram<4>(G, g, c->stream, c->gram_il); break;
-  case 3: launch_gram<6>(G, g, c->stream, c->gram_il); break;
-  case 4: launch_gram<8>(G, g, c->stream, c->gram_il); break;
-  case 5: launch_gram<10>(G, g, c->stream, c->gram_il); break;
-  case 6: launch_gram<12>(G, g, c->stream, c->gram_il); break;
-  case 7: launch_gram<14>(G, g, c->stream, c->gram_il); break;
+  case 1: launch_gram<2>(c, G, g, c->stream, c->gram_il); break;
+  case 2: launch_gram<4>(c, G, g, c->stream, c->gram_il); break;
+  case 3: launch_gram<6>(c, G, g, c->stream, c->gram_il); break;
+  case 4: launch_gram<8>(c, G, g, c->stream, c->gram_il); break;
+  case 5: launch_gram<10>(c, G, g, c->stream, c->gram_il); break;
+  case 6: launch_gram<12>(c, G, g, c->stream, c->gram_il); break;
+  case 7: launch_gram<14>(c, G, g, c->stream, c->gram_il); break;
   default:
-    if (NT == 15) launch_gram<15>(G, g, c->stream, c->gram_il); // (the one odd count with a grid of its own: configs[3], D = 236)
-    else launch_gram<16>(G, g, c->stream, c->gram_il);
+    if (NT == 15) launch_gram<15>(c, G, g, c->stream, c->gram_il); // (the one odd count with a grid of its own: configs[3], D = 236)
+    else launch_gram<16>(c, G, g, c->stream, c->gram_il);
     break;
   }
   hipLaunchKernelGGL(gram::k_gram_reduce, dim3(NP), dim3(1024), 0, c->stream, NT, G, c->gram_part.p, c->gram_G.p);
@@ -560,13 +527,8 @@ static int launch_chol_fused(ovgpu_ctx *c, chol::CholParams &q, int slot, hipStr
   q.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot, q.uinv = c->chol_uinv.p + (size_t)slot * 16 * 256, q.err = q.flags + 2, q.dbg = c->dbg_cycles.p;
   q.spin_limit = c->chol_spin_limit, q.n_arrive = chol::chol_tile_waves((q.D + 15) / 16);
   c->last_uinv = q.uinv;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)chol::k_chol_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chol::chol_lds_bytes());
-    attr = true;
-  }
   const int carried = (q.LA - q.D + 15) / 16;
-  hipLaunchKernelGGL(chol::k_chol_fused, dim3(1 + (carried + chol::CH_FC - 1) / chol::CH_FC), dim3(64 * (chol::CH_FW + 1)), chol::chol_lds_bytes(), s, q);
+  hipLaunchKernelGGL(with_max_lds<chol::k_chol_fused>(c), dim3(1 + (carried + chol::CH_FC - 1) / chol::CH_FC), dim3(64 * (chol::CH_FW + 1)), chol::chol_lds_bytes(), s, q);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
@@ -755,7 +717,7 @@ static EventPair *next_events(ovgpu_ctx *c, std::vector<EventPair> &v, size_t id
   }
   EventPair &e = v[idx];
   if (!e.a) {
-    if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return nullptr;
+    if (e.a.create() != hipSuccess || e.b.create() != hipSuccess) return nullptr;
   }
   return &e;
 }

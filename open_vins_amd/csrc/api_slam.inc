@@ -9,12 +9,12 @@ static LandmarkStore landmark_store(ovgpu_ctx *c) { return LandmarkStore{c->lm_v
 
 static int reserve_landmarks(ovgpu_ctx *c, int cap, int keep) {
   const size_t n = (size_t)std::max(cap, 1);
-  HIPCHK(c->lm_val.grow(3 * n, 3 * (size_t)keep));
-  HIPCHK(c->lm_fej.grow(3 * n, 3 * (size_t)keep));
-  HIPCHK(c->lm_cov.grow(n, keep));
-  HIPCHK(c->lm_col.grow(n, keep));
-  HIPCHK(c->lm_anchor.grow(n, keep));
-  HIPCHK(c->lm_repd.grow(n, keep));
+  HIPCHK(c->lm_val.reserve(3 * n, 3 * (size_t)keep));
+  HIPCHK(c->lm_fej.reserve(3 * n, 3 * (size_t)keep));
+  HIPCHK(c->lm_cov.reserve(n, keep));
+  HIPCHK(c->lm_col.reserve(n, keep));
+  HIPCHK(c->lm_anchor.reserve(n, keep));
+  HIPCHK(c->lm_repd.reserve(n, keep));
   return OVGPU_OK;
 }
 

@@ -46,7 +46,6 @@ int ovgpu_ekf_update(ovgpu_ctx *c, int rows, int cols, const int32_t *col_cov_id
     ej.col_cov = cols_dev.p, ej.sigma2 = sigma2;
     rc = enqueue_ekf(c, ej);
     if (rc == OVGPU_OK) rc = finish_update(c, dx, P_out, nullptr);
-    cols_dev.release();
   }
   // the context's own workspaces are sized by its column map again
   HIPCHK(c->Mt.reserve((size_t)c->D * c->N));
@@ -222,7 +221,6 @@ int ovgpu_cam_distort(ovgpu_ctx *c, int is_fisheye, const double *cam8, int n, c
   if (dz_dzn) HIPCHK(hipMemcpyAsync(dz_dzn, d_a.p, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, s));
   if (dz_dzeta) HIPCHK(hipMemcpyAsync(dz_dzeta, d_b.p, sizeof(double) * 16 * n, hipMemcpyDeviceToHost, s));
   HIPCHK(upload_sync(c, s));
-  d_cam.release(), d_in.release(), d_uv.release(), d_a.release(), d_b.release();
   return OVGPU_OK;
 }
 

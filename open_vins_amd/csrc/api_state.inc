@@ -16,25 +16,15 @@ void ovgpu_default_options(ovgpu_options *o) {
 double ovgpu_chi2_quantile_95(int dof) { return chi2_quantile_95(dof); }
 int ovgpu_abi_version(void) { return OVGPU_ABI_VERSION; }
 
-int ovgpu_create(const ovgpu_options *opts, int device, ovgpu_ctx **out) {
-  if (!opts || !out) return set_err(OVGPU_ERR_INVALID, "null argument");
-  *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return set_err(OVGPU_ERR_NO_DEVICE, std::string("no HIP device (") + hipGetErrorString(e) + "): this library has no CPU fallback");
-  if (device < 0 || device >= ndev) return set_err(OVGPU_ERR_INVALID, "device index out of range");
-  if (opts->feat_rep_msckf < 0 || opts->feat_rep_msckf > OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE)
-    return set_err(OVGPU_ERR_INVALID, "unknown feature representation");
-  HIPCHK(hipSetDevice(device));
-  ovgpu_ctx *c = new ovgpu_ctx();
+// what ovgpu_create does to a fresh context (the device is current); on an error the caller deletes it
+static int init_context(ovgpu_ctx *c, const ovgpu_options *opts, int device) {
   c->device = device;
   c->opts = *opts;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
   c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->lds_limit = (int)std::min<size_t>(prop.sharedMemPerBlock, 160 * 1024);
-  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking));
   HIPCHK(c->ctrl.reserve(CTRL_INTS));
   HIPCHK(hipMemset(c->ctrl.p, 0, CTRL_INTS * sizeof(int32_t)));
   // the views into it, set here and nowhere else (DevView: nothing to reserve or release; they go with ctrl)
@@ -57,10 +47,8 @@ int ovgpu_create(const ovgpu_options *opts, int device, ovgpu_ctx **out) {
   d.gate_always_factor = opts->gate_always_factor != 0;
   if (d.feat_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) d.feat_rep = OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH; // UpdaterMSCKF.cpp:180-183
   c->row_stride = (d.feat_rep >= OVGPU_REP_ANCHORED_3D) ? 72 : 48;
-  // allow the large dynamic LDS carve of the per-feature kernel
   // library switches are options of the context, not of the environment (include/ovgpu.h)
   if (opts->compress_route < 0 || opts->compress_route > OVGPU_COMPRESS_PCHOLQR || opts->compress_route == 2 /* the retired unpivoted factor */ || opts->tsqr_overlap < 0 || opts->tsqr_overlap > 2 || opts->tsqr_workers < 0) {
-    ovgpu_destroy(c); // (the stream and the control block exist already: a bare delete would leak them)
     return set_err(OVGPU_ERR_INVALID, "bad library switch in ovgpu_options");
   }
   c->tree_pipelined = opts->tsqr_no_pipeline == 0;
@@ -75,20 +63,37 @@ int ovgpu_create(const ovgpu_options *opts, int device, ovgpu_ctx **out) {
   c->no_chol_pipe = opts->no_single_launch_cholesky != 0;
   c->feat_shape = opts->feature_kernel_shape;
   c->gram_fp32 = opts->gram_fp32 != 0;
-  if (hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming) != hipSuccess) c->no_feat_kernel = true;
+  if (c->ev_rows.create(hipEventDisableTiming) != hipSuccess) c->no_feat_kernel = true;
   // The side stream (the prior block's factorisation next to the triangulation) gets a PRIORITY of its own: the runtime deals its hardware queues
   // per priority level, so this stream never lands on the queue of the context's main stream.  Without it the SECOND context of a process
   // (bench.py's extras; the drop-in's UpdaterSLAM context beside UpdaterMSCKF's) had both streams on one hardware queue and ran its two
   // head chains one after the other: 0.827 instead of 0.762 ms per update (tools/dev_two_contexts.py, round 5).
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  if (hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
+  if (hipStreamCreateWithPriority(&c->stream2.h, hipStreamNonBlocking, prio_hi) != hipSuccess || c->ev_fork.create(hipEventDisableTiming) != hipSuccess ||
+      c->ev_join.create(hipEventDisableTiming) != hipSuccess)
     c->tree_overlap = 0;
-  (void)hipFuncSetAttribute((const void *)k_system_t<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-  (void)hipFuncSetAttribute((const void *)k_system_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
-  (void)hipFuncSetAttribute((const void *)k_triangulate, hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_limit);
   c->timing = opts->no_timing == 0;
+  return OVGPU_OK;
+}
+
+int ovgpu_create(const ovgpu_options *opts, int device, ovgpu_ctx **out) {
+  if (!opts || !out) return set_err(OVGPU_ERR_INVALID, "null argument");
+  *out = nullptr;
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0)
+    return set_err(OVGPU_ERR_NO_DEVICE, std::string("no HIP device (") + hipGetErrorString(e) + "): this library has no CPU fallback");
+  if (device < 0 || device >= ndev) return set_err(OVGPU_ERR_INVALID, "device index out of range");
+  if (opts->feat_rep_msckf < 0 || opts->feat_rep_msckf > OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE)
+    return set_err(OVGPU_ERR_INVALID, "unknown feature representation");
+  HIPCHK(hipSetDevice(device));
+  ovgpu_ctx *c = new ovgpu_ctx();
+  const int rc = init_context(c, opts, device);
+  if (rc != OVGPU_OK) {
+    delete c; // (nothing has been enqueued yet: what exists by now goes with the struct)
+    return rc;
+  }
   *out = c;
   return OVGPU_OK;
 }
@@ -98,51 +103,9 @@ void ovgpu_destroy(ovgpu_ctx *c) {
   (void)hipSetDevice(c->device);
   (void)upload_sync(c, c->stream);
   if (c->stream2) (void)hipStreamSynchronize(c->stream2); // a prior-block factorisation nobody joined
-  for (auto &e : c->ev_compress) {
-    if (e.a) (void)hipEventDestroy(e.a);
-    if (e.b) (void)hipEventDestroy(e.b);
-  }
-  for (auto &e : c->ev_update) {
-    if (e.a) (void)hipEventDestroy(e.a);
-    if (e.b) (void)hipEventDestroy(e.b);
-  }
-  for (auto &e : c->ev_system) {
-    if (e.a) (void)hipEventDestroy(e.a);
-    if (e.b) (void)hipEventDestroy(e.b);
-  }
-  c->P.release(), c->P0.release(), c->clone_qp.release(), c->clone_qp0.release(), c->clone_fej.release();
-  c->calib_qp.release(), c->calib_qp0.release(), c->intr.release(), c->intr0.release(), c->fisheye.release();
-  c->clone_cov.release(), c->calib_cov.release(), c->intr_cov.release(), c->clone_col.release(), c->calib_col.release();
-  c->intr_col.release(), c->var_tab.release(), c->active_idx.release(), c->col_cov.release(), c->col_kind.release(), c->col_sub.release(), c->col_var.release();
-  c->tab_clone.release(), c->tab_cam.release(), c->tab_cc.release();
-  c->retri_sys[0].release(), c->retri_sys[1].release(), c->retri_pos.release(), c->retri_uvd.release(), c->retri_int.release(), c->retri_f.release(), c->marg_idx.release(), c->marg_out.release(), c->seed_anchor.release(), c->seed_pA.release();
-  c->meas_offsets.release(), c->meas_cc.release(), c->uv.release(), c->uvn.release(), c->row_off.release();
-  c->pA.release(), c->pG.release(), c->chi2.release(), c->chi2_thr.release(), c->anchor.release(), c->anchor_pre.release(), c->status.release(), c->sys_order.release(), c->feat_sigma.release(), c->feat_mult.release();
-  c->Hbig32.release(), c->gram32_part.release(), c->gram32_tiles.release();
-  c->up_arena.release(), c->down_arena.release();
-  c->chi2_table.release(), c->Hbig.release(), c->gate_ws.release(), c->Rws.release(), c->tree_nodes.release(), c->tree_nodes2.release(), c->tree_flags.release(), c->tree_err.release(), c->Mt.release(), c->Aaug.release(), c->Yaug.release();
-  c->pFej.release(), c->lm_val.release(), c->lm_fej.release(), c->feat_lm.release(), c->feat_lmcol.release(), c->feat_lmcov.release(), c->lm_cov.release();
-  c->feat_anchor.release(), c->lm_col.release(), c->lm_anchor.release(), c->lm_index.release(), c->Ppad.release(), c->init_ws.release(), c->dx_seq.release();
-  c->init_ctr.release(), c->feat_slot.release(), c->prop_w.release(), c->prop_in.release(), c->prop_ids.release();
-  c->anc_tab.release(), c->anc_ids.release(), c->anc_phi.release(), c->anc_w.release();
-  c->chk_tab.release(), c->chk_offs.release(), c->chk_flags.release(), c->chk_rowoff.release(), c->chk_dx.release(), c->chk_save.release();
-  c->marg_tab.release(), c->lm_anchor_b.release(), c->lm_repd_b.release(), c->clone_qp_b.release(), c->clone_fej_b.release(), c->lm_val_b.release(), c->lm_fej_b.release();
-  c->trk_count.release(), c->trk_cam.release(), c->trk_slot_in.release(), c->trk_cam_in.release(), c->trk_sel.release(), c->trk_nvalid.release(), c->trk_flag.release();
-  c->trk_time.release(), c->trk_clone_times.release(), c->trk_aux.release(), c->trk_uv.release(), c->trk_uvn.release(), c->trk_uv_in.release(), c->trk_uvn_in.release();
-  c->dx.release(), c->given_status.release();
-  c->ctrl.release();
-  c->gram_part.release(), c->gram_G.release(), c->gram_rho.release(), c->Yaug2.release(), c->gram_dropped.release(), c->Lw.release(), c->dbg_cycles.release();
-  c->chol_uinv.release();
-  c->chol_wide_A.release(), c->chol_wide_Y.release();
-  c->h_tri.release();
-  c->fs_slots.release(), c->fs_minfo.release(), c->fs_meas_feat.release(), c->fs_pos.release(), c->fs_rows.release(), c->fs_V.release(), c->fs_z.release(), c->fs_w.release(), c->fs_tq.release(), c->fs_inst.release(), c->featyb_ws.release();
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  c->comm_buf.release();
-  if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
-  c->leaf_flags.release();
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  // Every launch and asynchronous copy that touches a buffer of this context was enqueued on one of these two streams (the loop-back collective's
+  // reads from other ranks' streams are ordered before this stream's tail by its `ready` events), and both are idle now: nothing is in flight, so
+  // the members may go in any order — the buffers (OwnedBuf), the events and the two streams (Event, Stream) each free what they own.
   delete c;
 }
 

@@ -95,8 +95,7 @@ int ovgpu_state_marginalize(ovgpu_ctx *c, int32_t cov_id, int32_t size) {
     if (c->active_given && drop_lm < (int)c->h_lm_active.size()) c->h_lm_active.erase(c->h_lm_active.begin() + drop_lm); // the set follows the landmarks' indices
     c->L -= 1;
   }
-  HIPCHK(upload_sync(c, s)); // the scratch copies go out of scope
-  tmpd.release(), tmpi.release();
+  HIPCHK(upload_sync(c, s)); // (the scratch copies are done with; tmpd and tmpi go with the scope)
   auto shift = [&](int32_t &id) { if (id > cov_id) id -= size; };
   for (auto &id : c->h_clone_cov) shift(id);
   for (auto &id : c->h_calib_cov) shift(id);
@@ -257,8 +256,8 @@ int ovgpu_state_augment_clone(ovgpu_ctx *c, int32_t src_cov_id, const double *q_
     HIPCHK(hipGetLastError());
   }
   // ---- the clone joins the resident ones (State::_clones_IMU[timestamp] = pose, :597)
-  HIPCHK(c->clone_qp.grow(7 * (size_t)(C + 1), 7 * (size_t)C));
-  HIPCHK(c->clone_fej.grow(7 * (size_t)(C + 1), 7 * (size_t)C));
+  HIPCHK(c->clone_qp.reserve(7 * (size_t)(C + 1), 7 * (size_t)C));
+  HIPCHK(c->clone_fej.reserve(7 * (size_t)(C + 1), 7 * (size_t)C));
   HIPCHK(upload(c->clone_qp.p + 7 * C, q_p, sizeof(double) * 7, s));
   HIPCHK(upload(c->clone_fej.p + 7 * C, q_p_fej, sizeof(double) * 7, s));
   HIPCHK(upload_sync(c, s));

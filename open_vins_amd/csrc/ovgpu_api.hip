@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +44,7 @@
 #include "k_retri.h"
 #include "k_init_fused.h"
 #include "ovgpu_types.h"
+#include "dev_buf.h"
 
 // The fused per-feature kernels live in the second translation unit (ovgpu_featy_tu.hip: its own scheduler strategy); here they are
 // only declared, so that their launches below bind to those definitions.
