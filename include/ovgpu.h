@@ -1245,6 +1245,12 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             memory together, and their bytes as requested (a buffer of n elements counts max(n, 1) elements).  The same values
  *                             from any context: a context that was destroyed has given back everything it held, so both return to what they
  *                             were before it was created (tests/test_gpu_context_frees.py)
+ *   "upload_arena_bytes"      reads the capacity of the page-locked upload arena of ovgpu_set_state / ovgpu_set_features (8 MB once the first
+ *                             of them has run).  A value >= 64 is the size asked for the next time one of them starts; the arena only ever
+ *                             grows, so a small arena is had by setting this before the context's first upload.  An array that does not fit
+ *                             what is left of the arena bypasses it: it is copied from the caller's memory and the stream is synchronised
+ *                             before the call goes on, and the arena is twice what would have fitted (1 GiB at most) from the next call on
+ *   "upload_bypasses"         counter: the arrays that bypassed the arena; a value >= 0 sets it
  *   "raw_gram_tile_rows"      (read only) rows x tiles summed over the regions of the resident batch: the 16 x 16 products per row k_gram_regions executes
  *   "speculative_prior"       (round 6, default 1) ovgpu_set_features starts the prior block's factorisation on the second stream, next to its own
  *                             uploads; the update joins it.  0: the factorisation starts with the update (round 5)

@@ -147,20 +147,7 @@ struct FeatPlan {
 };
 
 struct LoopComm;
-// ---- one launch instead of one copy per array (round 6) ---------------------------------------------------------------------------
-// ovgpu_set_state + ovgpu_set_features hand over ~20 arrays per frame, most of them a few hundred bytes.  As one hipMemcpyAsync each they
-// cost the caller's thread ~5 us apiece and the stream a DMA packet with its own completion signal apiece.  The arrays are packed into the
-// page-locked arena anyway: ONE kernel reads the arena over PCIe (page-locked host memory is mapped into the device's address space) and
-// scatters every array to its own device buffer — the same bytes cross the bus once, the caller pays one launch.
-struct UpSeg {
-  void *dst;
-  uint32_t off, bytes; // offset in the arena (64-byte aligned), length
-};
-constexpr int UP_MAX_SEG = 28, UP_BLOCKS = 48; // workgroups per array: 48 x 256 lanes x 16 B = 196 KB in flight per pass and array
-struct UpBatch {
-  UpSeg seg[UP_MAX_SEG];
-  int n = 0;
-};
+// ---- the page-locked arena and landing zone (host_link.h): their two kernels and the HIP port -----------------------------------------
 __global__ void __launch_bounds__(256) k_upload_scatter(const unsigned char *__restrict__ arena, UpBatch b) {
   const UpSeg sg = b.seg[blockIdx.y];
   const unsigned char *src = arena + sg.off;
@@ -172,6 +159,26 @@ __global__ void __launch_bounds__(256) k_upload_scatter(const unsigned char *__r
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) d4[i] = __builtin_nontemporal_load(s4 + i);
   for (uint32_t i = (nvec << 4) + blockIdx.x * 256 + threadIdx.x; i < sg.bytes; i += gridDim.x * 256) dst[i] = src[i];
 }
+
+// the HIP port of Uplink / Landing (host_link.h): everything on the stream the context hands them
+struct HipLink {
+  using Err = hipError_t;
+  static constexpr Err ok = hipSuccess, refused = hipErrorInvalidValue;
+  using Stream = hipStream_t;
+  using Pinned = PinnedAlloc;
+  static unsigned char *device_alias(unsigned char *host) { // (page-locked host memory is mapped into the device's address space)
+    void *dev = nullptr;
+    return hipHostGetDevicePointer(&dev, host, 0) == hipSuccess ? static_cast<unsigned char *>(dev) : nullptr;
+  }
+  static Err h2d(Stream s, void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); }
+  static Err d2h(Stream s, void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); }
+  static Err scatter(Stream s, const unsigned char *arena, const UpBatch &b) {
+    hipLaunchKernelGGL(k_upload_scatter, dim3(UP_BLOCKS, b.n), dim3(256), 0, s, arena, b);
+    return hipGetLastError();
+  }
+  static Err gather(Stream s, unsigned char *zone, const UpBatch &b); // (behind k_download_gather, below)
+  static Err sync(Stream s) { return hipStreamSynchronize(s); }
+};
 
 struct ovgpu_ctx {
   int device = 0;
@@ -395,18 +402,10 @@ struct ovgpu_ctx {
   bool no_chol_pipe = false;   // options.no_single_launch_cholesky
   int tri_waves = 0;           // features per workgroup of k_triangulate; 0 = by the batch (enqueue_triangulate); ovgpu_debug_option "tri_waves" forces 1 .. 16
   int feat_shape = 0;          // options.feature_kernel_shape
-  PinBuf<unsigned char> up_arena; // page-locked upload arena of ovgpu_set_state / ovgpu_set_features (upload_staged)
-  PinBuf<unsigned char> down_arena; // page-locked landing zone of the results (status, chi2, p_FinG, dx, P'): asynchronous copies, one synchronisation, memcpy to the caller
-  size_t up_off = 0, up_want = 8u << 20;
-  UpBatch up_batch;                       // arrays packed into the arena since the last scatter launch (upload_deferred / upload_flush)
-  const unsigned char *up_arena_dev = nullptr; // the arena as the device sees it (page-locked host memory is mapped)
-  bool up_kernel = true;                  // ovgpu_debug_option "upload_kernel": 0 = one hipMemcpyAsync per array (rounds 4-5)
-  UpBatch down_batch;                     // result arrays on their way to the landing zone (download_deferred / download_flush)
-  unsigned char *down_arena_dev = nullptr;
+  Uplink<HipLink> up;    // page-locked upload arena of ovgpu_set_state / ovgpu_set_features; ovgpu_debug_option "upload_kernel" 0 = one hipMemcpyAsync per array (rounds 4-5)
+  Landing<HipLink> down; // page-locked landing zone of the results (status, chi2, p_FinG, dx, P'): one gather launch, one synchronisation, memcpy to the caller
   const double *chi2_table_dev = nullptr; // what the device's chi2 table holds: buffer and length at its last upload
   int chi2_table_dev_len = 0;
-  bool up_dirty = false;    // copies out of the arena may be in flight
-  bool up_fallback = false; // an upload since the last synchronisation bypassed the arena (its host source must outlive the copy)
   bool gram_fp32 = false;      // options.gram_fp32
   bool want_stack_f32 = false; // this pipeline: gram_fp32 on the prior-whitened Gram route -> the fused per-feature kernels may store floats
   bool stack_is_f32 = false;   // ... and did: the stack is c->Hbig32 [rows_total][stack_ldf] (k_gram32.h reads it)
@@ -500,30 +499,7 @@ static hipError_t upload(void *dst, const void *src, size_t bytes, hipStream_t s
   return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
 }
 
-// The uploads of a state / feature batch (25 arrays per update of the drop-in path): a copy from PAGEABLE memory is staged by the
-// runtime one call at a time (~20 us apiece, the caller blocked); here the CPU packs the bytes into one page-locked arena and the
-// copies leave asynchronously, so packing the next array overlaps the DMA of the previous one.  upload_begin() at the top of
-// ovgpu_set_state / ovgpu_set_features (both end with a stream synchronisation: the arena is free again when they return).
-static hipError_t upload_flush(ovgpu_ctx *c);
-static hipError_t upload_begin(ovgpu_ctx *c) {
-  // copies out of the arena may still be in flight (ovgpu_set_state returns without a synchronisation): keep appending behind them;
-  // the offset goes back to 0 once a synchronisation of the stream has been seen (upload_sync / upload_fence)
-  if (!c->up_dirty) c->up_off = 0;
-  if (c->up_want > c->up_arena.cap) {
-    if (c->up_dirty) {
-      if (hipError_t ef = upload_flush(c); ef != hipSuccess) return ef;
-      hipError_t e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) return e;
-      c->up_dirty = false, c->up_fallback = false, c->up_off = 0;
-    }
-    if (hipError_t e = c->up_arena.reserve(c->up_want); e != hipSuccess) return e;
-    void *dev = nullptr;
-    c->up_arena_dev = hipHostGetDevicePointer(&dev, c->up_arena.p, 0) == hipSuccess ? static_cast<const unsigned char *>(dev) : nullptr;
-  }
-  return hipSuccess;
-}
-// ... and the way back: the results of an update (status, chi2, p_FinG, flags, dx, P': eight device arrays) land in the page-locked zone
-// by ONE launch that writes them over PCIe (round 5: eight hipMemcpyAsync, ~60 us between the last kernel and the caller's memcpy)
+// the landing zone's gather launch (host_link.h: Landing)
 __global__ void __launch_bounds__(256) k_download_gather(unsigned char *__restrict__ arena, UpBatch b) {
   const UpSeg sg = b.seg[blockIdx.y];
   unsigned char *dst = arena + sg.off;
@@ -535,104 +511,20 @@ __global__ void __launch_bounds__(256) k_download_gather(unsigned char *__restri
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) __builtin_nontemporal_store(s4[i], d4 + i);
   for (uint32_t i = (nvec << 4) + blockIdx.x * 256 + threadIdx.x; i < sg.bytes; i += gridDim.x * 256) dst[i] = src[i];
 }
-static hipError_t down_reserve(ovgpu_ctx *c, size_t bytes) {
-  unsigned char *before = c->down_arena.p;
-  if (hipError_t e = c->down_arena.reserve(bytes); e != hipSuccess) return e;
-  if (c->down_arena.p != before || !c->down_arena_dev) {
-    void *dev = nullptr;
-    c->down_arena_dev = hipHostGetDevicePointer(&dev, c->down_arena.p, 0) == hipSuccess ? static_cast<unsigned char *>(dev) : nullptr;
-  }
-  return hipSuccess;
-}
-static hipError_t download_flush(ovgpu_ctx *c) {
-  if (c->down_batch.n == 0) return hipSuccess;
-  const int n = c->down_batch.n;
-  c->down_batch.n = 0;
-  hipLaunchKernelGGL(k_download_gather, dim3(UP_BLOCKS, n), dim3(256), 0, c->stream, c->down_arena_dev, c->down_batch);
+inline hipError_t HipLink::gather(hipStream_t s, unsigned char *zone, const UpBatch &b) {
+  hipLaunchKernelGGL(k_download_gather, dim3(UP_BLOCKS, b.n), dim3(256), 0, s, zone, b);
   return hipGetLastError();
-}
-// device array -> offset `off` (16-byte aligned) of the landing zone, with the next download_flush (the zone must have been reserved)
-static hipError_t download_deferred(ovgpu_ctx *c, size_t off, const void *src, size_t bytes) {
-  if (bytes == 0) return hipSuccess;
-  if (!c->up_kernel || !c->down_arena_dev || (off & 15) || off + bytes > 0xffffffffull)
-    return hipMemcpyAsync(c->down_arena.p + off, src, bytes, hipMemcpyDeviceToHost, c->stream);
-  if (c->down_batch.n >= UP_MAX_SEG) {
-    if (hipError_t e = download_flush(c); e != hipSuccess) return e;
-  }
-  UpSeg &sg = c->down_batch.seg[c->down_batch.n++];
-  sg.dst = const_cast<void *>(src), sg.off = (uint32_t)off, sg.bytes = (uint32_t)bytes;
-  return hipSuccess;
 }
 
-// the arrays packed since the last flush leave by ONE launch on the context's stream
-static hipError_t upload_flush(ovgpu_ctx *c) {
-  if (c->up_batch.n == 0) return hipSuccess;
-  const int n = c->up_batch.n;
-  c->up_batch.n = 0;
-  hipLaunchKernelGGL(k_upload_scatter, dim3(UP_BLOCKS, n), dim3(256), 0, c->stream, c->up_arena_dev, c->up_batch);
-  return hipGetLastError();
-}
-static hipError_t upload_staged(ovgpu_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t s);
-// upload_staged whose copy is DEFERRED to the next upload_flush (every upload_staged / upload_fence / upload_sync flushes first, so stream
-// order is what the call order says); the caller flushes before it launches anything that reads the array
-static hipError_t upload_deferred(ovgpu_ctx *c, void *dst, const void *src, size_t bytes) {
-  if (bytes == 0) return hipSuccess;
-  const size_t off = (c->up_off + 63) & ~(size_t)63;
-  if (!c->up_kernel || !c->up_arena_dev || off + bytes > c->up_arena.cap || off + bytes > 0xffffffffull) return upload_staged(c, dst, src, bytes, c->stream);
-  if (c->up_batch.n >= UP_MAX_SEG) {
-    if (hipError_t e = upload_flush(c); e != hipSuccess) return e;
-  }
-  std::memcpy(c->up_arena.p + off, src, bytes);
-  c->up_off = off + bytes, c->up_dirty = true;
-  UpSeg &sg = c->up_batch.seg[c->up_batch.n++];
-  sg.dst = dst, sg.off = (uint32_t)off, sg.bytes = (uint32_t)bytes;
-  return hipSuccess;
-}
-// ... for an array the caller builds in place: room in the arena (nullptr when the deferred path is off or full — the caller then builds it
-// elsewhere and uses upload_deferred), registered for the next scatter launch once its destination is known
-static void *upload_arena_take(ovgpu_ctx *c, size_t bytes, size_t *off_out) {
-  const size_t off = (c->up_off + 63) & ~(size_t)63;
-  if (bytes == 0 || !c->up_kernel || !c->up_arena_dev || off + bytes > c->up_arena.cap || off + bytes > 0xffffffffull) return nullptr;
-  c->up_off = off + bytes, c->up_dirty = true;
-  *off_out = off;
-  return c->up_arena.p + off;
-}
-static hipError_t upload_deferred_taken(ovgpu_ctx *c, void *dst, size_t off, size_t bytes) {
-  if (c->up_batch.n >= UP_MAX_SEG) {
-    if (hipError_t e = upload_flush(c); e != hipSuccess) return e;
-  }
-  UpSeg &sg = c->up_batch.seg[c->up_batch.n++];
-  sg.dst = dst, sg.off = (uint32_t)off, sg.bytes = (uint32_t)bytes;
-  return hipSuccess;
-}
-static hipError_t upload_staged(ovgpu_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (bytes == 0) return hipSuccess;
-  if (hipError_t e = upload_flush(c); e != hipSuccess) return e;
-  const size_t off = (c->up_off + 63) & ~(size_t)63;
-  if (s != c->stream || off + bytes > c->up_arena.cap) { // no room this time: the runtime's own staging; the arena grows at the next upload_begin
-    if (s == c->stream) c->up_want = std::min<size_t>(std::max(c->up_want, 2 * (off + bytes)), (size_t)1 << 30); // (bounded: beyond 1 GiB the runtime's own staging serves)
-    c->up_fallback = true;
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-  }
-  std::memcpy(c->up_arena.p + off, src, bytes);
-  c->up_off = off + bytes, c->up_dirty = true;
-  return hipMemcpyAsync(dst, c->up_arena.p + off, bytes, hipMemcpyHostToDevice, s);
-}
-// "the host staging vectors go out of scope": needed only for uploads that bypassed the arena
-static hipError_t upload_fence(ovgpu_ctx *c, hipStream_t s) {
-  if (hipError_t e = upload_flush(c); e != hipSuccess) return e;
-  if (!c->up_fallback) return hipSuccess;
-  c->up_fallback = false, c->up_dirty = false;
-  return hipStreamSynchronize(s);
-}
-// a synchronisation of the context's stream that the caller needs anyway
+// a synchronisation of stream s that the caller needs anyway, with everything registered for upload or read-back on its way first
 // (EVERY synchronisation of the context's stream goes through here — ovgpu_synchronize, the read-backs, the track store — so that the
 // arena's offset returns to 0 behind any of them: a caller that only ever uses the asynchronous update would otherwise grow it for ever)
 static hipError_t upload_sync(ovgpu_ctx *c, hipStream_t s) {
-  if (hipError_t e = upload_flush(c); e != hipSuccess) return e;
-  if (hipError_t e = download_flush(c); e != hipSuccess) return e;
-  if (s == c->stream) c->up_fallback = false, c->up_dirty = false;
-  return hipStreamSynchronize(s);
+  if (hipError_t e = c->up.flush(); e != hipSuccess) return e;
+  if (hipError_t e = c->down.flush(); e != hipSuccess) return e;
+  if (hipError_t e = hipStreamSynchronize(s); e != hipSuccess) return e;
+  if (s == c->stream) c->up.synced(), c->down.synced();
+  return hipSuccess;
 }
 
 // profiling builds (-DQR_PROFILE): 128 cycle counters written by node 0 of the last leaf / merge launch

@@ -60,8 +60,14 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->featy_big;
     if (value >= 0) c->featy_big = (int)value;
   } else if (n == "upload_kernel") { // ovgpu_set_state / ovgpu_set_features: one scatter launch out of the page-locked arena (1, default) or one copy per array (0)
-    if (old_value) *old_value = c->up_kernel;
-    if (value >= 0) c->up_kernel = value != 0;
+    if (old_value) *old_value = c->up.use_kernel;
+    if (value >= 0) c->up.use_kernel = c->down.use_kernel = value != 0;
+  } else if (n == "upload_arena_bytes") { // reads the arena's capacity; a value >= 64 is the size asked for at the next Uplink::begin (the arena only grows)
+    if (old_value) *old_value = (int64_t)c->up.capacity();
+    if (value >= 64) c->up.want = (size_t)std::min<int64_t>(value, (int64_t)1 << 30);
+  } else if (n == "upload_bypasses") { // reads the count of uploads that did not fit the arena (host_link.h); a value >= 0 sets it
+    if (old_value) *old_value = c->up.bypasses;
+    if (value >= 0) c->up.bypasses = value;
   } else if (n == "layout_every_update") { // the per-batch integer tables rebuilt at the head of every update (api_state.inc: enqueue_batch_tables)
     if (old_value) *old_value = c->layout_every_update;
     if (value >= 0) c->layout_every_update = value != 0;

@@ -862,12 +862,11 @@ static void unpack_feature_outputs(ovgpu_ctx *c, const PendingFeatOut &q) {
   ovgpu_update_stats *stats = q.stats;
   std::vector<int32_t> st(F);
   if (F > 0) {
-    const unsigned char *h = c->down_arena.p;
-    std::memcpy(st.data(), h + q.o_st, sizeof(int32_t) * F);
-    if (chi2) std::memcpy(chi2, h + q.o_c2, sizeof(double) * F);
-    if (chi2_thresh) std::memcpy(chi2_thresh, h + q.o_th, sizeof(double) * F);
-    if (p_FinG) std::memcpy(p_FinG, h + q.o_pg, sizeof(double) * 3 * F);
-    if (stats) std::memcpy(&stats->n_gate_bound, h + q.o_gb, sizeof(int32_t));
+    std::memcpy(st.data(), c->down.at(q.o_st), sizeof(int32_t) * F);
+    if (chi2) std::memcpy(chi2, c->down.at(q.o_c2), sizeof(double) * F);
+    if (chi2_thresh) std::memcpy(chi2_thresh, c->down.at(q.o_th), sizeof(double) * F);
+    if (p_FinG) std::memcpy(p_FinG, c->down.at(q.o_pg), sizeof(double) * 3 * F);
+    if (stats) std::memcpy(&stats->n_gate_bound, c->down.at(q.o_gb), sizeof(int32_t));
   }
   const double qnan = std::nan("");
   int n_used = 0;
@@ -898,30 +897,28 @@ static int read_feature_outputs(ovgpu_ctx *c, int32_t *feat_status, double *chi2
                                 PendingFeatOut *pend = nullptr, size_t tail_bytes = 0) {
   const Batch b = batch_of(c);
   const int F = b.F;
-  hipStream_t s = c->stream;
   PendingFeatOut q;
   q.feat_status = feat_status, q.chi2 = chi2, q.chi2_thresh = chi2_thresh, q.p_FinG = p_FinG, q.stats = stats;
   if (F > 0) { // through the page-locked landing zone: a device-to-PAGEABLE copy is staged by the runtime, one blocking call per array
-    q.o_st = 0, q.o_c2 = (sizeof(int32_t) * F + 63) & ~(size_t)63; // (every landing offset 64-byte aligned: the gather kernel stores 16-byte vectors)
-    q.o_th = (q.o_c2 + sizeof(double) * F + 63) & ~(size_t)63, q.o_pg = (q.o_th + sizeof(double) * F + 63) & ~(size_t)63;
-    q.o_gb = (q.o_pg + sizeof(double) * 3 * F + 63) & ~(size_t)63;
-    q.end = q.o_gb + 64;
-    HIPCHK(down_reserve(c, q.end + tail_bytes)); // (before the first copy: a later reserve that grew the zone would free it under the copies)
-    HIPCHK(download_deferred(c, q.o_st, b.status, sizeof(int32_t) * F));
-    if (stats) HIPCHK(download_deferred(c, q.o_gb, c->rows_used.p + 1, sizeof(int32_t)));
-    if (chi2) HIPCHK(download_deferred(c, q.o_c2, b.chi2, sizeof(double) * F));
-    if (chi2_thresh) HIPCHK(download_deferred(c, q.o_th, b.chi2_thr, sizeof(double) * F));
-    if (p_FinG) HIPCHK(download_deferred(c, q.o_pg, b.pG, sizeof(double) * 3 * F));
+    LandLayout l;
+    q.o_st = l.add(sizeof(int32_t) * F), q.o_c2 = l.add(sizeof(double) * F), q.o_th = l.add(sizeof(double) * F);
+    q.o_pg = l.add(sizeof(double) * 3 * F), q.o_gb = l.add(64);
+    q.end = l.end;
+    HIPCHK(c->down.reserve(q.end + tail_bytes)); // (for both: finish_update's part lands behind q.end)
+    HIPCHK(c->down.get(q.o_st, b.status, sizeof(int32_t) * F));
+    if (stats) HIPCHK(c->down.get(q.o_gb, c->rows_used.p + 1, sizeof(int32_t)));
+    if (chi2) HIPCHK(c->down.get(q.o_c2, b.chi2, sizeof(double) * F));
+    if (chi2_thresh) HIPCHK(c->down.get(q.o_th, b.chi2_thr, sizeof(double) * F));
+    if (p_FinG) HIPCHK(c->down.get(q.o_pg, b.pG, sizeof(double) * 3 * F));
   } else if (tail_bytes) {
-    HIPCHK(down_reserve(c, tail_bytes));
+    HIPCHK(c->down.reserve(tail_bytes));
   }
-  (void)s;
   if (pend) { // the caller's finish_update synchronises and completes
     q.active = true;
     *pend = q;
     return OVGPU_OK;
   }
-  HIPCHK(upload_sync(c, s));
+  HIPCHK(upload_sync(c, c->stream));
   unpack_feature_outputs(c, q);
   return OVGPU_OK;
 }
@@ -1055,29 +1052,33 @@ static int decode_update_flags(ovgpu_ctx *c, const int32_t fl[4], ovgpu_update_s
 }
 
 // with_lm: the resident landmark values land behind P' (ovgpu_msckf_update_lm)
-static size_t finish_update_bytes(const ovgpu_ctx *c, bool with_lm = false) {
-  const size_t N = (size_t)c->N;
-  return 64 + ((sizeof(double) * N + 63) & ~(size_t)63) + ((sizeof(double) * N * N + 63) & ~(size_t)63) + (with_lm ? sizeof(double) * 3 * (size_t)c->L : 0);
-}
+struct UpdateLanding { // where finish_update's arrays land, behind `base`
+  size_t o_fl, o_dx, o_P, o_lm, n_lm, end;
+  UpdateLanding(const ovgpu_ctx *c, size_t base, bool with_lm) {
+    const size_t N = (size_t)c->N;
+    LandLayout l(base);
+    o_fl = l.add(64), o_dx = l.add(sizeof(double) * N), o_P = l.add(sizeof(double) * N * N);
+    n_lm = with_lm ? sizeof(double) * 3 * (size_t)c->L : 0, o_lm = l.add(n_lm);
+    end = l.end;
+  }
+};
+static size_t finish_update_bytes(const ovgpu_ctx *c, bool with_lm = false) { return UpdateLanding(c, 0, with_lm).end; }
 static int finish_update(ovgpu_ctx *c, double *dx, double *P_out, ovgpu_update_stats *stats, const PendingFeatOut *pend = nullptr, double *lm_out = nullptr) {
-  hipStream_t s = c->stream;
   int32_t flags[4] = {0, 0, 0, 0};
   {
-    const size_t base = (pend && pend->active) ? pend->end : 0; // behind the per-feature outputs still in flight
-    const size_t N = (size_t)c->N, o_dx = base + 64, o_P = o_dx + ((sizeof(double) * N + 63) & ~(size_t)63);
-    const size_t o_lm = o_P + ((sizeof(double) * N * N + 63) & ~(size_t)63), n_lm = (lm_out && c->L > 0) ? sizeof(double) * 3 * (size_t)c->L : 0;
-    HIPCHK(down_reserve(c, o_lm + n_lm)); // (no-op with `pend`: read_feature_outputs reserved both zones)
-    HIPCHK(download_deferred(c, base, c->flags.p, sizeof(flags)));
-    if (dx) HIPCHK(download_deferred(c, o_dx, c->dx.p, sizeof(double) * N));
-    if (P_out) HIPCHK(download_deferred(c, o_P, c->P.p, sizeof(double) * N * N));
-    if (n_lm) HIPCHK(download_deferred(c, o_lm, c->lm_val.p, n_lm));
-    HIPCHK(upload_sync(c, s)); // (one gather launch for everything deferred, then the synchronisation)
-    unsigned char *h = c->down_arena.p;
+    const size_t N = (size_t)c->N;
+    const UpdateLanding u(c, (pend && pend->active) ? pend->end : 0, lm_out && c->L > 0); // behind the per-feature outputs still in flight
+    HIPCHK(c->down.reserve(u.end)); // (no-op with `pend`: read_feature_outputs reserved both zones)
+    HIPCHK(c->down.get(u.o_fl, c->flags.p, sizeof(flags)));
+    if (dx) HIPCHK(c->down.get(u.o_dx, c->dx.p, sizeof(double) * N));
+    if (P_out) HIPCHK(c->down.get(u.o_P, c->P.p, sizeof(double) * N * N));
+    if (u.n_lm) HIPCHK(c->down.get(u.o_lm, c->lm_val.p, u.n_lm));
+    HIPCHK(upload_sync(c, c->stream)); // (one gather launch for everything registered, then the synchronisation)
     if (pend && pend->active) unpack_feature_outputs(c, *pend);
-    std::memcpy(flags, h + base, sizeof(flags));
-    if (dx) std::memcpy(dx, h + o_dx, sizeof(double) * N);
-    if (P_out) std::memcpy(P_out, h + o_P, sizeof(double) * N * N);
-    if (n_lm) std::memcpy(lm_out, h + o_lm, n_lm);
+    std::memcpy(flags, c->down.at(u.o_fl), sizeof(flags));
+    if (dx) std::memcpy(dx, c->down.at(u.o_dx), sizeof(double) * N);
+    if (P_out) std::memcpy(P_out, c->down.at(u.o_P), sizeof(double) * N * N);
+    if (u.n_lm) std::memcpy(lm_out, c->down.at(u.o_lm), u.n_lm);
   }
   const int status = decode_update_flags(c, flags, stats, UPDATE_FLAG_TEXT);
   if (c->chol_timed_out) return status;

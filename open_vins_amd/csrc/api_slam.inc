@@ -70,7 +70,7 @@ int ovgpu_set_active_landmarks(ovgpu_ctx *c, int32_t n, const int32_t *lm_index)
   if (n < 0 && !c->active_given) return OVGPU_OK; // every landmark has its columns already: nothing changes, the resident batch stays
   { const int rdp = drop_pending_prior(c); if (rdp != OVGPU_OK) return rdp; } // the column map changes: a prior-block factorisation started for the old one is stale
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(upload_begin(c));
+  HIPCHK(c->up.begin());
   c->active_given = n >= 0;
   c->h_lm_active.assign(n >= 0 ? c->L : 0, 0);
   for (int i = 0; i < n; i++) c->h_lm_active[lm_index[i]] = 1; // (a landmark named twice is in the set once)
@@ -374,11 +374,11 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   pl.o_lm = pl.tab.size(), pl.tab.insert(pl.tab.end(), lm_index, lm_index + F);
   pl.o_order = pl.tab.size(), pl.tab.insert(pl.tab.end(), pl.order.begin(), pl.order.begin() + F);
   HIPCHK(c->chk_tab.reserve(pl.tab.size()));
-  HIPCHK(upload_begin(c));
+  HIPCHK(c->up.begin());
   { const int rcv = upload_var_tab(c); if (rcv != OVGPU_OK) return rcv; }
-  HIPCHK(upload_deferred(c, c->chk_tab.p, pl.tab.data(), sizeof(int32_t) * pl.tab.size()));
-  HIPCHK(upload_deferred(c, c->chk_rowoff.p, pl.row_off.data(), sizeof(int64_t) * pl.row_off.size()));
-  HIPCHK(upload_fence(c, s));
+  HIPCHK(c->up.put(c->chk_tab.p, pl.tab.data(), sizeof(int32_t) * pl.tab.size()));
+  HIPCHK(c->up.put(c->chk_rowoff.p, pl.row_off.data(), sizeof(int64_t) * pl.row_off.size()));
+  HIPCHK(c->up.flush());
   hipLaunchKernelGGL(k_chunk_offsets, dim3((F + n + 255) / 256), dim3(256), 0, s, n, F, (const int32_t *)c->chk_tab.p, (const int32_t *)batch_of(c).meas_offsets, c->chk_offs.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));
@@ -391,24 +391,23 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   for (int k = 0; k < n && rc == OVGPU_OK; k++) rc = enqueue_chunk(c, pl, k);
   // ---- one read-back
   std::vector<int32_t> flags((size_t)5 * n, 0);
-  const size_t al = 63;
-  const size_t o_fl = 0, o_st = (sizeof(int32_t) * 5 * n + al) & ~al, o_c2 = (o_st + sizeof(int32_t) * F + al) & ~al, o_th = (o_c2 + sizeof(double) * F + al) & ~al;
-  const size_t o_dx = (o_th + sizeof(double) * F + al) & ~al, o_lm = (o_dx + sizeof(double) * (size_t)n * N + al) & ~al, o_P = (o_lm + sizeof(double) * 3 * L + al) & ~al;
-  const size_t o_end = o_P + sizeof(double) * (size_t)N * N;
+  LandLayout land;
+  const size_t o_fl = land.add(sizeof(int32_t) * 5 * n), o_st = land.add(sizeof(int32_t) * F), o_c2 = land.add(sizeof(double) * F), o_th = land.add(sizeof(double) * F);
+  const size_t o_dx = land.add(sizeof(double) * (size_t)n * N), o_lm = land.add(sizeof(double) * 3 * L), o_P = land.add(sizeof(double) * (size_t)N * N);
   auto gather = [&]() -> int {
-    HIPCHK(down_reserve(c, o_end));
-    HIPCHK(download_deferred(c, o_fl, c->chk_flags.p, sizeof(int32_t) * 5 * n));
+    HIPCHK(c->down.reserve(land.end));
+    HIPCHK(c->down.get(o_fl, c->chk_flags.p, sizeof(int32_t) * 5 * n));
     if (F > 0) {
       const Batch w = batch_of(c);
-      HIPCHK(download_deferred(c, o_st, w.status, sizeof(int32_t) * F));
-      if (chi2) HIPCHK(download_deferred(c, o_c2, w.chi2, sizeof(double) * F));
-      if (chi2_thresh) HIPCHK(download_deferred(c, o_th, w.chi2_thr, sizeof(double) * F));
+      HIPCHK(c->down.get(o_st, w.status, sizeof(int32_t) * F));
+      if (chi2) HIPCHK(c->down.get(o_c2, w.chi2, sizeof(double) * F));
+      if (chi2_thresh) HIPCHK(c->down.get(o_th, w.chi2_thr, sizeof(double) * F));
     }
-    if (dx_seq) HIPCHK(download_deferred(c, o_dx, c->chk_dx.p, sizeof(double) * (size_t)n * N));
-    if (lm_out) HIPCHK(download_deferred(c, o_lm, c->lm_val.p, sizeof(double) * 3 * L));
-    if (P_out) HIPCHK(download_deferred(c, o_P, c->P.p, sizeof(double) * (size_t)N * N));
+    if (dx_seq) HIPCHK(c->down.get(o_dx, c->chk_dx.p, sizeof(double) * (size_t)n * N));
+    if (lm_out) HIPCHK(c->down.get(o_lm, c->lm_val.p, sizeof(double) * 3 * L));
+    if (P_out) HIPCHK(c->down.get(o_P, c->P.p, sizeof(double) * (size_t)N * N));
     HIPCHK(upload_sync(c, s)); // the ONE synchronisation of the call
-    std::memcpy(flags.data(), c->down_arena.p + o_fl, sizeof(int32_t) * 5 * n);
+    std::memcpy(flags.data(), c->down.at(o_fl), sizeof(int32_t) * 5 * n);
     return OVGPU_OK;
   };
   // on return the active set in force is "all" (the all-landmarks map leaves with the gather's launch); the batch was never anything but the
@@ -465,13 +464,12 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   }
   // ---- to the caller
   {
-    const unsigned char *h = c->down_arena.p;
     const double qnan = std::nan("");
-    const int32_t *st = reinterpret_cast<const int32_t *>(h + o_st);
+    const int32_t *st = reinterpret_cast<const int32_t *>(c->down.at(o_st));
     const int Fd = pl.first[k_done];
     if (feat_status && Fd > 0) std::memcpy(feat_status, st, sizeof(int32_t) * Fd);
-    if (chi2 && Fd > 0) std::memcpy(chi2, h + o_c2, sizeof(double) * Fd);
-    if (chi2_thresh && Fd > 0) std::memcpy(chi2_thresh, h + o_th, sizeof(double) * Fd);
+    if (chi2 && Fd > 0) std::memcpy(chi2, c->down.at(o_c2), sizeof(double) * Fd);
+    if (chi2_thresh && Fd > 0) std::memcpy(chi2_thresh, c->down.at(o_th), sizeof(double) * Fd);
     for (int k = 0; k < k_done; k++) {
       int n_used = 0;
       int64_t rows = 0;
@@ -485,9 +483,9 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
       if (stats && pl.first[k + 1] > pl.first[k])
         stats[k].n_used = n_used, stats[k].n_rows = (int32_t)rows, stats[k].D = pl.D[k], stats[k].n_rows_comp = rows > 0 ? pl.D[k] : 0, stats[k].n_gate_bound = flags[(size_t)4 * n + k];
     }
-    if (dx_seq) std::memcpy(dx_seq, h + o_dx, sizeof(double) * (size_t)n * N);
-    if (lm_out) std::memcpy(lm_out, h + o_lm, sizeof(double) * 3 * L);
-    if (P_out) std::memcpy(P_out, h + o_P, sizeof(double) * (size_t)N * N);
+    if (dx_seq) std::memcpy(dx_seq, c->down.at(o_dx), sizeof(double) * (size_t)n * N);
+    if (lm_out) std::memcpy(lm_out, c->down.at(o_lm), sizeof(double) * 3 * L);
+    if (P_out) std::memcpy(P_out, c->down.at(o_P), sizeof(double) * (size_t)N * N);
   }
   if (status != OVGPU_OK) return status;
   return check_tree_error(c);

@@ -25,6 +25,7 @@ static int init_context(ovgpu_ctx *c, const ovgpu_options *opts, int device) {
   c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->lds_limit = (int)std::min<size_t>(prop.sharedMemPerBlock, 160 * 1024);
   HIPCHK(hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking));
+  c->up.stream = c->down.stream = c->stream;
   HIPCHK(c->ctrl.reserve(CTRL_INTS));
   HIPCHK(hipMemset(c->ctrl.p, 0, CTRL_INTS * sizeof(int32_t)));
   // the views into it, set here and nowhere else (DevView: nothing to reserve or release; they go with ctrl)
@@ -195,7 +196,7 @@ static int upload_var_tab(ovgpu_ctx *c) {
     std::vector<int32_t> tab((size_t)4 * std::max(V, 1), 0);
     for (int v = 0; v < V; v++) tab[4 * v] = c->h_sorted[v].cov, tab[4 * v + 1] = c->h_sorted[v].size, tab[4 * v + 2] = c->h_sorted[v].kind, tab[4 * v + 3] = c->h_sorted[v].index;
     HIPCHK(c->var_tab.reserve(tab.size()));
-    HIPCHK(upload_deferred(c, c->var_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
+    HIPCHK(c->up.put(c->var_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
     c->var_tab_ok = true;
   }
   return OVGPU_OK;
@@ -208,9 +209,9 @@ static int enqueue_active_columns(ovgpu_ctx *c, const std::vector<int32_t> &acti
     const int rcv = upload_var_tab(c);
     if (rcv != OVGPU_OK) return rcv;
     HIPCHK(c->active_idx.reserve(std::max<size_t>(active_idx.size(), 1)));
-    HIPCHK(upload_deferred(c, c->active_idx.p, active_idx.data(), sizeof(int32_t) * active_idx.size()));
+    HIPCHK(c->up.put(c->active_idx.p, active_idx.data(), sizeof(int32_t) * active_idx.size()));
   }
-  HIPCHK(upload_fence(c, c->stream));
+  HIPCHK(c->up.flush());
   HIPCHK(c->lm_col.reserve(std::max(c->L, 1)));
   ActiveColsParams ap;
   ap.V = V, ap.L = c->L, ap.C = c->C, ap.K = c->K, ap.n_active = (int)active_idx.size(), ap.Dcap = D;
@@ -284,7 +285,7 @@ static int layout_columns(ovgpu_ctx *c, bool defer_flush, const int32_t *residen
         c->h_cls_of_clone[i] = (uint8_t)k;
       }
       HIPCHK(c->cls_of_clone.reserve(C));
-      HIPCHK(upload_deferred(c, c->cls_of_clone.p, c->h_cls_of_clone.data(), C));
+      HIPCHK(c->up.put(c->cls_of_clone.p, c->h_cls_of_clone.data(), C));
       c->raw_j0 = clone_min + 6; // the oldest clone's block and the calibration columns left of it: the prior's common mode (ovgpu_types.h)
       c->raw_cols_ok = true;
     }
@@ -297,24 +298,20 @@ static int layout_columns(ovgpu_ctx *c, bool defer_flush, const int32_t *residen
   HIPCHK(c->Mt.reserve((size_t)D * N));
   HIPCHK(c->Aaug.reserve((size_t)D * (D + N + 1)));
   HIPCHK(c->Yaug.reserve((size_t)D * (D + N + 1)));
-  hipStream_t s = c->stream;
-  (void)s;
-  if (act) { // tables of an active set: built on the device
+  if (act) { // tables of an active set: built on the device (the uploads leave there)
     const int rca = enqueue_active_columns(c, active_idx, D, resident_set); // (resident_set lists the set in this walk's order)
     if (rca != OVGPU_OK) return rca;
-    if (!defer_flush) HIPCHK(upload_fence(c, c->stream));
   } else {
-    HIPCHK(upload_deferred(c, c->clone_col.p, clone_col.data(), sizeof(int32_t) * C));
-    HIPCHK(upload_deferred(c, c->calib_col.p, calib_col.data(), sizeof(int32_t) * K));
-    HIPCHK(upload_deferred(c, c->intr_col.p, intr_col.data(), sizeof(int32_t) * K));
-    HIPCHK(upload_deferred(c, c->col_cov.p, col_cov.data(), sizeof(int32_t) * D));
-    HIPCHK(upload_deferred(c, c->col_kind.p, col_kind.data(), D));
-    HIPCHK(upload_deferred(c, c->col_sub.p, col_sub.data(), D));
-    HIPCHK(upload_deferred(c, c->col_var.p, col_var.data(), sizeof(uint16_t) * D));
-    if (c->L > 0) HIPCHK(upload_deferred(c, c->lm_col.p, c->h_lm_col.data(), sizeof(int32_t) * c->L));
-    // host staging vectors go out of scope: their bytes sit in the page-locked arena (round 6: no synchronisation; the scatter launch that
-    // carries them may be the caller's — ovgpu_set_state adds its own arrays to it — and is flushed here otherwise)
-    if (!defer_flush) HIPCHK(upload_fence(c, c->stream));
+    HIPCHK(c->up.put(c->clone_col.p, clone_col.data(), sizeof(int32_t) * C));
+    HIPCHK(c->up.put(c->calib_col.p, calib_col.data(), sizeof(int32_t) * K));
+    HIPCHK(c->up.put(c->intr_col.p, intr_col.data(), sizeof(int32_t) * K));
+    HIPCHK(c->up.put(c->col_cov.p, col_cov.data(), sizeof(int32_t) * D));
+    HIPCHK(c->up.put(c->col_kind.p, col_kind.data(), D));
+    HIPCHK(c->up.put(c->col_sub.p, col_sub.data(), D));
+    HIPCHK(c->up.put(c->col_var.p, col_var.data(), sizeof(uint16_t) * D));
+    if (c->L > 0) HIPCHK(c->up.put(c->lm_col.p, c->h_lm_col.data(), sizeof(int32_t) * c->L));
+    // (the scatter launch that carries them may be the caller's — ovgpu_set_state adds its own arrays to it — and leaves here otherwise)
+    if (!defer_flush) HIPCHK(c->up.flush());
   }
   c->have_feats = false;           // workspaces depend on D
   c->tri_readable = false;
@@ -330,7 +327,7 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
       !st->calib_cov_id || !st->intr_cov_id)
     return set_err(OVGPU_ERR_INVALID, "null state array");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(upload_begin(c));
+  HIPCHK(c->up.begin());
   const int N = st->N, C = st->C, K = st->K;
 
   // ---- canonical column order: calibrated camera variables and clones sorted by covariance id
@@ -374,7 +371,6 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
   HIPCHK(c->Yaug.reserve((size_t)D * (D + N + 1)));
   HIPCHK(c->dx.reserve(N));
 
-  hipStream_t s = c->stream;
   // calibration ids the kernels see: -1 when that calibration is not being estimated
   std::vector<int32_t> calib_cov(K), intr_cov(K);
   for (int k = 0; k < K; k++) {
@@ -385,31 +381,18 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
   c->h_calib_cov = calib_cov, c->h_intr_cov = intr_cov;
   // one scatter launch for the column map (build_columns above) and the state: the device-side copy of the prior that ovgpu_reset_state
   // restores is a second destination of the same arena bytes (round 5: four device-to-device copies behind nine uploads)
-  (void)s;
   bool twins = true;
-  auto put2 = [&](void *dst, void *dst0, const void *src, size_t bytes) -> hipError_t {
-    const int n0 = c->up_batch.n;
-    if (hipError_t e = upload_deferred(c, dst, src, bytes); e != hipSuccess) return e;
-    if (n0 < UP_MAX_SEG && c->up_batch.n == n0 + 1 && c->up_batch.n < UP_MAX_SEG) { // deferred: the same arena bytes once more, to the twin
-      UpSeg sg = c->up_batch.seg[n0];
-      sg.dst = dst0;
-      c->up_batch.seg[c->up_batch.n++] = sg;
-    } else {
-      twins = false;
-    }
-    return hipSuccess;
-  };
-  HIPCHK(put2(c->P.p, c->P0.p, st->P, sizeof(double) * N * N));
-  HIPCHK(put2(c->clone_qp.p, c->clone_qp0.p, st->clone_q_p, sizeof(double) * 7 * C));
-  HIPCHK(put2(c->calib_qp.p, c->calib_qp0.p, st->calib_q_p, sizeof(double) * 7 * K));
-  HIPCHK(put2(c->intr.p, c->intr0.p, st->intrinsics, sizeof(double) * 8 * K));
-  HIPCHK(upload_deferred(c, c->clone_fej.p, st->clone_q_p_fej, sizeof(double) * 7 * C));
-  HIPCHK(upload_deferred(c, c->fisheye.p, st->cam_is_fisheye, K));
-  HIPCHK(upload_deferred(c, c->clone_cov.p, st->clone_cov_id, sizeof(int32_t) * C));
-  HIPCHK(upload_deferred(c, c->calib_cov.p, calib_cov.data(), sizeof(int32_t) * K));
-  HIPCHK(upload_deferred(c, c->intr_cov.p, intr_cov.data(), sizeof(int32_t) * K));
-  // the caller's buffers may change when this returns: the bytes sit in the page-locked arena (a synchronisation only for what bypassed it)
-  HIPCHK(upload_fence(c, s));
+  HIPCHK(c->up.put2(c->P.p, c->P0.p, st->P, sizeof(double) * N * N, twins));
+  HIPCHK(c->up.put2(c->clone_qp.p, c->clone_qp0.p, st->clone_q_p, sizeof(double) * 7 * C, twins));
+  HIPCHK(c->up.put2(c->calib_qp.p, c->calib_qp0.p, st->calib_q_p, sizeof(double) * 7 * K, twins));
+  HIPCHK(c->up.put2(c->intr.p, c->intr0.p, st->intrinsics, sizeof(double) * 8 * K, twins));
+  HIPCHK(c->up.put(c->clone_fej.p, st->clone_q_p_fej, sizeof(double) * 7 * C));
+  HIPCHK(c->up.put(c->fisheye.p, st->cam_is_fisheye, K));
+  HIPCHK(c->up.put(c->clone_cov.p, st->clone_cov_id, sizeof(int32_t) * C));
+  HIPCHK(c->up.put(c->calib_cov.p, calib_cov.data(), sizeof(int32_t) * K));
+  HIPCHK(c->up.put(c->intr_cov.p, intr_cov.data(), sizeof(int32_t) * K));
+  // the caller's buffers may change when this returns: the bytes sit in the page-locked arena or on the device (Uplink::put)
+  HIPCHK(c->up.flush());
   int rc = OVGPU_OK;
   if (!twins && (rc = copy_reset_baseline(c)) != OVGPU_OK) return rc; // (an array bypassed the arena, or the launch was split: the copies of rounds 4-5)
   rc = launch_build_tables(c);
@@ -628,7 +611,7 @@ static int size_feature_stage(ovgpu_ctx *c) {
       r[4] = (int32_t)(uint32_t)((uint64_t)row_off[f] & 0xffffffffu), r[5] = (int32_t)(uint32_t)((uint64_t)row_off[f] >> 32);
     }
     HIPCHK(c->fs_slots.reserve(slots.size()));
-    HIPCHK(upload_deferred(c, c->fs_slots.p, slots.data(), sizeof(int32_t) * slots.size()));
+    HIPCHK(c->up.put(c->fs_slots.p, slots.data(), sizeof(int32_t) * slots.size()));
   }
   // ---- stacked system and TSQR accumulators
   return configure_tsqr(c);
@@ -646,10 +629,10 @@ static int set_row_layout(ovgpu_ctx *c, bool slam_rows, bool anchors = false) {
   const int rcs = size_feature_stage(c);
   if (rcs != OVGPU_OK) return rcs;
   HIPCHK(c->row_off.reserve(F + 1));
-  HIPCHK(upload_deferred(c, c->row_off.p, c->h_row_off.data(), sizeof(int64_t) * (F + 1)));
+  HIPCHK(c->up.put(c->row_off.p, c->h_row_off.data(), sizeof(int64_t) * (F + 1)));
   // everything ovgpu_set_features packed into the arena (offsets, packed codes, pixel coordinates, the slot records and row offsets above)
   // leaves by ONE scatter launch; behind it the batch's integer tables (one launch; `anchors`: a new batch, end_feature_batch)
-  HIPCHK(upload_fence(c, c->stream));
+  HIPCHK(c->up.flush());
   return enqueue_batch_tables(c, anchors);
 }
 
@@ -692,7 +675,7 @@ static int raw_stack_layout(ovgpu_ctx *c, const uint16_t *cc) {
   HIPCHK(c->raw_featbase.reserve(fb.size()));
   HIPCHK(c->raw_dst.reserve((size_t)M));
   HIPCHK(c->raw_runs.reserve((size_t)F * feat::FY_RUNREC * 4));
-  HIPCHK(upload_deferred(c, c->raw_featbase.p, fb.data(), sizeof(int32_t) * fb.size()));
+  HIPCHK(c->up.put(c->raw_featbase.p, fb.data(), sizeof(int32_t) * fb.size()));
   // workgroups: one per compute unit, every live region at least one, the rest by work
   const int G = std::max(c->num_cu, live);
   int wgs[RAW_MAXCLS + 1] = {0}, given = 0;
@@ -725,7 +708,7 @@ static int raw_stack_layout(ovgpu_ctx *c, const uint16_t *cc) {
   }
   c->gram_wg_n = (int)tab.size(), c->gram_wg_tiles = tiles;
   HIPCHK(c->gram_wg.reserve(tab.size()));
-  HIPCHK(upload_deferred(c, c->gram_wg.p, tab.data(), sizeof(gram::GramRegionWG) * tab.size()));
+  HIPCHK(c->up.put(c->gram_wg.p, tab.data(), sizeof(gram::GramRegionWG) * tab.size()));
   c->raw_tables_ok = true;
   return OVGPU_OK;
 }
@@ -769,16 +752,14 @@ static int begin_feature_batch(ovgpu_ctx *c, int F, int M, const int32_t *offset
   HIPCHK(c->anchor_pre.reserve(F));
   HIPCHK(c->status.reserve(F));
 
-  hipStream_t s = c->stream;
   std::vector<int32_t> order(std::max(F, 1), 0);
   track_order(offsets, F, m_max, order.data()); // longest track first
   c->h_order.assign(order.begin(), order.begin() + F);
   HIPCHK(c->sys_order.reserve(std::max(F, 1)));
-  (void)s;
-  HIPCHK(upload_deferred(c, c->sys_order.p, order.data(), sizeof(int32_t) * F));
-  HIPCHK(upload_deferred(c, c->meas_offsets.p, c->h_offsets.data(), sizeof(int32_t) * (F + 1)));
+  HIPCHK(c->up.put(c->sys_order.p, order.data(), sizeof(int32_t) * F));
+  HIPCHK(c->up.put(c->meas_offsets.p, c->h_offsets.data(), sizeof(int32_t) * (F + 1)));
   if (c->chi2_table_dev != c->chi2_table.p || c->chi2_table_dev_len != c->chi2_table_len) { // (the table only ever grows: uploaded when it did)
-    HIPCHK(upload_deferred(c, c->chi2_table.p, c->h_chi2_table.data(), sizeof(double) * c->chi2_table_len));
+    HIPCHK(c->up.put(c->chi2_table.p, c->h_chi2_table.data(), sizeof(double) * c->chi2_table_len));
     c->chi2_table_dev = c->chi2_table.p, c->chi2_table_dev_len = c->chi2_table_len;
   }
   // (host staging vectors go out of scope: the arena keeps their bytes; the scatter launch is end_feature_batch's)
@@ -805,7 +786,7 @@ int ovgpu_set_features(ovgpu_ctx *c, const ovgpu_features_view *fv) {
   if (fv->F > 0 && (!fv->meas_offsets)) return set_err(OVGPU_ERR_INVALID, "null feature arrays");
   if (fv->M > 0 && (!fv->uv || !fv->uvn || !fv->clone_idx || !fv->cam_idx)) return set_err(OVGPU_ERR_INVALID, "null measurement arrays");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(upload_begin(c));
+  HIPCHK(c->up.begin());
   const int F = fv->F, M = fv->M;
   if (F > 0 && (fv->meas_offsets[0] != 0 || fv->meas_offsets[F] != M)) return set_err(OVGPU_ERR_INVALID, "meas_offsets must span [0, M]");
   // The prior block's factorisation (75 us on a dozen compute units) needs the resident state alone: it starts HERE, on the second stream, while
@@ -818,8 +799,7 @@ int ovgpu_set_features(ovgpu_ctx *c, const ovgpu_features_view *fv) {
   // 0.08 ms per 100 k measurements on the caller's thread)
   // (packed straight into the page-locked arena when the scatter path is on: one pass over the caller's indices instead of a pass and a copy;
   //  a batch that fails the range test leaves the resident one untouched)
-  size_t cc_off = 0;
-  void *cc_arena = upload_arena_take(c, sizeof(uint16_t) * (size_t)M, &cc_off);
+  void *cc_arena = c->up.take(sizeof(uint16_t) * (size_t)M);
   if (!cc_arena) c->h_cc.resize((size_t)std::max(M, 1));
   uint16_t *cc = cc_arena ? static_cast<uint16_t *>(cc_arena) : c->h_cc.data();
   {
@@ -836,21 +816,19 @@ int ovgpu_set_features(ovgpu_ctx *c, const ovgpu_features_view *fv) {
   const int32_t zero = 0;
   int rc = begin_feature_batch(c, F, M, F > 0 ? fv->meas_offsets : &zero);
   if (rc != OVGPU_OK) return rc;
-  if (cc_arena) HIPCHK(upload_deferred_taken(c, c->meas_cc.p, cc_off, sizeof(uint16_t) * (size_t)M));
+  if (cc_arena) HIPCHK(c->up.commit(c->meas_cc.p, cc_arena, sizeof(uint16_t) * (size_t)M));
   if ((rc = raw_stack_layout(c, cc)) != OVGPU_OK) return rc;
-  hipStream_t s = c->stream;
   // Order of departure (round 6): the small tables and the packed codes first — one scatter launch, then the batch's integer tables, which
   // need nothing else (end_feature_batch) —, the pixel coordinates behind them in two launches of 0.8 MB per 100 k measurements: the device
   // builds the tables and moves the first array while this thread still packs the second.
-  if (!cc_arena) HIPCHK(upload_deferred(c, c->meas_cc.p, cc, sizeof(uint16_t) * M));
+  if (!cc_arena) HIPCHK(c->up.put(c->meas_cc.p, cc, sizeof(uint16_t) * M));
   const int rce = end_feature_batch(c);
   if (rce != OVGPU_OK) return rce;
-  HIPCHK(upload_deferred(c, c->uv.p, fv->uv, sizeof(float) * 2 * M));
-  HIPCHK(upload_flush(c));
-  HIPCHK(upload_deferred(c, c->uvn.p, fv->uvn, sizeof(float) * 2 * M));
+  HIPCHK(c->up.put(c->uv.p, fv->uv, sizeof(float) * 2 * M));
+  HIPCHK(c->up.flush());
+  HIPCHK(c->up.put(c->uvn.p, fv->uvn, sizeof(float) * 2 * M));
   // No synchronisation here (round 4): everything above left the page-locked arena asynchronously, the kernels of the update queue
-  // behind the copies on the same stream, and the arena is not reused before a synchronisation has been seen (upload_begin appends).
-  // An upload that had to bypass the arena is fenced (its host source goes out of scope with this call).
-  HIPCHK(upload_fence(c, s));
+  // behind the copies on the same stream, and the arena is not reused before a synchronisation has been seen (Uplink::begin appends).
+  HIPCHK(c->up.flush());
   return OVGPU_OK;
 }

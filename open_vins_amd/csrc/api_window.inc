@@ -170,7 +170,7 @@ int ovgpu_state_marginalize_batched(ovgpu_ctx *c, int32_t n, const int32_t *cov_
   const int Nn = N - gone; // (>= 6: a clone stays)
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  HIPCHK(upload_begin(c));
+  HIPCHK(c->up.begin());
   HIPCHK(c->marg_tab.reserve(tab.size() + (size_t)N + 2 * (size_t)C + L));
   HIPCHK(c->Ppad.reserve((size_t)Nn * Nn));
   HIPCHK(c->clone_qp_b.reserve(std::max<size_t>(c->clone_qp.cap, 1)));
@@ -180,8 +180,8 @@ int ovgpu_state_marginalize_batched(ovgpu_ctx *c, int32_t n, const int32_t *cov_
   HIPCHK(c->lm_anchor_b.reserve(std::max<size_t>(c->lm_anchor.cap, 1)));
   HIPCHK(c->lm_repd_b.reserve(std::max<size_t>(c->lm_repd.cap, 1)));
   // ---- the device pass (a HIP error from here on is reported; the host tables below change only behind the launches)
-  HIPCHK(upload_deferred(c, c->marg_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
-  HIPCHK(upload_fence(c, s));
+  HIPCHK(c->up.put(c->marg_tab.p, tab.data(), sizeof(int32_t) * tab.size()));
+  HIPCHK(c->up.flush());
   MargPlan mp;
   mp.N = N, mp.C = C, mp.L = L, mp.n = n;
   mp.blk = c->marg_tab.p, mp.clone_keep = mp.blk + 2 * n, mp.lm_keep = mp.clone_keep + C;
@@ -703,11 +703,11 @@ int ovgpu_tracks_to_features(ovgpu_ctx *c, int32_t F, const int64_t *featid, con
   } else {
     HIPCHK(upload_sync(c, s));
   }
-  HIPCHK(upload_begin(c)); // the stream is idle: the page-locked upload arena starts over
+  HIPCHK(c->up.begin()); // the stream is idle: the page-locked upload arena starts over
   const int M = offs[F];
   int rc = begin_feature_batch(c, F, M, offs.data());
   if (rc != OVGPU_OK) return rc;
-  HIPCHK(upload_flush(c)); // (the gather below reads the offsets begin_feature_batch packed)
+  HIPCHK(c->up.flush()); // (the gather below reads the offsets begin_feature_batch packed)
   if (F > 0) {
     const Batch b = batch_of(c); // (the batch begin_feature_batch made room for)
     hipLaunchKernelGGL(k_tracks_gather, dim3((F + 127) / 128), dim3(128), 0, s, F, K, C, c->trk_sel.p, c->trk_clone_times.p, track_store(c), c->trk_nvalid.p,

@@ -45,6 +45,7 @@
 #include "k_init_fused.h"
 #include "ovgpu_types.h"
 #include "dev_buf.h"
+#include "host_link.h"
 
 // The fused per-feature kernels live in the second translation unit (ovgpu_featy_tu.hip: its own scheduler strategy); here they are
 // only declared, so that their launches below bind to those definitions.
