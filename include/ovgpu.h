@@ -687,6 +687,11 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_stat
  * ovgpu_options::no_single_launch_cholesky is set or ovgpu_debug_option "delayed_init_fused" is 0 (then the outputs are
  * ovgpu_slam_delayed_init's bit for bit).  "delayed_init_fused_steps" / "delayed_init_chain_steps" count the candidates of this
  * entry by the step they took.  A time-out of the factorisation's bounded waits is reported as OVGPU_ERR_HIP, as there.
+ * At level 2 of "delayed_init_fused" (default 1) chi2 is the statistic of the projected system's own factorisation,
+ * |U^-T res2|^2 with S = A2 P A2^T + sigma^2 I = U^T U: the same number to rounding, the verdicts identical for a candidate
+ * that does not sit on its threshold.  A rejected candidate then costs the step's first four launches (the system's rows, the
+ * two products, the factorisation) where level 1 pays the per-feature kernel alone; a candidate whose triangulation failed
+ * costs neither.  "delayed_init_rows_steps" counts the candidates that took the step at level 2.
  * Callers find the entry by symbol (ABI 10).                                                                      */
 int ovgpu_slam_delayed_init_fused(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_status, double *chi2,
                                   double *chi2_thresh, int32_t *lm_cov_id, double *lm_value,
@@ -1180,7 +1185,13 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             sets the last two only
  *   "slam_chunked_fallbacks"  number of ovgpu_slam_update_chunked passes that put the entry state back and ran the chunks one by one
  *                             (a value >= 0 sets the counter)
- *   "delayed_init_fused"      (default 1) 0: ovgpu_slam_delayed_init_fused runs ovgpu_slam_delayed_init's step for every candidate
+ *   "delayed_init_fused"      (default 1) a level; the read-back returns it (values above 2 are taken as 2).
+ *                             0: ovgpu_slam_delayed_init_fused runs ovgpu_slam_delayed_init's step for every candidate
+ *                             1: the fused step of five launches; its first, the general per-feature kernel, decides the gate ahead of the step
+ *                             2: the fused step with the gate-free k_init_rows as its first launch; the step's tail decides the gate from the
+ *                                residual the factorisation of the projected system carries (chi2 = |U^-T res2|^2)
+ *   "delayed_init_rows_steps" number of candidates of ovgpu_slam_delayed_init_fused that took the fused step at level 2 (a value >= 0 sets the
+ *                             counter); "delayed_init_fused_steps" counts the fused steps of either level
  *   "delayed_init_fused_steps" / "delayed_init_chain_steps"  number of candidates of ovgpu_slam_delayed_init_fused that took the fused step /
  *                             the chain's step (a track beyond the fused step's bound, or the switch above; a value >= 0 sets the counter)
  *   "slam_chunked_fail_chunk" k >= 0: the next ovgpu_slam_update_chunked treats chunk k's flag word as failed after its pass and takes

@@ -220,8 +220,10 @@ struct ovgpu_ctx {
   DevBuf<double> chk_dx, chk_save;
   int chunk_fail_inject = -1;   // ovgpu_debug_option "slam_chunked_fail_chunk": this chunk's flag word reads as failed after the pass (one-shot; tests of the restore-and-chain path)
   int64_t chunk_fallbacks = 0;  // ovgpu_debug_option "slam_chunked_fallbacks": how often ovgpu_slam_update_chunked put the entry state back and ran the chain
-  bool init_fused_on = true;    // ovgpu_debug_option "delayed_init_fused": 0 makes ovgpu_slam_delayed_init_fused run the chain's step for every candidate
+  int init_fused = 1;           // ovgpu_debug_option "delayed_init_fused", a level.  0: ovgpu_slam_delayed_init_fused runs the chain's step for every candidate;
+                                // 1: the fused step behind k_system_t's gate; 2: the fused step behind k_init_rows, the gate taken from the step's own factorisation
   int64_t init_fused_steps = 0, init_chain_steps = 0; // "delayed_init_fused_steps" / "delayed_init_chain_steps": candidates of ovgpu_slam_delayed_init_fused by the step they took
+  int64_t init_rows_steps = 0;  // "delayed_init_rows_steps": those of the fused steps that ran at level 2
   // SLAM landmarks (ovgpu_set_landmarks); L > 0 switches the per-feature kernel to the UpdaterSLAM rules
   int L = 0;
   // the resident landmarks' representations, one each (Landmark::_feat_representation: StateOptions::feat_rep_slam, or feat_rep_aruco for

@@ -11,12 +11,15 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "slam_chunked_fallbacks") { // reads the count of restore-and-chain passes; a value >= 0 sets it
     if (old_value) *old_value = c->chunk_fallbacks;
     if (value >= 0) c->chunk_fallbacks = value;
-  } else if (n == "delayed_init_fused") { // 0: ovgpu_slam_delayed_init_fused runs the chain's step (enqueue_init_feature) for every candidate
-    if (old_value) *old_value = c->init_fused_on ? 1 : 0;
-    if (value >= 0) c->init_fused_on = value != 0;
+  } else if (n == "delayed_init_fused") { // a level.  0: ovgpu_slam_delayed_init_fused runs the chain's step (enqueue_init_feature) for every candidate; 1: the fused step, gated by k_system_t ahead of it (default); 2 (and above): the fused step behind k_init_rows, the gate read off the step's own factorisation in its tail; reads back the level
+    if (old_value) *old_value = c->init_fused;
+    if (value >= 0) c->init_fused = (int)std::min<int64_t>(value, 2);
   } else if (n == "delayed_init_fused_steps") { // reads the count of candidates that took the fused step; a value >= 0 sets it
     if (old_value) *old_value = c->init_fused_steps;
     if (value >= 0) c->init_fused_steps = value;
+  } else if (n == "delayed_init_rows_steps") { // ... of those that took it at level 2 (k_init_rows in place of k_system_t)
+    if (old_value) *old_value = c->init_rows_steps;
+    if (value >= 0) c->init_rows_steps = value;
   } else if (n == "delayed_init_chain_steps") { // ... and of those ovgpu_slam_delayed_init_fused ran as the chain runs them
     if (old_value) *old_value = c->init_chain_steps;
     if (value >= 0) c->init_chain_steps = value;

@@ -116,12 +116,9 @@ static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams
   return OVGPU_OK;
 }
 
-// f_one >= 0: only that feature, in StateHelper::initialize mode with the landmark representation init_rep
-// whiten: the rows leave as [H L | r] with L = c->Lw (the prior block's factor must be complete on this stream)
-static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool whiten = false) {
-  const Batch b = batch_of(c);
-  if (b.F == 0) return OVGPU_OK;
-  SysParams p;
+// The per-feature stage's parameters from the context and the batch in force, for a launch over the whole batch on the unwhitened route
+// (enqueue_system and k_init_rows' launch, api_slam.inc, start from these)
+static void fill_sys_params(ovgpu_ctx *c, const Batch &b, SysParams &p) {
   p.F = b.F, p.C = c->C, p.K = c->K, p.D = c->D, p.LD = c->LD, p.N = c->N;
   p.meas_offsets = b.meas_offsets, p.meas_cc = b.meas_cc, p.uv = b.uv;
   p.tab_clone = c->tab_clone.p, p.tab_cam = c->tab_cam.p, p.intr = c->intr.p, p.fisheye = c->fisheye.p;
@@ -132,7 +129,6 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   p.chi2_table = c->chi2_table.p, p.chi2_table_len = c->chi2_table_len;
   p.row_off = b.row_off, p.Hbig = c->Hbig.p, p.ws = c->gate_ws.p, p.ws_stride = c->plan.gate_ws_stride;
   p.Hbig32 = nullptr, p.LDF = 0;
-  c->stack_is_f32 = false;
   p.m_lds_max = c->plan.m_lds_max, p.m_max = std::max(b.m_max, 1), p.row_stride = c->row_stride;
   p.opt = c->dopt;
   p.dbg = c->dbg_cycles.p ? c->dbg_cycles.p : qr_dbg_buffer();
@@ -145,22 +141,36 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   }
   p.f_begin = 0, p.f_end = b.F, p.init = 0, p.init_out = nullptr, p.init_flag = nullptr, p.init_keep = 0, p.order = b.sys_order;
   p.rows_used = c->rows_used.p;
-  p.Lw = (whiten && f_one < 0) ? c->Lw.p : nullptr;
+  p.Lw = nullptr;
   p.skip = c->featy_skip;
   // The Gram route's stack as unprojected rows in regions by column reach (ovgpu_types.h: RawStack; the whitened stack only ever feeds the Gram kernels):
-  // the one-pass fused kernels on a batch laid out by ovgpu_set_features, float64 stack.  Decided below, once the kernel shape is known.
+  // the one-pass fused kernels on a batch laid out by ovgpu_set_features, float64 stack.  enqueue_system decides, once the kernel shape is known.
   p.raw.on = 0;
+}
+
+// ... narrowed to feature f_one in StateHelper::initialize mode with the landmark representation init_rep
+static void sys_params_init_mode(ovgpu_ctx *c, SysParams &p, int f_one, int init_rep) {
+  p.order = nullptr;
+  p.rows_used = nullptr;
+  p.f_begin = f_one, p.f_end = f_one + 1, p.init = 1, p.init_out = c->init_ws.p, p.init_flag = c->init_ctr.p + 2;
+  p.init_keep = c->init_export ? 1 : 0; // ovgpu_slam_init_systems: the host decides the gate again, rejected features are exported too
+  p.opt.feat_rep = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH : init_rep; // UpdaterSLAM.cpp:151-155
+  p.init_dof_less = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 2 : 0;
+}
+
+// f_one >= 0: only that feature, in StateHelper::initialize mode with the landmark representation init_rep
+// whiten: the rows leave as [H L | r] with L = c->Lw (the prior block's factor must be complete on this stream)
+static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool whiten = false) {
+  const Batch b = batch_of(c);
+  if (b.F == 0) return OVGPU_OK;
+  SysParams p;
+  fill_sys_params(c, b, p);
+  c->stack_is_f32 = false;
+  p.Lw = (whiten && f_one < 0) ? c->Lw.p : nullptr;
   c->last_stack_raw = false;
   if (f_one < 0) c->last_feat_kernel = FK_GENERAL;
   if (f_one < 0) HIPCHK(ctrl_zero(c, CTRL_ROWS, c->rows_used.p, 2 * sizeof(int32_t), c->stream));
-  if (f_one >= 0) {
-    p.order = nullptr;
-    p.rows_used = nullptr;
-    p.f_begin = f_one, p.f_end = f_one + 1, p.init = 1, p.init_out = c->init_ws.p, p.init_flag = c->init_ctr.p + 2;
-    p.init_keep = c->init_export ? 1 : 0; // ovgpu_slam_init_systems: the host decides the gate again, rejected features are exported too
-    p.opt.feat_rep = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? OVGPU_REP_ANCHORED_MSCKF_INVERSE_DEPTH : init_rep; // UpdaterSLAM.cpp:151-155
-    p.init_dof_less = init_rep == OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 2 : 0;
-  }
+  if (f_one >= 0) sys_params_init_mode(c, p, f_one, init_rep);
   const FeatLaunch s = select_feat_kernel(c, p, b.F, f_one);
   if (s.err != OVGPU_OK) return set_err(s.err, s.msg);
   if (s.cb) { // the head of the MSCKF fast path

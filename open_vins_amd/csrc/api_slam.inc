@@ -526,13 +526,31 @@ static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap
   return OVGPU_OK;
 }
 
+// The system of candidate f without its gate (k_init_rows, k_init_fused.h): enqueue_system's parameters for f_one = f, one workgroup whose carve
+// holds the fused step's longest track at most
+static int enqueue_init_rows(ovgpu_ctx *c, int f, int rep) {
+  const Batch b = batch_of(c);
+  SysParams p;
+  fill_sys_params(c, b, p);
+  sys_params_init_mode(c, p, f, rep);
+  c->stack_is_f32 = false, c->last_stack_raw = false; // (as enqueue_system leaves them: the candidate's rows are float64 and projected)
+  p.P = nullptr, p.ws = nullptr, p.init_keep = 0;      // nothing of the gate is read
+  p.m_max = std::min(p.m_max, INITF_M_MAX);
+  const size_t lds = init_rows_lds_layout(p.m_max, p.row_stride).total; // (42496 bytes at the bound and 72-double records: under the 64 KB every kernel may ask for)
+  if (p.row_stride > 72) return set_err(OVGPU_ERR_INVALID, "internal: k_init_rows' carve is sized for records of 72 doubles at most");
+  hipLaunchKernelGGL(k_init_rows, dim3(1), dim3(SYS_NT), lds, c->stream, p);
+  HIPCHK(hipGetLastError());
+  return OVGPU_OK;
+}
+
 // One candidate as the fused step (k_init_fused.h): five launches, no memset.  The caller has checked initf_holds(c, m).
+// level 1: k_system_t decides the gate ahead of the step; 2: k_init_rows, and the tail decides it from the factorisation's carried residual.
 static bool initf_holds(const ovgpu_ctx *c, int m) { return m >= 2 && m <= INITF_M_MAX && chol_pipe_usable(c, 2 * m - 3); }
-static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, double *dx) {
+static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, double *dx, int level) {
   hipStream_t s = c->stream;
   const Batch b = batch_of(c);
   const int m = b.h_offsets[f + 1] - b.h_offsets[f], r = 2 * m - 3;
-  int rc = enqueue_system(c, f, rep);
+  int rc = level >= 2 ? enqueue_init_rows(c, f, rep) : enqueue_system(c, f, rep);
   if (rc != OVGPU_OK) return rc;
   c->last_update_tform = false;
   InitFusedParams p;
@@ -554,7 +572,8 @@ static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, do
   q.D = r, q.LA = p.LA, q.A = p.A, q.Y = c->Yaug.p, q.Lt = nullptr, q.flags = c->flags.p, q.diag0 = nullptr, q.pivot_tol = 1e-13, q.pred = c->init_ctr.p + 2;
   q.src = chol::CH_SRC_MATRIX, q.N = Nmax, q.pred_not = nullptr;
   if ((rc = launch_chol_fused(c, q, slot, s)) != OVGPU_OK) return rc;
-  hipLaunchKernelGGL(k_initf_tail, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p);
+  if (level >= 2) hipLaunchKernelGGL(k_initf_tail_gate, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p, InitGateParams{b.chi2_thr, b.chi2, b.status});
+  else hipLaunchKernelGGL(k_initf_tail, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
@@ -652,9 +671,10 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   for (int f = 0; f < F && rc == OVGPU_OK; f++) {
     const int m = b.h_offsets[f + 1] - b.h_offsets[f];
     if (m < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
-    if (fused && c->init_fused_on && initf_holds(c, m)) {
-      rc = enqueue_init_feature_fused(c, f, ch.rep[f], Nmax, c->dx_seq.p + (size_t)f * Nmax);
+    if (fused && c->init_fused > 0 && initf_holds(c, m)) {
+      rc = enqueue_init_feature_fused(c, f, ch.rep[f], Nmax, c->dx_seq.p + (size_t)f * Nmax, c->init_fused);
       c->init_fused_steps++;
+      if (c->init_fused >= 2) c->init_rows_steps++;
       continue;
     }
     rc = enqueue_init_feature(c, f, ch.rep[f], Nmax, L0 + F, ch.init_lds, c->dx_seq.p + (size_t)f * Nmax, nullptr);

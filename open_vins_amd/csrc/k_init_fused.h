@@ -22,14 +22,172 @@
 // The only waits of the step are k_chol_fused's bounded ones.
 //
 // Bound: 2m - 3 + 3 <= 128 rows of W (eight 16-row tiles), m <= INITF_M_MAX = 64; a longer track takes the chain of single launches.
+//
+// Level 2 of ovgpu_debug_option "delayed_init_fused": the gate is taken from the chain's own factor.  k_chol_fused carries res2 through
+// S = U^T U to y = U^-T res2, and |y|^2 = res2^T (A2_x P_DD A2_x^T + sigma^2 I)^-1 res2 is the statistic StateHelper::initialize gates on
+// (StateHelper.cpp:466; rows scaled by sigma / sigma_f scale S by its square and res2 by itself: the statistic does not see the scale).  So
+//
+//   k_init_rows                          A1, R1, A2 and the threshold as k_system_t's init mode leaves them, WITHOUT its gate: nothing of P is read
+//   k_initf_w, k_initf_s, k_chol_fused   as above, predicated on ctr[2] = "the candidate was triangulated"
+//   k_initf_tail_gate                    every workgroup forms chi2 = |y|^2 in one fixed order and decides alone; a rejected candidate writes
+//                                        chi2 and its status (the last workgroup) and nothing else
 #pragma once
 #include "k_ekf.h"
 #include "k_slam.h"
+#include "k_system.h"
 #include "k_triangulate.h"
 
 namespace ovg {
 
 constexpr int INITF_M_MAX = 64;
+
+// k_init_rows' LDS carve in bytes for a launch whose candidate holds at most m_max measurements (host and device agree on this): the Jacobian
+// records at the context's row stride, their bookkeeping, V of the three reflectors, the representation scratch.  64 measurements of 72 doubles:
+// 42496 bytes.
+struct InitRowsLds {
+  size_t minfo, rows, V, hq, total;
+};
+__host__ __device__ inline InitRowsLds init_rows_lds_layout(int m_max, int row_stride) {
+  InitRowsLds L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += (bytes + 15) & ~(size_t)15;
+    return at;
+  };
+  L.minfo = take((size_t)m_max * 8 * sizeof(int));
+  L.rows = take((size_t)m_max * row_stride * sizeof(double));
+  L.V = take((size_t)2 * m_max * 3 * sizeof(double));
+  L.hq = take(64 * sizeof(double)); // [0..2] tau, [3..8] T, [12..20] dpfg_dlambda, [21..38] H_anc, [39..56] H_calib, [58..60] diag(R1)
+  L.total = o;
+  return L;
+}
+
+// The system of ONE candidate (p.f_begin) of the delayed initialisation without the gate: phases (a0), (a), (b) and the unwhitened (d) of
+// k_system_t for p.init = 1 (an MSCKF-style system: all three columns of H_f are projected), through the same device functions.  One workgroup.
+//   init_out[0 .. 3 LD) = oscale Q1^T [H_x | res],  init_out[3 LD .. + 9) = oscale R1,  the candidate's rows of Hbig = oscale Q2^T [H_x | res],
+//   chi2_thresh[f],  init_flag[0] = the candidate arrived OVGPU_FEAT_USED.
+// Neither chi2[f] nor status[f] is written, neither P nor the gate's workspaces are read.  p.m_max sizes the carve (the host passes the fused
+// step's bound when the batch's longest track is beyond it).
+__global__ void __launch_bounds__(SYS_NT) k_init_rows(SysParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int D = p.D, LD = p.LD, RS = p.row_stride;
+  const InitRowsLds lo = init_rows_lds_layout(p.m_max, RS);
+  int *minfo = reinterpret_cast<int *>(smem + lo.minfo);
+  double *rows = reinterpret_cast<double *>(smem + lo.rows);
+  double *V = reinterpret_cast<double *>(smem + lo.V);
+  double *hq = reinterpret_cast<double *>(smem + lo.hq);
+
+  const int f = p.f_begin;
+  const int m0 = p.meas_offsets[f];
+  const int m = p.meas_offsets[f + 1] - m0;
+  const int64_t orow0 = p.row_off[f];
+  const int n_out = (int)(p.row_off[f + 1] - orow0); // 2m - 3
+  if (p.status[f] != OVGPU_FEAT_USED || m < 2 || m > p.m_max) { // failed before the gate (or a track the carve does not hold: the host never sends one)
+    for (int64_t e = tid; e < (int64_t)n_out * LD; e += SYS_NT) p.Hbig[orow0 * LD + e] = 0.0;
+    if (tid == 0) p.init_flag[0] = 0;
+    return;
+  }
+  const int n = 2 * m;
+  constexpr int nproj = 3;
+
+  // (a0) representation Jacobian — UpdaterHelper.cpp:32-190
+  const int rep_f = p.opt.feat_rep;
+  const bool relative = rep_is_relative(rep_f);
+  const double mult_f = p.feat_chi2mult ? p.feat_chi2mult[f] : p.opt.chi2_multipler;
+  const double oscale = p.feat_sigma ? sqrt(p.opt.sigma_pix_sq) / p.feat_sigma[f] : 1.0; // (k_system_t: the stack keeps ONE isotropic noise level)
+  V3 p_FinG = load_v3(p.p_FinG + 3 * f);
+  int anchor_cam = -1, anchor_clone = -1;
+  if (relative) { // the anchor of the triangulation
+    const int ac = p.meas_cc[p.anchor_meas[f]];
+    anchor_cam = ac >> 10, anchor_clone = ac & 1023;
+    const V3 p_FinA = load_v3(p.p_FinA + 3 * f);
+    const M3 R_ItoC = load_m3(p.tab_cam + 12 * anchor_cam);
+    const V3 p_IinC = load_v3(p.tab_cam + 12 * anchor_cam + 9);
+    const M3 R_GtoI = load_m3(p.tab_clone + 24 * anchor_clone);
+    const V3 p_IinG = load_v3(p.tab_clone + 24 * anchor_clone + 9);
+    p_FinG = mulT(R_GtoI, mulT(R_ItoC, p_FinA - p_IinC)) + p_IinG; // UpdaterHelper.cpp:274
+  }
+  const V3 p_FinG_fej = p_FinG; // fej == value for a feature that is not in the state yet (UpdaterMSCKF.cpp:186-194, UpdaterHelper.cpp:279-283)
+  if (tid == 0) {
+    double *dl = hq + 12;
+    if (rep_f == OVGPU_REP_GLOBAL_3D) {
+      dl[0] = 1, dl[1] = 0, dl[2] = 0, dl[3] = 0, dl[4] = 1, dl[5] = 0, dl[6] = 0, dl[7] = 0, dl[8] = 1;
+    } else if (rep_f == OVGPU_REP_GLOBAL_FULL_INVERSE_DEPTH) {
+      inv_depth_jac(p_FinG, dl); // UpdaterHelper.cpp:46
+    } else {
+      anchored_rep_jacobian(rep_f, p.opt.do_fej, p.tab_cam + 12 * anchor_cam, p.tab_clone + 24 * anchor_clone, load_v3(p.p_FinA + 3 * f), dl, hq + 21, hq + 39);
+    }
+    // StateHelper::initialize gates against the quantile of the res.rows() it was handed: 2m, or 2m - 2 when the bearing was projected out
+    // before (StateHelper.cpp:466, UpdaterSLAM.cpp:181-196)
+    p.chi2_thresh[f] = mult_f * p.chi2_table[min(n - p.init_dof_less, p.chi2_table_len - 1)];
+    p.init_flag[0] = 1;
+  }
+  __syncthreads();
+
+  // (a) per-measurement sparse Jacobian rows — UpdaterHelper.cpp:314-421
+  for (int i = tid; i < m; i += SYS_NT) sys_measurement_rows(p, m0 + i, p_FinG, p_FinG_fej, relative, hq, minfo + 8 * i, rows + (size_t)i * RS);
+  __syncthreads();
+
+  // (b) Householder QR of H_f (2m x 3) -> V, tau, T
+  if (tid < 64) sys_hf_householder(rows, RS, V, hq, n, nproj, tid);
+  __syncthreads();
+
+  // (d) thread per column: rows 0..2 of Q^T [H_x | res] -> init_out, rows 3..n-1 -> Hbig (k_system_t's unwhitened stack, p.init)
+  const double T00 = hq[3], T01 = hq[4], T02 = hq[5], T11 = hq[6], T12 = hq[7], T22 = hq[8];
+  for (int c = tid; c < LD; c += SYS_NT) {
+    int kind = COL_RESIDUAL, var = 0, sub = 0;
+    if (c < D) kind = p.col_kind[c], var = p.col_var[c], sub = p.col_sub[c];
+    const bool anc_hit_c = (kind == COL_CLONE && var == anchor_clone && relative);
+    const bool anc_hit_p = (kind == COL_CALIB_POSE && var == anchor_cam && relative && p.opt.do_calib_pose);
+    const int kclone = (kind == COL_CLONE) ? var : -1000;
+    const int kcam = (kind == COL_CALIB_POSE || kind == COL_CALIB_INTR) ? var : -1000; // such a column exists only for a calibrated camera
+    const bool whole = kind == COL_RESIDUAL; // (a landmark's column: no candidate touches a resident landmark)
+    const int off0 = kind == COL_RESIDUAL ? RO_RES
+                                          : (kind == COL_CLONE ? RO_CLONE + sub
+                                                               : (kind == COL_CALIB_POSE ? RO_CPOSE + sub : (kind == COL_CALIB_INTR ? RO_CINTR + sub : RO_HF + sub)));
+    const int astr = kind == COL_RESIDUAL ? 1 : (kind == COL_CALIB_INTR ? 8 : (kind == COL_LANDMARK ? 3 : 6));
+    auto hval = [&](int i, int a) -> double {
+      const int2 key = *reinterpret_cast<const int2 *>(minfo + 8 * i); // (camera, clone)
+      const double *rd = rows + (size_t)i * RS;
+      const double hv = rd[off0 + astr * a];
+      double h = (whole || key.y == kclone || key.x == kcam) ? hv : 0.0;
+      if (anc_hit_c) h += rd[RO_ANC + 6 * a + sub];
+      if (anc_hit_p) h += rd[RO_ACAL + 6 * a + sub];
+      return h;
+    };
+    double y0 = 0, y1 = 0, y2 = 0; // y = V^T h
+#pragma unroll 4
+    for (int i = 0; i < m; i++) {
+      const double h0 = hval(i, 0), h1 = hval(i, 1);
+      const double *v = V + (size_t)6 * i;
+      y0 = fma(v[0], h0, y0), y1 = fma(v[1], h0, y1), y2 = fma(v[2], h0, y2);
+      y0 = fma(v[3], h1, y0), y1 = fma(v[4], h1, y1), y2 = fma(v[5], h1, y2);
+    }
+    const double z0 = T00 * y0, z1 = T01 * y0 + T11 * y1, z2 = T02 * y0 + T12 * y1 + T22 * y2; // z = T^T y
+    double *out = p.Hbig + orow0 * LD + c;
+#pragma unroll 4
+    for (int r = 0; r < n; r++) { // StateHelper.cpp:445-448: the first three rows determine the new variable, the others are gated and update
+      const double h = hval(r >> 1, r & 1);
+      const double *v = V + (size_t)3 * r;
+      const double q = oscale * (h - (v[0] * z0 + v[1] * z1 + v[2] * z2));
+      if (r < nproj) p.init_out[(size_t)r * LD + c] = q;
+      else out[(size_t)(r - nproj) * LD] = q;
+    }
+  }
+  if (tid < 9) { // H_finit = R1 (3 x 3 upper triangular): Q^T H_f, diagonal = beta
+    const int i = tid / 3, j = tid % 3;
+    p.init_out[(size_t)3 * LD + tid] = oscale * (j < i ? 0.0 : (j == i ? hq[58 + i] : rows[(size_t)(i >> 1) * RS + RO_HF + 3 * (i & 1) + j]));
+  }
+}
+
+// What the gated tail (level 2) reads and writes beyond InitFusedParams: the batch's gate arrays
+struct InitGateParams {
+  const double *chi2_thresh; // [F] written by k_init_rows
+  double *chi2;              // [F]
+  int32_t *status;           // [F]
+};
 
 struct InitFusedParams {
   int N;                    // leading dimension of P (the padded capacity) = carried covariance columns
@@ -45,7 +203,7 @@ struct InitFusedParams {
   double *T;                // [3 x N] G P(cols, :)
   double *PLL;              // [9] G P_DD G^T + sigma^2 R1^-1 R1^-T
   double sigma2;
-  int32_t *ctr;             // [0] covariance dimension, [1] landmark count, [2] this candidate passed the gate, [4] arrivals of the tail's workgroups
+  int32_t *ctr;             // [0] covariance dimension, [1] landmark count, [2] this candidate passed the gate (level 2: was triangulated), [4] arrivals of the tail's workgroups
   int32_t *prog;            // [16] k_chol_fused's step words (cleared by k_initf_s)
   double *dx;               // [N] row f of dx_seq
   int32_t *flags;           // [1] = 1: a negative diagonal of P after the update
@@ -169,13 +327,41 @@ __global__ void __launch_bounds__(256) k_initf_s(InitFusedParams p) {
 // columns taken from T and P_LL (symmetric by construction: Z^T Z is, -T is mirrored, P_LL is averaged with its transpose).  The last workgroup:
 // dx = Z^T y, Landmark::update of the resident landmarks, the new landmark, box-plus of clones / calibration / intrinsics, the pose tables.  The
 // workgroup that arrives last advances the dimension and the landmark count.
-__global__ void __launch_bounds__(256) k_initf_tail(InitFusedParams p) {
+//
+// GATE (level 2): ctr[2] only says that the candidate was triangulated, and the decision is taken here.  Every workgroup sums y_k^2 over the r rows
+// of the factorisation's carried residual column in ONE order — wavefront 0: lane-strided partial sums, a fixed butterfly, broadcast through LDS —
+// so all of them hold the same bits and take the same branch without a word between them.  reject = chi2 > thr (k_system_t's comparison).  A
+// rejected candidate: the last workgroup writes chi2 and the status, nobody writes anything else, the arrivals are counted and reset, the
+// dimension and the landmark count stay.
+template <bool GATE> __device__ __forceinline__ void initf_tail_body(const InitFusedParams &p, const InitGateParams &g) {
   if (p.ctr[2] == 0) return; // (every workgroup reads the same word: all of them leave, nobody counts)
   const int lane = threadIdx.x & 63, tid = threadIdx.x;
   const int r = p.r, LA = p.LA, N = p.N;
   const int id = p.ctr[0], slot = p.ctr[1], j0 = 3 - p.sz, n1 = id + p.sz;
   const double *Z = p.Y + r;
-  if (blockIdx.x + 1 < gridDim.x) {
+  bool reject = false;
+  if constexpr (GATE) {
+    __shared__ double chi2_s;
+    if (tid < 64) {
+      double s = 0.0;
+      for (int k = lane; k < r; k += 64) {
+        const double yk = p.Y[(size_t)k * LA + r + N];
+        s = fma(yk, yk, s);
+      }
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (lane == 0) chi2_s = s;
+    }
+    __syncthreads();
+    const double chi2 = chi2_s;
+    reject = chi2 > g.chi2_thresh[p.f];
+    if (blockIdx.x + 1 == gridDim.x && tid == 0) {
+      g.chi2[p.f] = chi2;
+      if (reject) g.status[p.f] = OVGPU_FEAT_CHI2_REJECTED;
+    }
+  }
+  if (reject) {
+    // (nothing of the state is written)
+  } else if (blockIdx.x + 1 < gridDim.x) {
     const int tile = blockIdx.x * 4 + (tid >> 6);
     const int tn = (N + 15) / 16;
     const int r0 = (tile / tn) * 16, c0 = (tile % tn) * 16;
@@ -244,8 +430,13 @@ __global__ void __launch_bounds__(256) k_initf_tail(InitFusedParams p) {
   __syncthreads();
   if (tid == 0) {
     __threadfence();
-    if (atomicAdd(p.ctr + 4, 1) == (int)gridDim.x - 1) p.ctr[0] = n1, p.ctr[1] = slot + 1, p.ctr[4] = 0;
+    if (atomicAdd(p.ctr + 4, 1) == (int)gridDim.x - 1) {
+      if (!reject) p.ctr[0] = n1, p.ctr[1] = slot + 1;
+      p.ctr[4] = 0;
+    }
   }
 }
+__global__ void __launch_bounds__(256) k_initf_tail(InitFusedParams p) { initf_tail_body<false>(p, InitGateParams{nullptr, nullptr, nullptr}); }
+__global__ void __launch_bounds__(256) k_initf_tail_gate(InitFusedParams p, InitGateParams g) { initf_tail_body<true>(p, g); }
 
 } // namespace ovg

@@ -5,7 +5,8 @@ in the tree and stores every output; `compare <a.npz> <b.npz>` compares two such
 nothing but instruction ORDER (a scheduler strategy, ovgpu_featy_tu.hip): no tolerance applies, and no oracle time is spent
 (tools/gpu_bitcompare.sh swaps the library files on one box).  `dump` also runs the entries that read the resident feature batch on
 small seeded landmark states (batch_scenarios below): used when a change is meant to touch host code only.  `fused <out.npz> <level>` runs
-SLAM updates with ovgpu_debug_option "slam_fused" at that level (fused_scenarios below): two builds must agree bit for bit at a level both know."""
+SLAM updates with ovgpu_debug_option "slam_fused" at that level (fused_scenarios below): two builds must agree bit for bit at a level both know.
+`init <out.npz> <level>` runs the delayed-initialisation scenarios with "delayed_init_fused" at that level (init_scenarios below), likewise."""
 import sys
 
 import numpy as np
@@ -162,6 +163,51 @@ def fused_scenarios(path, level):
     np.savez(path, **out)
 
 
+def init_scenarios(path, level):
+    """batch_scenarios' delayed-initialisation state (three resident landmarks, eight candidate tracks, one of them made a gross outlier here) with
+    "delayed_init_fused" = level: both entries, each followed by ovgpu_reset_state, and mode A.  Level 2 puts k_init_rows in front of the fused
+    step and the gate into its tail; ovgpu_slam_delayed_init and ovgpu_slam_init_systems keep their kernels at every level."""
+    import copy
+    from open_vins_amd import capi, synth
+    from open_vins_amd.updater import UpdaterMSCKF
+    opts = capi.default_options(chi2_multipler=1.0)
+    out = {}
+    cand = copy.copy(synth.make_slam_problem(2, L=3, lm_rep=np.array([0, 5, 2], np.int32), seed=21))
+    tracks = synth.make_problem(2, F=8, seed=22)
+    a, b = int(tracks.meas_offsets[3]), int(tracks.meas_offsets[4])
+    uv = tracks.uv.reshape(-1, 2).copy()
+    uv[a:b] += np.float32(15.0) * np.where(np.arange(2 * (b - a)).reshape(-1, 2) % 3 == 0, -1, 1).astype(np.float32)  # (uvn stays: the gate reads uv)
+    tracks.uv = np.ascontiguousarray(uv.reshape(-1))
+    for k in CAND:
+        setattr(cand, k, getattr(tracks, k))
+
+    def resident():
+        u = UpdaterMSCKF(opts, device=0)
+        u.debug_option("delayed_init_fused", level)
+        u.set_slam_state(cand)
+        u.set_active_landmarks([])
+        u.set_features(cand)
+        return u
+
+    for rep in (capi.REP_GLOBAL_3D, capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE):
+        for tag, fused in (("delayed_init", False), ("delayed_init_fused", True)):
+            up = resident()
+            res = up.delayed_init(rep, fused=fused)
+            res["landmarks"] = up.get_landmarks()["value"]
+            res["steps"] = np.array([up.debug_option("delayed_init_fused_steps"), up.debug_option("delayed_init_chain_steps")])
+            put(out, f"rep{rep}.{tag}", res)
+            up.reset_state()
+            put(out, f"rep{rep}.{tag}.after_reset", up.get_state(P=True))
+            print(f"rep {rep}", tag, "level", level, "status", res["feat_status"].tolist(), "steps", res["steps"].tolist(), flush=True)
+            up.close()
+    up = resident()
+    for f, d in enumerate(up.init_systems(capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH)):
+        put(out, f"init_systems.f{f}", {k: v for k, v in d.items() if v is not None})
+    put(out, "init_systems.state", up.get_state(P=True))
+    up.close()
+    np.savez(path, **out)
+
+
 def prepare(path):
     """The problems are generated once (CPU work: here, not on the GPU box's clock) and travel as a pickle."""
     import pickle
@@ -227,6 +273,8 @@ if __name__ == "__main__":
         prepare(sys.argv[2])
     elif sys.argv[1] == "fused":
         fused_scenarios(sys.argv[2], int(sys.argv[3]))
+    elif sys.argv[1] == "init":
+        init_scenarios(sys.argv[2], int(sys.argv[3]))
     elif sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     else:

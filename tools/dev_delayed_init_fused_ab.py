@@ -8,8 +8,15 @@ next to the chain of single launches (ovgpu_slam_delayed_init): an A/B of the tw
                     the entry, whose read-back ends it (the device triangulates).  The two entries take turns frame by frame, `rounds`
                     repetitions of `reps` frames each; a row per (case, entry) with the median of every round, the median of those and their
                     spread (max - min): the yardstick for a difference between the two.
-    trace [--F 30] [--calls 10] [--entry fused|chain]
-                    the frames alone, for a rocprofv3 --kernel-trace --stats run of its own (the kernels per candidate)"""
+    time --legs [--lib-a PATH] [--level-a 1] [--level-b 2] [--tag-a NAME] [--outlier-frac 0.2]
+                    three legs of the FUSED entry, interleaved frame by frame on the same inputs: A on the library --lib-a names (the parent
+                    commit's build, its options untouched; without --lib-a: the tree's), A' on the tree's with "delayed_init_fused" = --level-a,
+                    B on the tree's with "delayed_init_fused" = --level-b (the switch is a level: 1 the step behind k_system_t's gate, 2 behind
+                    k_init_rows with the gate in the tail).  A row per (F, leg); bits_equal_A: the leg's N, covariance ids, values, dx_seq and P
+                    are leg A's bit for bit.  --outlier-frac 1: every candidate a gross outlier (the all-rejected frame).
+    trace [--F 30] [--calls 10] [--entry fused|chain] [--lib-a PATH] [--level N]
+                    the frames alone, for a rocprofv3 --kernel-trace --stats run of its own (the kernels per candidate); --lib-a: on that
+                    library; --level: "delayed_init_fused" set to it first"""
 import argparse
 import ctypes as C
 import json
@@ -25,10 +32,10 @@ REPS6 = [0, 2, 0, 3, 1, 5]
 L_RESIDENT = 50
 
 
-def problem(synth, F, seed=3):
+def problem(synth, F, seed=3, outlier_frac=0.2):
     L = L_RESIDENT
     prob = synth.make_slam_problem(2, L=L, lm_rep=np.array((REPS6 * ((L + 5) // 6))[:L], np.int32), seed=seed)
-    tracks = synth.make_problem(2, F=F, seed=seed, outlier_frac=0.2)
+    tracks = synth.make_problem(2, F=F, seed=seed, outlier_frac=outlier_frac)
     for k in ("meas_offsets", "uv", "uvn", "clone_idx", "cam_idx", "p_FinG_true"):
         setattr(prob, k, getattr(tracks, k))
     return prob
@@ -64,6 +71,116 @@ def forms(up, capi, prob):
     return dict(chain=frame("ovgpu_slam_delayed_init", "chain"), fused=frame("ovgpu_slam_delayed_init_fused", "fused")), got, v
 
 
+def bind(capi, path):
+    """a library by path with the entries a leg calls (another build: it may not know this tree's option names)"""
+    if path is None:
+        return capi.load()
+    lib = C.CDLL(os.path.abspath(path))
+    ip, dp, ctx, st = capi.c_int32_p, capi.c_double_p, C.c_void_p, C.POINTER(capi.UpdateStats)
+    sig = {"ovgpu_create": [C.POINTER(capi.Options), C.c_int, C.POINTER(ctx)], "ovgpu_destroy": [ctx], "ovgpu_set_state": [ctx, C.POINTER(capi.StateView)],
+           "ovgpu_set_landmarks": [ctx, C.POINTER(capi.LandmarksView)], "ovgpu_set_active_landmarks": [ctx, C.c_int32, ip],
+           "ovgpu_set_features": [ctx, C.POINTER(capi.FeaturesView)], "ovgpu_set_feature_reps": [ctx, ip], "ovgpu_synchronize": [ctx],
+           "ovgpu_slam_delayed_init_fused": [ctx, C.c_int32, ip, dp, dp, ip, dp, dp, ip, ip, dp, ip, dp, st],
+           "ovgpu_debug_option": [ctx, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]}
+    for name, args in sig.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, (None if name == "ovgpu_destroy" else C.c_int)
+    lib.ovgpu_last_error.restype = C.c_char_p
+    return lib
+
+
+class Leg:
+    """one context of `lib` and its frame through the fused entry; level: "delayed_init_fused" is set to it, None leaves the library alone"""
+
+    def __init__(self, capi, lib, prob, kind, level):
+        self.capi, self.lib, self.kind, self.level, self.ctx = capi, lib, kind, level, C.c_void_p()
+        opts = capi.default_options(chi2_multipler=1.0)
+        self.ok(lib.ovgpu_create(C.byref(opts), 0, C.byref(self.ctx)), "ovgpu_create")
+        if level is not None:
+            self.ok(lib.ovgpu_debug_option(self.ctx, b"delayed_init_fused", int(level), None), "ovgpu_debug_option")
+        self.v = capi.Views(prob)
+        F, N = self.v.features.F, prob.N
+        self.reps = np.array((REPS6 * ((F + 5) // 6))[:F], np.int32)
+        Nmax = N + int(np.where(self.reps == capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE, 1, 3).sum())
+        self.st, self.cov = np.zeros(F, np.int32), np.zeros(F, np.int32)
+        self.val, self.fej, self.dx, self.P = np.zeros((F, 3)), np.zeros((F, 3)), np.zeros((F, Nmax)), np.zeros(Nmax * Nmax)
+        self.N_out, self.stats = C.c_int32(0), capi.UpdateStats()
+
+    def ok(self, rc, where):
+        if rc != 0:
+            raise RuntimeError(f"leg {self.kind}: {where} returned {rc}: {self.lib.ovgpu_last_error()}")
+
+    def frame(self):
+        lib, ctx, v = self.lib, self.ctx, self.v
+        ip = lambda a: a.ctypes.data_as(self.capi.c_int32_p)
+        dp = lambda a: a.ctypes.data_as(self.capi.c_double_p)
+        self.ok(lib.ovgpu_set_state(ctx, C.byref(v.state)), "ovgpu_set_state")
+        self.ok(lib.ovgpu_set_landmarks(ctx, C.byref(v.landmarks)), "ovgpu_set_landmarks")
+        self.ok(lib.ovgpu_set_active_landmarks(ctx, 0, None), "ovgpu_set_active_landmarks")
+        self.ok(lib.ovgpu_set_features(ctx, C.byref(v.features)), "ovgpu_set_features")
+        self.ok(lib.ovgpu_set_feature_reps(ctx, ip(self.reps)), "ovgpu_set_feature_reps")
+        self.ok(lib.ovgpu_slam_delayed_init_fused(ctx, 0, ip(self.st), None, None, ip(self.cov), dp(self.val), dp(self.fej), None, None, dp(self.dx),
+                                                  C.byref(self.N_out), dp(self.P), C.byref(self.stats)), "ovgpu_slam_delayed_init_fused")
+
+    def outputs(self):
+        n = self.N_out.value
+        return n, self.st.copy(), self.cov.copy(), self.val.copy(), self.dx.copy(), self.P[: n * n].copy()
+
+    def counter(self, name):
+        if self.level is None:
+            return -1
+        n = C.c_int64(0)
+        self.ok(self.lib.ovgpu_debug_option(self.ctx, name.encode(), -1, C.byref(n)), "ovgpu_debug_option")
+        return int(n.value)
+
+    def close(self):
+        self.lib.ovgpu_destroy(self.ctx)
+
+
+def bits_equal(a, b):
+    return a[0] == b[0] and all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a[1:], b[1:]))
+
+
+def timed_legs(a):
+    import torch  # noqa: F401  (capi.load: torch's HIP runtime first)
+    from open_vins_amd import capi, synth
+    lib, lib_a = capi.load(), bind(capi, a.lib_a)
+    rows = []
+    for F in (1, 5, 30):
+        prob = problem(synth, F, outlier_frac=a.outlier_frac)
+        legs = {"A": Leg(capi, lib_a, prob, "A", None), "A'": Leg(capi, lib, prob, "A'", a.level_a), "B": Leg(capi, lib, prob, "B", a.level_b)}
+        med = {k: [] for k in legs}
+        for rnd in range(a.rounds):
+            t = {k: [] for k in legs}
+            for i in range(a.reps + 3):
+                for k, leg in legs.items():  # interleaved frame by frame
+                    leg.ok(leg.lib.ovgpu_synchronize(leg.ctx), "ovgpu_synchronize")
+                    t0 = time.perf_counter()
+                    leg.frame()
+                    t1 = time.perf_counter()
+                    if i >= 3:
+                        t[k].append((t1 - t0) * 1e3)
+            for k in legs:
+                med[k].append(float(np.median(t[k])))
+        ref = legs["A"].outputs()
+        for k, leg in legs.items():
+            o = leg.outputs()
+            assert o[0] == ref[0] and np.array_equal(o[1], ref[1]) and np.array_equal(o[2], ref[2]), f"leg {k}: verdicts differ from leg A's"
+            row = dict(case="delayed_init_gate", leg=k, level=leg.level, F=F, L=L_RESIDENT, outlier_frac=a.outlier_frac, n_accepted=int((o[2] >= 0).sum()),
+                       n_rejected=int((o[1] == capi.FEAT_CHI2_REJECTED).sum()), N=int(prob.N), N_out=int(o[0]), clones=int(prob.C), cameras=int(prob.K),
+                       build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k], ms_median=float(np.median(med[k])),
+                       ms_spread=float(np.max(med[k]) - np.min(med[k])), bits_equal_A=bool(bits_equal(o, ref)),
+                       fused_steps=leg.counter("delayed_init_fused_steps"), rows_steps=(leg.counter("delayed_init_rows_steps") if k != "A" or a.lib_a is None else -1))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        for leg in legs.values():
+            leg.close()
+    if a.out:
+        with open(a.out, "a") as fh:
+            for r in rows:
+                fh.write(json.dumps(r) + "\n")
+
+
 def same(got):
     (n0, c0, v0), (n1, c1, v1) = got["chain"], got["fused"]
     acc = c0 >= 0
@@ -71,6 +188,8 @@ def same(got):
 
 
 def timed(a):
+    if a.legs:
+        return timed_legs(a)
     import torch  # noqa: F401  (capi.load: torch's HIP runtime first)
     from open_vins_amd import capi, synth
     from open_vins_amd.updater import UpdaterMSCKF
@@ -112,7 +231,15 @@ def trace(a):
     import torch  # noqa: F401
     from open_vins_amd import capi, synth
     from open_vins_amd.updater import UpdaterMSCKF
-    prob = problem(synth, a.F)
+    prob = problem(synth, a.F, outlier_frac=a.outlier_frac)
+    if a.lib_a is not None or a.level is not None:  # the fused entry on a library by path and / or at a level
+        leg = Leg(capi, bind(capi, a.lib_a), prob, "trace", a.level)
+        for _ in range(a.calls):
+            leg.frame()
+        o = leg.outputs()
+        leg.close()
+        print(f"{a.calls} frames of the fused entry (library {a.lib_a or 'of the tree'}, level {a.level}), {a.F} candidates ({int((o[2] >= 0).sum())} accepted), L = {L_RESIDENT}")
+        return
     up = UpdaterMSCKF(capi.default_options(chi2_multipler=1.0))
     fns, got, keep_alive = forms(up, capi, prob)
     for _ in range(a.calls):
@@ -129,10 +256,19 @@ def main():
     t.add_argument("--rounds", type=int, default=3)
     t.add_argument("--tag", default="tree")
     t.add_argument("--out", default=None)
+    t.add_argument("--legs", action="store_true")
+    t.add_argument("--lib-a", default=None)
+    t.add_argument("--tag-a", default="parent")
+    t.add_argument("--level-a", type=int, default=1)
+    t.add_argument("--level-b", type=int, default=2)
+    t.add_argument("--outlier-frac", type=float, default=0.2)
     r = sub.add_parser("trace")
     r.add_argument("--F", type=int, default=30)
     r.add_argument("--calls", type=int, default=10)
     r.add_argument("--entry", choices=("fused", "chain"), default="fused")
+    r.add_argument("--lib-a", default=None)
+    r.add_argument("--level", type=int, default=None)
+    r.add_argument("--outlier-frac", type=float, default=0.2)
     a = ap.parse_args()
     {"time": timed, "trace": trace}[a.cmd](a)
 
