@@ -340,7 +340,11 @@ int ovgpu_set_features(ovgpu_ctx *ctx, const ovgpu_features_view *fv);
  *                           Feature::anchor_cam_id / anchor_clone_timestamp
  *   status           [F]    OVGPU_FEAT_USED (= success so far),
  *                           _TOO_FEW_MEAS, _TRI_FAILED or _GN_FAILED
- * All outputs are host pointers; any may be NULL.                            */
+ * All outputs are host pointers; any may be NULL.
+ * The kernel keeps the pose of every (camera, clone) pair in LDS, 96 bytes
+ * a pair: a rig with 96 * K * C beyond the workgroup's LDS (160 KB: 1706
+ * pairs) is refused with OVGPU_ERR_CAPACITY by this and every other entry
+ * that triangulates, before anything is launched.                            */
 int ovgpu_triangulate(ovgpu_ctx *ctx, double *p_FinA, double *p_FinG,
                       int32_t *anchor_meas, int32_t *status);
 

@@ -12,6 +12,10 @@ static int enqueue_triangulate(ovgpu_ctx *c, const double *seed_pA = nullptr, co
   p.p_FinA = b.pA, p.p_FinG = b.pG, p.anchor_meas = c->anchor.p, p.status = b.status;
   p.opt = c->dopt;
   const size_t lds = (size_t)c->K * c->C * 12 * sizeof(double);
+  if (lds > (size_t)c->lds_limit) { // the kernel stages the whole pose table in LDS: refused here, before anything is launched (OVG_MAX_CLONES x OVG_MAX_CAMS would be 6 MB)
+    return set_err(OVGPU_ERR_CAPACITY, "k_triangulate: the pose table of K = " + std::to_string(c->K) + " cameras x C = " + std::to_string(c->C) + " clones (96 bytes a pair, " +
+                                           std::to_string(lds) + " bytes) exceeds the LDS limit of " + std::to_string(c->lds_limit) + " bytes");
+  }
   // Features (wavefronts) per workgroup.  The prior block's factorisation is dispatched a few microseconds BEHIND this kernel and needs whole
   // compute units (k_chol_fused: 16 wavefronts x 128 registers, 90 KB of LDS per block): with four features per workgroup every CU holds a
   // piece of this kernel and the factorisation only becomes resident when the first CUs drain, ~30 us later.  Where the batch allows it the

@@ -589,6 +589,23 @@ struct FeatMeas {
   const int32_t *cam_idx;
 };
 
+// What the three routines below decided for one feature, and by how much (oracle_triangulate_trace: the tests that pin k_triangulate at
+// every branch and loop exit show with it that a case reaches the clause it is named for, and that nothing sits within round-off of a
+// threshold).  Optional everywhere: with a null record the routines compute exactly what they compute without one.
+enum { TR_NONE = 0, TR_COND, TR_LIN_LO, TR_LIN_HI, TR_LIN_NAN, TR_GN_LO, TR_GN_HI, TR_BASELINE, TR_GN_NAN };      // the clause that rejected, in the order tested
+enum { TR_EXIT_NOT_ENTERED = 0, TR_EXIT_RUNS, TR_EXIT_LAM, TR_EXIT_DX, TR_EXIT_DCOST };                           // how the LM loop was left
+struct TriTrace {
+  double condA = NAN, lin_depth = NAN; // single_triangulation's condition number (NaN in 1-D), the linear depth p_f.z
+  double gn_depth = NAN, base_ratio = NAN, lam_final = NAN; // the refined depth, |p| / base_line_max, lam when the loop was left
+  double min_margin = INFINITY;        // the smallest decision margin of the loop: |cost - cost_old| / cost_old of every comparison, and of every
+                                       // accepted step |(cost_old - cost) / cost_old - min_dcost| / min_dcost; structural ties left out
+  double min_dx_margin = INFINITY;     // ... and |eps - min_dx| / min_dx of every step that set eps
+  int32_t reject = TR_NONE, exit = TR_EXIT_NOT_ENTERED, n_accept = 0, n_reject = 0;
+  int32_t n_structural = 0; // comparisons whose two float residual vectors were bit-identical (cost == cost_old by construction, whatever the summation order)
+  int32_t n_exact = 0;      // cost == cost_old with DIFFERENT residual vectors: a tie that summation order could break (counted in min_margin as 0)
+};
+constexpr int TR_ND = 7, TR_NI = 6; // doubles / ints per feature of oracle_triangulate_trace's flat records
+
 // anchor rule — FeatureInitializer.cpp:36-46
 int pick_anchor(const FeatMeas &fm) {
   int best_count = 0, best_last = -1;
@@ -608,7 +625,7 @@ int pick_anchor(const FeatMeas &fm) {
 }
 
 // FeatureInitializer::single_triangulation — FeatureInitializer.cpp:30-112
-bool single_triangulation(const ovgpu_options &o, const StateTables &T, const FeatMeas &fm, int anchor, V3 &p_FinA, V3 &p_FinG) {
+bool single_triangulation(const ovgpu_options &o, const StateTables &T, const FeatMeas &fm, int anchor, V3 &p_FinA, V3 &p_FinG, TriTrace *tr = nullptr) {
   M3 A = m3_zero();
   V3 b{{0, 0, 0}};
   const ClonePose &anc = T.clones_cam[(size_t)fm.cam_idx[anchor] * T.C + fm.clone_idx[anchor]];
@@ -631,6 +648,10 @@ bool single_triangulation(const ovgpu_options &o, const StateTables &T, const Fe
   }
   V3 p_f = colpiv_qr_solve3(A, b); // :92
   double condA = cond3(A);         // :95-99
+  if (tr) {
+    tr->condA = condA, tr->lin_depth = p_f[2];
+    tr->reject = std::abs(condA) > o.max_cond_number ? TR_COND : p_f[2] < o.min_dist ? TR_LIN_LO : p_f[2] > o.max_dist ? TR_LIN_HI : std::isnan(norm(p_f)) ? TR_LIN_NAN : TR_NONE;
+  }
   if (std::abs(condA) > o.max_cond_number || p_f[2] < o.min_dist || p_f[2] > o.max_dist || std::isnan(norm(p_f))) return false;
   p_FinA = p_f;
   p_FinG = add(mulT(R_GtoA, p_FinA), p_AinG);
@@ -638,7 +659,7 @@ bool single_triangulation(const ovgpu_options &o, const StateTables &T, const Fe
 }
 
 // FeatureInitializer::single_triangulation_1d — FeatureInitializer.cpp:114-195
-bool single_triangulation_1d(const ovgpu_options &o, const StateTables &T, const FeatMeas &fm, int anchor, V3 &p_FinA, V3 &p_FinG) {
+bool single_triangulation_1d(const ovgpu_options &o, const StateTables &T, const FeatMeas &fm, int anchor, V3 &p_FinA, V3 &p_FinG, TriTrace *tr = nullptr) {
   double A = 0.0, b = 0.0;
   const ClonePose &anc = T.clones_cam[(size_t)fm.cam_idx[anchor] * T.C + fm.clone_idx[anchor]];
   const M3 &R_GtoA = anc.R_GtoC;
@@ -664,6 +685,10 @@ bool single_triangulation_1d(const ovgpu_options &o, const StateTables &T, const
   }
   double depth = b / A;
   V3 p_f{{depth * bearing_inA[0], depth * bearing_inA[1], depth * bearing_inA[2]}};
+  if (tr) {
+    tr->lin_depth = p_f[2];
+    tr->reject = p_f[2] < o.min_dist ? TR_LIN_LO : p_f[2] > o.max_dist ? TR_LIN_HI : std::isnan(norm(p_f)) ? TR_LIN_NAN : TR_NONE;
+  }
   if (p_f[2] < o.min_dist || p_f[2] > o.max_dist || std::isnan(norm(p_f))) return false;
   p_FinA = p_f;
   p_FinG = add(mulT(R_GtoA, p_FinA), p_AinG);
@@ -677,8 +702,9 @@ struct RelPose {
 };
 
 // FeatureInitializer::compute_error — FeatureInitializer.cpp:377-423
-double compute_error(const std::vector<RelPose> &rel, const FeatMeas &fm, double alpha, double beta, double rho) {
+double compute_error(const std::vector<RelPose> &rel, const FeatMeas &fm, double alpha, double beta, double rho, std::vector<float> *res = nullptr) {
   double err = 0;
+  if (res) res->resize((size_t)2 * (fm.m1 - fm.m0));
   for (int i = fm.m0; i < fm.m1; i++) {
     const RelPose &rp = rel[i - fm.m0];
     const M3 &R = rp.R_AtoCi;
@@ -688,13 +714,14 @@ double compute_error(const std::vector<RelPose> &rel, const FeatMeas &fm, double
     float z0 = f32(hi1 / hi3), z1 = f32(hi2 / hi3); // Eigen::Matrix<float,2,1> z  (:414-415)
     float r0 = fm.uvn[2 * i] - z0, r1 = fm.uvn[2 * i + 1] - z1;
     float n = std::sqrt(r0 * r0 + r1 * r1); // res.norm() in float
+    if (res) (*res)[2 * (i - fm.m0)] = r0, (*res)[2 * (i - fm.m0) + 1] = r1;
     err += std::pow((double)n, 2);          // pow(float, int) promotes to double (:418)
   }
   return err;
 }
 
 // FeatureInitializer::single_gaussnewton — FeatureInitializer.cpp:197-375
-bool single_gaussnewton(const ovgpu_options &o, const StateTables &T, const FeatMeas &fm, int anchor, V3 &p_FinA, V3 &p_FinG) {
+bool single_gaussnewton(const ovgpu_options &o, const StateTables &T, const FeatMeas &fm, int anchor, V3 &p_FinA, V3 &p_FinG, TriTrace *tr = nullptr) {
   double rho = 1 / p_FinA[2];
   double alpha = p_FinA[0] / p_FinA[2];
   double beta = p_FinA[1] / p_FinA[2];
@@ -722,7 +749,8 @@ bool single_gaussnewton(const ovgpu_options &o, const StateTables &T, const Feat
     rel[i - fm.m0] = rp;
   }
 
-  double cost_old = compute_error(rel, fm, alpha, beta, rho); // :217
+  std::vector<float> res_old, res_new; // (trace only) the float residuals behind cost_old and cost
+  double cost_old = compute_error(rel, fm, alpha, beta, rho, tr ? &res_old : nullptr); // :217
 
   while (runs < o.max_runs && lam < o.max_lamda && eps > o.min_dx) { // :227
     if (recompute) {
@@ -755,12 +783,25 @@ bool single_gaussnewton(const ovgpu_options &o, const StateTables &T, const Feat
     M3 Hess_l = Hess;
     for (int r = 0; r < 3; r++) Hess_l(r, r) *= (1.0 + lam); // :289-292
     V3 dx = colpiv_qr_solve3(Hess_l, grad);                  // :294
-    double cost = compute_error(rel, fm, alpha + dx[0], beta + dx[1], rho + dx[2]);
+    double cost = compute_error(rel, fm, alpha + dx[0], beta + dx[1], rho + dx[2], tr ? &res_new : nullptr);
+    if (tr) {
+      tr->exit = TR_EXIT_RUNS; // (entered; what the loop's own test says when it ends is recorded behind it)
+      if (std::memcmp(res_old.data(), res_new.data(), sizeof(float) * res_old.size()) == 0) {
+        tr->n_structural++;
+      } else {
+        if (cost == cost_old) tr->n_exact++;
+        tr->min_margin = std::fmin(tr->min_margin, std::abs(cost - cost_old) / cost_old);
+        if (cost <= cost_old) tr->min_margin = std::fmin(tr->min_margin, std::abs((cost_old - cost) / cost_old - o.min_dcost) / o.min_dcost);
+      }
+      if (cost <= cost_old) tr->n_accept++, res_old.swap(res_new);
+      else tr->n_reject++;
+    }
     if (cost <= cost_old && (cost_old - cost) / cost_old < o.min_dcost) { // :306
       alpha += dx[0];
       beta += dx[1];
       rho += dx[2];
       eps = 0;
+      if (tr) tr->exit = TR_EXIT_DCOST;
       break;
     }
     if (cost <= cost_old) { // :316
@@ -772,11 +813,16 @@ bool single_gaussnewton(const ovgpu_options &o, const StateTables &T, const Feat
       runs++;
       lam = lam / o.lam_mult;
       eps = norm(dx);
+      if (tr) tr->min_dx_margin = std::fmin(tr->min_dx_margin, std::abs(eps - o.min_dx) / o.min_dx);
     } else {
       recompute = false;
       lam = lam * o.lam_mult;
       continue;
     }
+  }
+  if (tr) {
+    if (tr->exit == TR_EXIT_RUNS) tr->exit = !(runs < o.max_runs) ? TR_EXIT_RUNS : !(lam < o.max_lamda) ? TR_EXIT_LAM : TR_EXIT_DX; // the loop's test, in its order
+    tr->lam_final = lam;
   }
   p_FinA[0] = alpha / rho; // :332-335
   p_FinA[1] = beta / rho;
@@ -799,6 +845,10 @@ bool single_gaussnewton(const ovgpu_options &o, const StateTables &T, const Feat
     if (base_line > base_line_max) base_line_max = base_line;
   }
   double pn = norm(p_FinA);
+  if (tr) {
+    tr->gn_depth = p_FinA[2], tr->base_ratio = pn / base_line_max;
+    tr->reject = p_FinA[2] < o.min_dist ? TR_GN_LO : p_FinA[2] > o.max_dist ? TR_GN_HI : (pn / base_line_max) > o.max_baseline ? TR_BASELINE : std::isnan(pn) ? TR_GN_NAN : TR_NONE;
+  }
   if (p_FinA[2] < o.min_dist || p_FinA[2] > o.max_dist || (pn / base_line_max) > o.max_baseline || std::isnan(pn)) return false; // :367
   p_FinG = add(mulT(R_GtoA, p_FinA), p_AinG); // :373
   return true;
@@ -1292,22 +1342,38 @@ int oracle_column_map(const ovgpu_options *opts, const ovgpu_state_view *st, int
   return cm.D;
 }
 
-int oracle_triangulate(const ovgpu_options *opts, const ovgpu_state_view *st, const ovgpu_features_view *fv, double *p_FinA_out,
-                       double *p_FinG_out, int32_t *anchor_meas, int32_t *status) {
+static void put_trace(const TriTrace &t, int f, double *trace_d, int32_t *trace_i) {
+  if (trace_d) {
+    const double d[TR_ND] = {t.condA, t.lin_depth, t.gn_depth, t.base_ratio, t.lam_final, t.min_margin, t.min_dx_margin};
+    std::memcpy(trace_d + (size_t)TR_ND * f, d, sizeof(d));
+  }
+  if (trace_i) {
+    const int32_t i[TR_NI] = {t.reject, t.exit, t.n_accept, t.n_reject, t.n_structural, t.n_exact};
+    std::memcpy(trace_i + (size_t)TR_NI * f, i, sizeof(i));
+  }
+}
+
+// oracle_triangulate with one trace record per feature: trace_d [F * 7] = condA, linear depth, refined depth, |p| / base_line_max, final lam,
+// smallest decision margin, smallest |eps - min_dx| / min_dx; trace_i [F * 6] = rejecting clause (TR_*), loop exit (TR_EXIT_*), accepted steps,
+// rejected steps, structural ties, exact ties that are not structural.  Quantities a feature never computed stay NaN (margins: +inf).
+int oracle_triangulate_trace(const ovgpu_options *opts, const ovgpu_state_view *st, const ovgpu_features_view *fv, double *p_FinA_out,
+                             double *p_FinG_out, int32_t *anchor_meas, int32_t *status, double *trace_d, int32_t *trace_i) {
+  const bool want = trace_d || trace_i;
   StateTables T = build_tables(st);
   for (int f = 0; f < fv->F; f++) {
     FeatMeas fm{fv->meas_offsets[f], fv->meas_offsets[f + 1], fv->uvn, fv->uv, fv->clone_idx, fv->cam_idx};
     int stt = OVGPU_FEAT_USED;
     V3 pA{{NAN, NAN, NAN}}, pG{{NAN, NAN, NAN}};
     int anchor = -1;
+    TriTrace t, *tr = want ? &t : nullptr;
     if (fm.m1 - fm.m0 < 2) {
       stt = OVGPU_FEAT_TOO_FEW_MEAS;
     } else {
       anchor = pick_anchor(fm);
-      bool ok = opts->triangulate_1d ? single_triangulation_1d(*opts, T, fm, anchor, pA, pG) : single_triangulation(*opts, T, fm, anchor, pA, pG);
+      bool ok = opts->triangulate_1d ? single_triangulation_1d(*opts, T, fm, anchor, pA, pG, tr) : single_triangulation(*opts, T, fm, anchor, pA, pG, tr);
       if (!ok)
         stt = OVGPU_FEAT_TRI_FAILED;
-      else if (opts->refine_features && !single_gaussnewton(*opts, T, fm, anchor, pA, pG))
+      else if (opts->refine_features && !single_gaussnewton(*opts, T, fm, anchor, pA, pG, tr))
         stt = OVGPU_FEAT_GN_FAILED;
     }
     for (int i = 0; i < 3; i++) {
@@ -1316,6 +1382,50 @@ int oracle_triangulate(const ovgpu_options *opts, const ovgpu_state_view *st, co
     }
     if (anchor_meas) anchor_meas[f] = anchor;
     if (status) status[f] = stt;
+    if (want) put_trace(t, f, trace_d, trace_i);
+  }
+  return OVGPU_OK;
+}
+
+int oracle_triangulate(const ovgpu_options *opts, const ovgpu_state_view *st, const ovgpu_features_view *fv, double *p_FinA_out,
+                       double *p_FinG_out, int32_t *anchor_meas, int32_t *status) {
+  return oracle_triangulate_trace(opts, st, fv, p_FinA_out, p_FinG_out, anchor_meas, status, nullptr, nullptr);
+}
+
+// single_gaussnewton ALONE from the caller's estimates and anchors (what ovgpu_refine documents, include/ovgpu.h): fewer than two measurements
+// -> TOO_FEW_MEAS; an anchor outside the feature's measurements -> TRI_FAILED, anchor -1; a refinement that returns false -> GN_FAILED.  Every
+// feature that is not USED leaves NaN positions (the reference's Feature keeps the refined p_FinA of a failed refinement; the device does not
+// report it, and neither does this entry).
+int oracle_refine(const ovgpu_options *opts, const ovgpu_state_view *st, const ovgpu_features_view *fv, const double *p_FinA_in,
+                  const int32_t *anchor_in, double *p_FinA_out, double *p_FinG_out, int32_t *anchor_meas, int32_t *status, double *trace_d,
+                  int32_t *trace_i) {
+  const bool want = trace_d || trace_i;
+  StateTables T = build_tables(st);
+  for (int f = 0; f < fv->F; f++) {
+    FeatMeas fm{fv->meas_offsets[f], fv->meas_offsets[f + 1], fv->uvn, fv->uv, fv->clone_idx, fv->cam_idx};
+    int stt = OVGPU_FEAT_USED;
+    V3 pA{{NAN, NAN, NAN}}, pG{{NAN, NAN, NAN}};
+    int anchor = -1;
+    TriTrace t, *tr = want ? &t : nullptr;
+    if (fm.m1 - fm.m0 < 2) {
+      stt = OVGPU_FEAT_TOO_FEW_MEAS;
+    } else if (anchor_in[f] < fm.m0 || anchor_in[f] >= fm.m1) {
+      stt = OVGPU_FEAT_TRI_FAILED;
+    } else {
+      anchor = anchor_in[f];
+      pA = V3{{p_FinA_in[3 * f], p_FinA_in[3 * f + 1], p_FinA_in[3 * f + 2]}};
+      if (!single_gaussnewton(*opts, T, fm, anchor, pA, pG, tr)) {
+        stt = OVGPU_FEAT_GN_FAILED;
+        pA = pG = V3{{NAN, NAN, NAN}};
+      }
+    }
+    for (int i = 0; i < 3; i++) {
+      if (p_FinA_out) p_FinA_out[3 * f + i] = pA[i];
+      if (p_FinG_out) p_FinG_out[3 * f + i] = pG[i];
+    }
+    if (anchor_meas) anchor_meas[f] = anchor;
+    if (status) status[f] = stt;
+    if (want) put_trace(t, f, trace_d, trace_i);
   }
   return OVGPU_OK;
 }

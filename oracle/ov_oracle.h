@@ -73,6 +73,29 @@ int oracle_triangulate(const ovgpu_options *opts, const ovgpu_state_view *st,
                        const ovgpu_features_view *fv, double *p_FinA,
                        double *p_FinG, int32_t *anchor_meas, int32_t *status);
 
+/* oracle_triangulate plus one trace record per feature (any of the two may be
+ * NULL): trace_d [7*F] = condA, linear depth, refined depth,
+ * |p| / base_line_max, final lam, smallest decision margin of the LM loop,
+ * smallest |eps - min_dx| / min_dx; trace_i [6*F] = rejecting clause
+ * (0 none, 1 cond, 2 lin-lo, 3 lin-hi, 4 lin-nan, 5 gn-lo, 6 gn-hi,
+ * 7 baseline, 8 gn-nan), loop exit (0 not entered, 1 runs, 2 lam, 3 dx,
+ * 4 dcost), accepted steps, rejected steps, structural ties, other exact
+ * ties.  The four result arrays are oracle_triangulate's, bit for bit. */
+int oracle_triangulate_trace(const ovgpu_options *opts, const ovgpu_state_view *st,
+                             const ovgpu_features_view *fv, double *p_FinA,
+                             double *p_FinG, int32_t *anchor_meas, int32_t *status,
+                             double *trace_d, int32_t *trace_i);
+
+/* single_gaussnewton alone from the caller's estimates / anchors (the
+ * contract of ovgpu_refine): m < 2 -> TOO_FEW_MEAS, an anchor outside the
+ * feature's measurements -> TRI_FAILED with anchor -1; every feature that is
+ * not USED leaves NaN positions.  Trace records as above. */
+int oracle_refine(const ovgpu_options *opts, const ovgpu_state_view *st,
+                  const ovgpu_features_view *fv, const double *p_FinA_in,
+                  const int32_t *anchor_in, double *p_FinA, double *p_FinG,
+                  int32_t *anchor_meas, int32_t *status, double *trace_d,
+                  int32_t *trace_i);
+
 /* UpdaterHelper::get_feature_jacobian_full for ONE feature f with given
  * p_FinG / p_FinA (UpdaterHelper.cpp:192-424) in the canonical column order
  * (see oracle_column_map).  H_f [2m x 3], H_x [2m x D], res [2m].           */

@@ -48,6 +48,10 @@ def load():
     lib.oracle_apply_dx.argtypes = [O, SV, dp, dp, dp, dp]
     lib.oracle_triangulate.restype = C.c_int
     lib.oracle_triangulate.argtypes = [O, SV, FV, dp, dp, ip, ip]
+    lib.oracle_triangulate_trace.restype = C.c_int
+    lib.oracle_triangulate_trace.argtypes = [O, SV, FV, dp, dp, ip, ip, dp, ip]
+    lib.oracle_refine.restype = C.c_int
+    lib.oracle_refine.argtypes = [O, SV, FV, dp, ip, dp, dp, ip, ip, dp, ip]
     lib.oracle_feature_jacobian.restype = C.c_int
     lib.oracle_feature_jacobian.argtypes = [O, SV, FV, C.c_int, dp, dp, C.c_int, dp, dp, dp, C.POINTER(C.c_int)]
     lib.oracle_column_map.restype = C.c_int
@@ -89,6 +93,54 @@ def triangulate(opts, views):
     status = np.zeros(F, dtype=np.int32)
     lib.oracle_triangulate(C.byref(opts), C.byref(views.state), C.byref(views.features), _p(pA), _p(pG), _pi(anchor), _pi(status))
     return dict(p_FinA=pA, p_FinG=pG, anchor_meas=anchor, status=status)
+
+
+# the codes of oracle_triangulate_trace's records (ov_oracle.h)
+REJECT = dict(none=0, cond=1, lin_lo=2, lin_hi=3, lin_nan=4, gn_lo=5, gn_hi=6, baseline=7, gn_nan=8)
+EXIT = dict(not_entered=0, runs=1, lam=2, dx=3, dcost=4)
+_TRACE_D = ("condA", "lin_depth", "gn_depth", "base_ratio", "lam_final", "min_margin", "min_dx_margin")
+_TRACE_I = ("reject", "exit", "n_accept", "n_reject", "n_structural", "n_exact")
+
+
+def _trace_out(F):
+    return np.zeros((F, len(_TRACE_D))), np.zeros((F, len(_TRACE_I)), dtype=np.int32)
+
+
+def _trace_dict(out, td, ti):
+    for j, name in enumerate(_TRACE_D):
+        out[name] = td[:, j].copy()
+    for j, name in enumerate(_TRACE_I):
+        out[name] = ti[:, j].copy()
+    return out
+
+
+def triangulate_trace(opts, views):
+    """triangulate() plus, per feature, what the three routines decided and by how much: condA, lin_depth, gn_depth, base_ratio
+    (|p| / base_line_max), lam_final, min_margin (smallest decision margin of the LM loop, structural ties left out), min_dx_margin,
+    reject (REJECT), exit (EXIT), n_accept, n_reject, n_structural, n_exact.  Quantities a feature never computed are NaN (margins: inf)."""
+    lib = load()
+    F = views.features.F
+    out = dict(p_FinA=np.zeros((F, 3)), p_FinG=np.zeros((F, 3)), anchor_meas=np.zeros(F, dtype=np.int32), status=np.zeros(F, dtype=np.int32))
+    td, ti = _trace_out(F)
+    lib.oracle_triangulate_trace(C.byref(opts), C.byref(views.state), C.byref(views.features), _p(out["p_FinA"]), _p(out["p_FinG"]),
+                                 _pi(out["anchor_meas"]), _pi(out["status"]), _p(td), _pi(ti))
+    return _trace_dict(out, td, ti)
+
+
+def refine(opts, views, p_FinA, anchor_meas):
+    """FeatureInitializer::single_gaussnewton alone on the given estimates (anchor frame) and anchor measurements, with ovgpu_refine's
+    refusals: m < 2 -> TOO_FEW_MEAS, an anchor outside the track -> TRI_FAILED with anchor -1; whatever is not USED leaves NaN positions.
+    Returns triangulate()'s four arrays and the trace of triangulate_trace()."""
+    lib = load()
+    F = views.features.F
+    pa = np.ascontiguousarray(p_FinA, dtype=np.float64)
+    am = np.ascontiguousarray(anchor_meas, dtype=np.int32)
+    assert pa.shape == (F, 3) and am.shape == (F,)
+    out = dict(p_FinA=np.zeros((F, 3)), p_FinG=np.zeros((F, 3)), anchor_meas=np.zeros(F, dtype=np.int32), status=np.zeros(F, dtype=np.int32))
+    td, ti = _trace_out(F)
+    lib.oracle_refine(C.byref(opts), C.byref(views.state), C.byref(views.features), _p(pa), _pi(am), _p(out["p_FinA"]), _p(out["p_FinG"]),
+                      _pi(out["anchor_meas"]), _pi(out["status"]), _p(td), _pi(ti))
+    return _trace_dict(out, td, ti)
 
 
 def feature_jacobian(opts, views, f, p_FinG, p_FinA=None, anchor_meas=-1):
