@@ -212,7 +212,8 @@ typedef struct {
 /* of ovgpu_msckf_compress (mode A: the compressed system leaves the device):                                */
 typedef enum {
   OVGPU_COMPRESS_GRAM = 0,   /* default.  Mode B: Gram matrix of the prior-whitened stack on the matrix cores + */
-                             /* the update in whitened coordinates (D <= 383 columns).  Mode A: the DIAGONALLY  */
+                             /* the update in whitened coordinates (D <= 383 columns; D <= 511 on a float64     */
+                             /* context under ovgpu_debug_option "gram_wide" = 1).  Mode A: the DIAGONALLY       */
                              /* PIVOTED Cholesky factor of that Gram matrix, un-whitened — a dense rank x D     */
                              /* system with H^T H, H^T r of the stack (D <= 255; Householder beyond, for SLAM   */
                              /* stacks and when the prior block's factorisation fails)                          */
@@ -1180,6 +1181,23 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             follower's time-out select the step-wise kernels at every column count
  *   "chol_wide_factorisations" number of factorisations ENQUEUED on the two-panel path, counted on the host: one that a predicate switches off on the
  *                             device counts too (a value >= 0 sets the counter)
+ *   "gram_wide"               (default 0) a level; the read-back returns it (values above 1 are taken as 1).
+ *                             1: a float64 context (options.gram_fp32 = 0) on compress_route = OVGPU_COMPRESS_GRAM takes the whitened Gram route of
+ *                             mode B at 384 .. 511 Jacobian columns as well: ovgpu_msckf_update, ovgpu_msckf_update_lm, ovgpu_slam_update and
+ *                             ovgpu_slam_update_chunked stack Y = H L, k_gram_blk forms Y^T Y over four column windows of 128 (ten block pairs;
+ *                             "last_gram_kernel" 2), both factorisations are two-panel ones ("chol_wide"), and the fused per-feature kernels are
+ *                             taken on the terms they have below 384 columns ("last_feature_kernel", "slam_fused").  0: such updates take the
+ *                             Householder route, as without the switch.  Whatever the level: mode A (ovgpu_msckf_compress, ovgpu_slam_compress),
+ *                             a gram_fp32 context, the local-Gram, sharded and multi-GPU entries and the speculative prior keep 383 columns, the
+ *                             stack beyond 383 columns is the projected one, and more than 511 columns are refused.  The fall-backs are the
+ *                             route's own: a failed prior pivot repeats through the Householder route, options.no_single_launch_cholesky,
+ *                             "chol_wide" = 0 and the repeat after a follower's time-out factor step-wise on the Gram route.  Takes effect with
+ *                             the next ovgpu_set_state / ovgpu_set_features (ovgpu_tracks_to_features hands a batch over as well) and at no
+ *                             other call: a batch that is resident keeps the level it was handed over under
+ *   "gram_wide_updates"       (read only) number of updates that took the Gram route beyond 383 columns and stand, once per update (per chunk of
+ *                             ovgpu_slam_update_chunked): an attempt the library repeats — through the Householder route after a failed prior
+ *                             pivot, with the step-wise Cholesky after a time-out, a chunked pass that is put back — is not counted, nor is an
+ *                             update that returns an error (ovgpu_msckf_update_async alone counts when it enqueues)
  *   "tsqr_leaves" / "tsqr_rows_per_node" / "tsqr_last_leaf_kernel" / "tsqr_last_tree" / "tsqr_last_qh"  (read only) what the last Householder
  *                             compression launched, stand-alone (ovgpu_measurement_compress, ovgpu_ekf_update) or on the update route: the number
  *                             of leaves W; the rows per leaf; the leaf kernel (0 the panel-wave kernel of k_tsqr_pw.h, 1 k_qr_node of k_tsqr.h,
@@ -1235,7 +1253,7 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             landmark the batch observes is 3-dof, its longest track holds at most 62 measurements, 16 <= D, K C <= 8192,
  *                             options.no_fast_feature_kernel is 0 and the update takes the whitened (Gram) route; per-feature sigma_pix /
  *                             chi2_multipler do not disqualify.  Everything else keeps the general kernel: a batch with a single-depth landmark,
- *                             the Householder route (compress_route = OVGPU_COMPRESS_TSQR, more than 383 columns, the repeat after a failed prior
+ *                             the Householder route (compress_route = OVGPU_COMPRESS_TSQR, more than 383 columns — 511 under "gram_wide" —, the repeat after a failed prior
  *                             pivot), ovgpu_slam_compress, the delayed initialisation.
  *                             2: level 1, and a batch that observes a single-depth landmark (OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) takes
  *                             k_slam_y<true> when the remaining terms hold (longest track <= 62, 16 <= D, K C <= 8192, no_fast_feature_kernel 0, the

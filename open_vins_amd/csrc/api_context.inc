@@ -399,6 +399,10 @@ struct ovgpu_ctx {
   DevBuf<double> chol_wide_A, chol_wide_Y; // [D - 256][LA - 256] each: the compact Schur complement and its factorisation (k_chol_wide.h: the second panel beyond 256 columns)
   bool chol_wide = true;          // ovgpu_debug_option "chol_wide": 0 = the step-wise kernels beyond 256 columns (1: two panels of k_chol_fused, measured faster on every leg: DESIGN.md §7)
   int64_t chol_wide_count = 0;    // ovgpu_debug_option "chol_wide_factorisations": factorisations enqueued on the two-panel path
+  int gram_wide = 0;              // ovgpu_debug_option "gram_wide": 1 = the whitened Gram route of mode B holds 32 tile columns of [H | r] (D <= 511) instead of 24 (gram_route_tile_cap, api_pipeline.inc); default 0
+  int gram_wide_on = 0;           // ... the level in force: taken over by ovgpu_set_state and by a batch handed over (end_feature_batch: ovgpu_set_features, ovgpu_tracks_to_features), nowhere else
+  int64_t gram_wide_updates = 0;  // ovgpu_debug_option "gram_wide_updates": updates that took the Gram route at 25 .. 32 tile columns AND stand: counted where the Gram kernel is enqueued, taken off again for an attempt that is repeated or that ends in an error (update_with_fallbacks, ovgpu_slam_update_chunked)
+  int gram_wide_attempt = 0;      // ... of them, the ones of the update attempt that is running (update_with_fallbacks)
   PinBuf<double> h_tri;        // mode A: the compressed system on its way to the caller ([D x LD] + one word of flags per double behind it)
   int chol_slot = 0;
   bool no_chol_pipe = false;   // options.no_single_launch_cholesky

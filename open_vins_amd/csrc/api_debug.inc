@@ -116,6 +116,11 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "chol_wide_factorisations") { // reads the count of factorisations enqueued on the two-panel path; a value >= 0 sets it
     if (old_value) *old_value = c->chol_wide_count;
     if (value >= 0) c->chol_wide_count = value;
+  } else if (n == "gram_wide") { // a level.  1: a float64 context on OVGPU_COMPRESS_GRAM takes the whitened Gram route of mode B at 384 .. 511 Jacobian columns as well (k_gram_blk over four column windows, the fused per-feature kernels on the terms they have below 384); default 0: such updates take the Householder route; reads back the level; takes effect with the next ovgpu_set_state / ovgpu_set_features
+    if (old_value) *old_value = c->gram_wide;
+    if (value >= 0) c->gram_wide = (int)std::min<int64_t>(value, 1);
+  } else if (n == "gram_wide_updates") { // read-only: the count of updates that took the Gram route beyond 383 columns, once per update (a repeated attempt — Householder route, step-wise Cholesky — is not counted)
+    if (old_value) *old_value = c->gram_wide_updates;
   } else if (n == "tsqr_leaves") { // read-only, this and the four below: what the last Householder compression launched (enqueue_compress / enqueue_merge_tree)
     if (old_value) *old_value = c->tsqr_last_W;
   } else if (n == "tsqr_rows_per_node") {

@@ -308,12 +308,39 @@ static int enqueue_merge_tree(ovgpu_ctx *c, int G, bool leaves_live = false, hip
 // G = [H | r]^T [H | r] on the matrix cores (k_gram.h): partial Gram matrices per workgroup, ordered sum; factor = true (mode A)
 // adds its diagonally pivoted Cholesky factor
 static int enqueue_gram_factor(ovgpu_ctx *c);
+// Row shares of k_gram_blk (gridDim.x; gridDim.y is the block pair) over a stack of `nchunks` stages of 32 rows.  Up to 24 tile columns, at most six
+// pairs: one share per compute unit, as ever (the reduction sums the shares in order: another count is other bits).  At 25 .. 32 tile columns the
+// stack is read TEN times, and every workgroup leaves 64 partial tiles (128 KB) whatever it summed: a share per compute unit would be 2560 workgroups
+// and 335 MB of partials, written and read again, against a stack of a few dozen MB.  The kernel's two staged windows take 135 KB of LDS, so a
+// compute unit holds one workgroup: num_cu / 10 shares (rounded down) put all ten passes on the device in ONE round of workgroups, every compute unit
+// streaming a tenth of the rows per pass it owns, and the partials stay at 32 MB.
+static int gram_blk_row_shares(const ovgpu_ctx *c, int NT, int64_t nchunks) {
+  int shares = c->num_cu;
+  if (NT > gram::GR_NT_BLK) shares = std::max(1, c->num_cu / (gram::GR_NT_WIDE / gram::GB_T * (gram::GR_NT_WIDE / gram::GB_T + 1) / 2));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(shares, nchunks));
+}
+// What enqueue_compress_gram reserves of c->gram_part, in doubles, for NT tile columns and a stack of `nchunks` stages, whichever of its kernels runs:
+// the one-pass kernels and k_gram_wide leave a triangle of NT (NT + 1) / 2 partial tiles per share, k_gram_blk (17 .. 32 tile columns, and every count
+// of a gram_fp32 context) 64 per share and block pair.  ovgpu_slam_update_chunked sizes the buffer by this in front of its first launch.
+static size_t gram_part_doubles(const ovgpu_ctx *c, int NT, int64_t nchunks) {
+  const size_t G = (size_t)std::max<int64_t>(1, std::min<int64_t>(c->num_cu, nchunks));
+  size_t need = NT <= gram::GR_NT_BLK ? G * (size_t)(NT * (NT + 1) / 2) * 256 : 0;
+  if (NT > gram::GR_NT || c->gram_fp32) {
+    const size_t NB = (size_t)(NT + gram::GB_T - 1) / gram::GB_T, pairs = NB * (NB + 1) / 2;
+    need = std::max(need, pairs * (size_t)gram_blk_row_shares(c, NT, nchunks) * gram::GB_T * gram::GB_T * 256);
+  }
+  return need;
+}
+// The Gram route's capacity in tile columns of [H | r] for the updates of this context: 32 under ovgpu_debug_option "gram_wide" on a float64 context
+// with the whitened stack (DESIGN.md §7), 24 otherwise.  Mode A (factor_gram), the speculative prior, the local-Gram, sharded and multi entries keep
+// gram::GR_NT_BLK whatever the switch says.
+static int gram_route_tile_cap(const ovgpu_ctx *c) { return c->gram_wide_on >= 1 && c->whiten && !c->gram_fp32 ? gram::GR_NT_WIDE : gram::GR_NT_BLK; }
 static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   const int D = c->D, LD = c->LD, NT = (LD + 15) / 16, NP = NT * (NT + 1) / 2, LG = 16 * NT;
   const int64_t rows_total = batch_of(c).rows_total;
   const int64_t nchunks = (rows_total + gram::GR_ROWS - 1) / gram::GR_ROWS;
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>(c->num_cu, nchunks));
-  HIPCHK(c->gram_part.reserve((size_t)G * NP * 256));
+  if (NT <= gram::GR_NT_BLK) HIPCHK(c->gram_part.reserve((size_t)G * NP * 256)); // (beyond: k_gram_blk's own, smaller reserve below)
   HIPCHK(c->gram_G.reserve((size_t)LG * LG));
   if (c->stack_is_f32) { // the fp32 stack of options.gram_fp32: one pass per part of the macro-tile triangle (k_gram32.h)
     const int LDF = c->stack_ldf, NTM = LDF / 32, P = gram32::gram32_parts(NTM), slots = P * gram32::G32_NW * gram32::G32_MAXT;
@@ -362,11 +389,12 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   }
   if (NT > gram::GR_NT || c->gram_fp32) { // more than 255 columns (configs[4]), or its fp32 variant: 8 x 8-tile blocks of the grid, one block pair per blockIdx.y
     const int NB = (NT + gram::GB_T - 1) / gram::GB_T, pairs = NB * (NB + 1) / 2;
-    HIPCHK(c->gram_part.reserve((size_t)pairs * G * gram::GB_T * gram::GB_T * 256));
+    const int Gb = gram_blk_row_shares(c, NT, nchunks);
+    HIPCHK(c->gram_part.reserve((size_t)pairs * Gb * gram::GB_T * gram::GB_T * 256));
     g.part = c->gram_part.p;
-    if (!c->gram_fp32) hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<false>>(c), dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes(), c->stream, g, NB);
-    else hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<true>>(c), dim3(G, pairs), dim3(256), gram::gram_blk_lds_bytes() / 2, c->stream, g, NB);
-    hipLaunchKernelGGL(gram::k_gram_blk_reduce, dim3(gram::GB_T * gram::GB_T, pairs), dim3(256), 0, c->stream, NB, NT, G, c->gram_part.p, c->gram_G.p);
+    if (!c->gram_fp32) hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<false>>(c), dim3(Gb, pairs), dim3(256), gram::gram_blk_lds_bytes(), c->stream, g, NB);
+    else hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<true>>(c), dim3(Gb, pairs), dim3(256), gram::gram_blk_lds_bytes() / 2, c->stream, g, NB);
+    hipLaunchKernelGGL(gram::k_gram_blk_reduce, dim3(gram::GB_T * gram::GB_T, pairs), dim3(256), 0, c->stream, NB, NT, Gb, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
     c->last_gram_kernel = 2;
     return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: up to 383 columns, k_gram_pchol<9 .. 12>)
@@ -774,7 +802,9 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   c->timed_this_update = eu != nullptr; // fill_times: an update that recorded no events reports no stage times (not an earlier update's)
   if (eu) HIPCHK(hipEventRecord(eu->a, c->stream));
   int rc = OVGPU_OK;
-  const bool fits = (c->LD + 15) / 16 <= gram::GR_NT_BLK && b.F > 0;
+  // (the Gram matrix alone — the local-Gram and sharded entries — keeps the 24 tile columns of its callers' checks)
+  const int tile_cap = gram_only ? gram::GR_NT_BLK : gram_route_tile_cap(c);
+  const bool fits = (c->LD + 15) / 16 <= tile_cap && b.F > 0;
   tform = !gram_only && c->compress_gram == 1 && !c->force_tsqr && fits && (stages & STAGE_EKF) != 0 && (stages & STAGE_LOCAL) != 0;
   // Mode A through the Gram matrix: whitened rows -> Gram matrix -> its Cholesky factor -> un-whitened (k_unwhiten): a compressed (H, r)
   // of the reference's form at the cost of the Gram route instead of the Householder TSQR's (4.0 ms host to host at 2000 features).
@@ -822,8 +852,10 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
     if (need_prior) c->gram_is_whitened = whiten;
     if (ec) HIPCHK(hipEventRecord(ec->a, c->stream));
     if (gram_only || tform) { // Gram matrix only: summed across GPUs (sharded update) or consumed by the prior-whitened EKF update
-      if ((c->LD + 15) / 16 > gram::GR_NT_BLK) return set_err(OVGPU_ERR_CAPACITY, "the Gram route holds at most 383 Jacobian columns");
+      if ((c->LD + 15) / 16 > tile_cap)
+        return set_err(OVGPU_ERR_CAPACITY, tile_cap == gram::GR_NT_WIDE ? "the Gram route holds at most 511 Jacobian columns" : "the Gram route holds at most 383 Jacobian columns");
       rc = enqueue_compress_gram(c, false);
+      if (rc == OVGPU_OK && tform && (c->LD + 15) / 16 > gram::GR_NT_BLK) c->gram_wide_updates++, c->gram_wide_attempt++;
     } else if (factor_gram) {
       rc = enqueue_compress_gram(c, true); // R = pivoted chol(Gram of the whitened stack) with [R^-T g] as last column -> c->Rws
       if (rc == OVGPU_OK) {
@@ -1115,7 +1147,7 @@ template <class Attempt> static int update_with_fallbacks(ovgpu_ctx *c, ovgpu_up
   int rc;
   for (;;) {
     c->chol_timed_out = false;
-    c->slam_fused_attempt = 0;
+    c->slam_fused_attempt = 0, c->gram_wide_attempt = 0;
     rc = attempt();
     if (rc == OVGPU_ERR_NOT_SPD && c->last_update_tform && !c->chol_timed_out && !tried_householder) {
       tried_householder = true, c->force_tsqr = true;
@@ -1125,8 +1157,11 @@ template <class Attempt> static int update_with_fallbacks(ovgpu_ctx *c, ovgpu_up
       break;
     }
     c->slam_fused_batches -= c->slam_fused_attempt; // the attempt does not stand: "slam_fused_batches" counts the pipelines of the attempt that is the update
+    c->gram_wide_updates -= c->gram_wide_attempt;   // ... and "gram_wide_updates" the update itself
     if (stats) std::memset(stats, 0, sizeof(*stats));
   }
+  if (rc != OVGPU_OK) c->gram_wide_updates -= c->gram_wide_attempt; // an update that ends in an error does not stand either
+  c->gram_wide_attempt = 0;
   c->no_chol_pipe = user_no_pipe;
   return rc;
 }

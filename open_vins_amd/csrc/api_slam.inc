@@ -355,7 +355,13 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     HIPCHK(c->gram_rho.reserve(std::max((size_t)N, Dm)));
     HIPCHK(c->Hbig.reserve((size_t)std::max<int64_t>(pl.rows_max, 1) * LDm));
     HIPCHK(c->gram_G.reserve(256 * NTm * NTm));
-    HIPCHK(c->gram_part.reserve((size_t)c->num_cu * (NTm * (NTm + 1) / 2) * 256));
+    { // every chunk's Gram stage, whatever its column count (a chunk is narrower than the widest by its landmarks' columns only, but a narrower
+      // count can take a kernel that leaves MORE partial tiles): the largest of what enqueue_compress_gram reserves for 1 .. NTm tile columns
+      const int64_t chunks_max = (pl.rows_max + gram::GR_ROWS - 1) / gram::GR_ROWS;
+      size_t need = 0;
+      for (int nt = 1; nt <= (int)NTm; nt++) need = std::max(need, gram_part_doubles(c, nt, chunks_max));
+      HIPCHK(c->gram_part.reserve(need));
+    }
     HIPCHK(c->pFej.reserve(3 * Fm));
     HIPCHK(c->feat_lm.reserve(Fm));
     HIPCHK(c->feat_lmcol.reserve(Fm));
@@ -387,7 +393,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
   if (rc != OVGPU_OK) return rc;
   // ---- every chunk, one after the other on the stream
   const NoStageTiming untimed(c); // (no stage events inside the pass: six marker packets per chunk; ovgpu_update_stats::ms_* stay 0)
-  const int64_t fused0 = c->slam_fused_batches;
+  const int64_t fused0 = c->slam_fused_batches, wide0 = c->gram_wide_updates;
   for (int k = 0; k < n && rc == OVGPU_OK; k++) rc = enqueue_chunk(c, pl, k);
   // ---- one read-back
   std::vector<int32_t> flags((size_t)5 * n, 0);
@@ -420,6 +426,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     return rcl;
   };
   if (rc != OVGPU_OK) {
+    c->gram_wide_updates = wide0; // (the pass does not stand)
     (void)leave();
     (void)upload_sync(c, s);
     return rc;
@@ -438,7 +445,7 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *c, int32_t n_chunks, const int32_t *chu
     // behind it ran on a state the chain would not have produced: the entry state comes back and the chunks run as the chain of single calls
     // runs them, one synchronisation and update_with_fallbacks each.  Correct, slower and rare; counted.
     c->chunk_fallbacks++;
-    c->slam_fused_batches = fused0; // (the pass does not stand: the chain below counts its own pipelines)
+    c->slam_fused_batches = fused0, c->gram_wide_updates = wide0; // (the pass does not stand: the chain below counts its own pipelines)
     if ((rc = state_snapshot(c, c->chk_save.p, true, true)) != OVGPU_OK) return rc;
     if ((rc = launch_build_tables(c)) != OVGPU_OK) return rc;
     HIPCHK(hipMemsetAsync(c->chk_flags.p, 0, sizeof(int32_t) * 5 * n, s));

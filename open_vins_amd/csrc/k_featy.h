@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) k_feat_vt(SysParams p, FeatStore st, doub
 //   pos[i]         where measurement i's Jacobian record goes inside its feature: clone-major order (clone column, then camera, then index),
 //                  what k_feat_y's sweep relies on.  The packed keys of the feature sit in LDS, every thread ranks its own;
 //   inst           the distinct column blocks ("instances": first column, width) of every tile row of 16 rows = 8 measurements, ascending — what
-//                  the sweep of k_feat_y loops over.  il[0] = count, il[1] = last non-zero column of the tile row, il[2 .. 5] = per column block
+//                  the sweep of k_feat_y loops over.  il[0] = count, il[1] = last non-zero column of the tile row, il[2 .. 7] = per column block
 //                  of `cb` columns the first instance that reaches the block and the first that reaches past its first half (three blocks of 10
 //                  bits per int), il[FY_IOFF ..] = (type << 24) | (width << 16) | first column (type 0 clone block, 1 camera extrinsics, 2
 //                  camera intrinsics).  One THREAD per candidate (tile row, measurement, kind): 24 per tile row, five tile rows per pass.  A
@@ -424,7 +424,8 @@ __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_m
       }
       if (keep) gl[FY_IOFF + below] = code; // ascending first column: a column block's dead instances (left of it) are a prefix of the list
       if (jk == 0) gl[0] = cnt, gl[1] = lim;
-      if (jk >= 1 && jk <= 4) { // per column block of cb columns: e0 = the first instance that reaches the block, e1 = the first that reaches past its first half
+      if (jk >= 1 && jk <= 6) { // per column block of cb columns: e0 = the first instance that reaches the block, e1 = the first that reaches past its first half
+                                // (gl[2 .. 7], three blocks a word: 18 blocks, the 16 of 511 columns at cb = 32 among them; FY_IOFF = 8 is the next word)
         int packed = 0;
 #pragma unroll
         for (int q = 0; q < 3; q++) {

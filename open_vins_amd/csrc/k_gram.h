@@ -44,6 +44,7 @@ constexpr int GR_ROWS = 32;  // rows of the stack per LDS stage
 constexpr int GR_LS = 272;   // LDS row stride in doubles (17 * 16 >= 256 columns; consecutive rows start half an LDS line apart)
 constexpr int GR_NT = 16;    // tile-grid capacity of k_gram: LD <= 256
 constexpr int GR_NT_BLK = 24; // of the block variant k_gram_blk (three column windows of 8 tiles): LD <= 384
+constexpr int GR_NT_WIDE = 32; // ... with a fourth window (NB = 4, ten block pairs): LD <= 512, the update's whitened route under ovgpu_debug_option "gram_wide"
 
 struct GramParams {
   int LD, NT;             // row length of the stack (D + 1) and its 16-column tiles
@@ -748,6 +749,9 @@ template <int WS> __global__ void __launch_bounds__(256) k_gram_wide_win(GramPar
 // 64 tiles of the block as 16 per wavefront (tile rows 2 w, 2 w + 1 of window a against all 8 tile columns of window b: ten
 // operand reads for sixteen matrix instructions).  Diagonal blocks compute both triangles; the reduction writes what lies on
 // or above the diagonal and mirrors it.  A fall-back shape: it reads the stack NB (NB + 1) / 2 times.
+// NB is a runtime argument: two or three windows up to 24 tile columns, FOUR (ten block pairs) for the 25 .. 32 tile columns of the update's
+// whitened route under ovgpu_debug_option "gram_wide" (GR_NT_WIDE; the host then deals fewer row shares: gram_blk_row_shares, api_pipeline.inc).
+// Columns of a window beyond LD are staged as zeros (`live`), tiles beyond the grid are computed and skipped by the reduction.
 // ---------------------------------------------------------------------------------------------------
 constexpr int GB_T = 8;            // tiles per window
 constexpr int GB_W = 16 * GB_T;    // columns per window

@@ -25,6 +25,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 TRAJ_FIXTURE = os.path.join(_HERE, "..", "tests", "golden", "sim_traj_window.txt")
+TRAJ_LONG_FIXTURE = os.path.join(_HERE, "..", "tests", "golden", "sim_traj_corridor_90s.txt")
 
 # config/rpng_sim/kalibr_imucam_chain.yaml:3-54 — T_imu_cam = [R_CtoI p_CinI], intrinsics, radtan distortion
 _T_IMU_CAM = [
@@ -252,8 +253,16 @@ class Problem:
         return q
 
 
-def load_traj_window():
-    return np.loadtxt(TRAJ_FIXTURE, comments="#")
+def load_traj_window(rows=64):
+    """The clone window: `rows` IMU poses at 10 Hz starting 5 s into the corridor trajectory.  Up to 64 the fixture every snapshot has been
+    built from; a longer window (up to 256 poses: states of more than 64 clones) is cut from the 95 s excerpt of the same trajectory by the
+    rule tools/make_traj_fixture.py cut the fixture by."""
+    if rows <= 64:
+        return np.loadtxt(TRAJ_FIXTURE, comments="#")
+    assert rows <= 256
+    traj = np.loadtxt(TRAJ_LONG_FIXTURE, comments="#")
+    i0 = int(np.argmin(np.abs(traj[:, 0] - (traj[0, 0] + 5.0))))
+    return traj[i0:i0 + 2 * rows:2]  # 20 Hz file -> 10 Hz clones
 
 
 def state_sigmas(C, K, imu_intrinsics=False):
@@ -292,7 +301,7 @@ def make_problem(cfg=2, rep=0, *, C=None, K=None, F=None, track="full", fisheye=
     rng_P = np.random.default_rng([seed, 2])      # prior covariance stream
     rng_f = np.random.default_rng([seed, 3, shard])  # feature stream
 
-    traj = load_traj_window()
+    traj = load_traj_window(C)
     assert C <= traj.shape[0]
     q_true = traj[:C, 4:8].copy()
     for i in range(C):

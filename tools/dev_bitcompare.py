@@ -6,7 +6,10 @@ nothing but instruction ORDER (a scheduler strategy, ovgpu_featy_tu.hip): no tol
 (tools/gpu_bitcompare.sh swaps the library files on one box).  `dump` also runs the entries that read the resident feature batch on
 small seeded landmark states (batch_scenarios below): used when a change is meant to touch host code only.  `fused <out.npz> <level>` runs
 SLAM updates with ovgpu_debug_option "slam_fused" at that level (fused_scenarios below): two builds must agree bit for bit at a level both know.
-`init <out.npz> <level>` runs the delayed-initialisation scenarios with "delayed_init_fused" at that level (init_scenarios below), likewise."""
+`init <out.npz> <level>` runs the delayed-initialisation scenarios with "delayed_init_fused" at that level (init_scenarios below), likewise.
+`wide <out.npz> [level]` runs updates of 384 .. 511 Jacobian columns (wide_scenarios below), with "gram_wide" at that level when one is given: without
+one the name is left alone, and a build that knows the switch must agree bit for bit with one that does not.
+`--lib PATH` behind any of the above runs it on that build of the library instead of the tree's."""
 import sys
 
 import numpy as np
@@ -208,6 +211,66 @@ def init_scenarios(path, level):
     np.savez(path, **out)
 
 
+def wide_scenarios(path, level=None):
+    """Every update entry at 384 .. 511 columns: ovgpu_msckf_update (448 columns, 70 clones stereo, 60 features; then mode A on the same upload),
+    ovgpu_slam_update over all columns (476: 30 clones stereo, 100 landmarks of the six representations, a batch of 25), ovgpu_slam_update_chunked
+    (64 clones stereo, twelve landmarks in three chunks: 422 / 422 / 424 columns) and ovgpu_msckf_update_lm (412 columns under eight resident
+    landmarks).  Without the switch every one of them takes the Householder route."""
+    import copy
+    from open_vins_amd import capi, synth
+    from open_vins_amd.updater import UpdaterMSCKF
+    opts = capi.default_options(chi2_multipler=1.0)
+    out = {}
+
+    def ctx():
+        u = UpdaterMSCKF(opts, device=0)
+        if level is not None:
+            u.debug_option("gram_wide", level)
+        return u
+
+    def tail(u, res):
+        res["route"], res["kernel"], res["gram"] = u.lib.ovgpu_last_update_route(u._ctx), u.debug_option("last_feature_kernel"), u.debug_option("last_gram_kernel")
+        return res
+
+    p = synth.make_problem(2, C=70, K=2, F=60, seed=5)
+    up = ctx()
+    up.set_problem(p)
+    put(out, "msckf448", tail(up, up.update()))
+    up.reset_state()
+    put(out, "msckf448.modeA", up.compress())
+    up.close()
+    full = synth.make_slam_problem(2, L=100, lm_rep=np.array((REPS6 * 17)[:100], np.int32), seed=3)
+    q = full.subset(np.arange(25))
+    q.lm_index = np.arange(25, dtype=np.int32)
+    up = ctx()
+    up.set_slam_problem(q)
+    res = up.slam_update(q.lm_index)
+    res.update(up.get_state(P=False))
+    put(out, "slam476", tail(up, res))
+    up.close()
+    q = synth.make_slam_problem(2, L=12, lm_rep=np.array(REPS6 * 2, np.int32), seed=41, C=64, K=2)
+    up = ctx()
+    up.set_slam_problem(q)
+    res = up.slam_update_chunked(q.lm_index, [0, 4, 8, 12])
+    res.update(up.get_state(P=False))
+    put(out, "chunked", tail(up, res))
+    up.close()
+    lm = copy.copy(synth.make_slam_problem(2, L=8, lm_rep=np.array(REPS6 + (0, 5), np.int32), seed=3, C=64, K=2))
+    tracks = synth.make_problem(2, F=40, seed=3, C=64, K=2)
+    for k in CAND:
+        setattr(lm, k, getattr(tracks, k))
+    up = ctx()
+    up.set_slam_state(lm)
+    up.set_active_landmarks([])
+    up.set_features(lm)
+    put(out, "msckf_update_lm", tail(up, up.update_lm()))
+    up.close()
+    for k in sorted(out):
+        if k.endswith(".route") or k.endswith(".kernel") or k.endswith(".gram"):
+            print(k, out[k].tolist(), flush=True)
+    np.savez(path, **out)
+
+
 def prepare(path):
     """The problems are generated once (CPU work: here, not on the GPU box's clock) and travel as a pickle."""
     import pickle
@@ -269,12 +332,20 @@ def compare(a, b):
 
 
 if __name__ == "__main__":
+    if "--lib" in sys.argv:  # another build of the library (the parent commit's): every scenario above loads it through capi.load()
+        import os
+        from open_vins_amd import capi
+        at = sys.argv.index("--lib")
+        capi.LIB_PATH = os.path.abspath(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
     if sys.argv[1] == "prepare":
         prepare(sys.argv[2])
     elif sys.argv[1] == "fused":
         fused_scenarios(sys.argv[2], int(sys.argv[3]))
     elif sys.argv[1] == "init":
         init_scenarios(sys.argv[2], int(sys.argv[3]))
+    elif sys.argv[1] == "wide":
+        wide_scenarios(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else None)
     elif sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     else:
