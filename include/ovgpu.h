@@ -462,8 +462,8 @@ int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, do
  *                                  matrix, un-whitened: DENSE, rows = its numerical rank (the stack of an MSCKF
  *                                  update has a null space: gauge directions) — 1.2 ms host to host at 2000 features
  *   OVGPU_COMPRESS_TSQR            the reference's form, the upper-triangular Householder factor, rows = D
- *                                  (4.0 ms); also taken beyond 383 columns (255 before ABI 5) and when the
- *                                  prior block's factorisation fails.  ovgpu_last_update_route tells which one came back.
+ *                                  (4.0 ms); also taken beyond 383 columns (255 before ABI 5; beyond 511 under
+ *                                  ovgpu_debug_option "mode_a_wide" = 1) and when the prior block's factorisation fails.  ovgpu_last_update_route tells which one came back.
  * Which kernels the default form runs, by the column count D (LD = D + 1 with the residual column, NT = ceil(LD / 16)
  * tile columns; ovgpu_debug_option "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel" report them):
  *   Gram matrix   D <= 255 (NT <= 16): the one-pass kernel with ceil(NT / 2) * 2 tile columns (15 at NT = 15);
@@ -473,7 +473,13 @@ int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, do
  *                 D, NB = 1 .. 12)
  *   un-whitening  D <= 256 and the prior block factored in one launch: k_unwhiten_blk<16>; D <= 256 otherwise
  *                 (options.no_single_launch_cholesky, "unwhiten_blocked" = 0): k_unwhiten<16>; D = 257 .. 383: k_unwhiten<24>
- *   D >= 384      none of them: the Householder triangle, rows = D, OVGPU_COMPRESS_TSQR
+ *   D >= 384      none of them: the Householder triangle, rows = D, OVGPU_COMPRESS_TSQR — unless ovgpu_debug_option "mode_a_wide" = 1
+ *                 is in force on a float64 context (options.gram_fp32 = 0) with the whitened stack: then, for D = 384 .. 511 (NT = 25 .. 32),
+ *                 Gram matrix k_gram_blk over four column windows; factor k_pchol_panel (32 pivots per launch) around k_pchol_schur
+ *                 ("last_factor_kernel" 3); un-whitening k_unwhiten_blk<32> on the inverse diagonal tiles of the prior block's two-panel
+ *                 factorisation ("last_unwhiten_kernel" 4), or on k_uinv_tiles' when that factorisation ran step-wise
+ *                 (options.no_single_launch_cholesky, "chol_wide" = 0) or "unwhiten_blocked" is 0 (5); rows = the numerical rank,
+ *                 OVGPU_COMPRESS_PCHOLQR.  ovgpu_slam_compress keeps the Householder triangle at every width.
  * A batch whose every feature is rejected returns rows = 0 and OVGPU_OK. */
 int ovgpu_msckf_compress(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2,
                          double *chi2_thresh, double *p_FinG, int32_t *D_out,
@@ -1187,8 +1193,8 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             ovgpu_slam_update_chunked stack Y = H L, k_gram_blk forms Y^T Y over four column windows of 128 (ten block pairs;
  *                             "last_gram_kernel" 2), both factorisations are two-panel ones ("chol_wide"), and the fused per-feature kernels are
  *                             taken on the terms they have below 384 columns ("last_feature_kernel", "slam_fused").  0: such updates take the
- *                             Householder route, as without the switch.  Whatever the level: mode A (ovgpu_msckf_compress, ovgpu_slam_compress),
- *                             a gram_fp32 context, the local-Gram, sharded and multi-GPU entries and the speculative prior keep 383 columns, the
+ *                             Householder route, as without the switch.  Whatever the level: mode A (ovgpu_msckf_compress, ovgpu_slam_compress;
+ *                             ovgpu_msckf_compress has a switch of its own, "mode_a_wide"), a gram_fp32 context, the local-Gram, sharded and multi-GPU entries and the speculative prior keep 383 columns, the
  *                             stack beyond 383 columns is the projected one, and more than 511 columns are refused.  The fall-backs are the
  *                             route's own: a failed prior pivot repeats through the Householder route, options.no_single_launch_cholesky,
  *                             "chol_wide" = 0 and the repeat after a follower's time-out factor step-wise on the Gram route.  Takes effect with
@@ -1198,6 +1204,17 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             ovgpu_slam_update_chunked): an attempt the library repeats — through the Householder route after a failed prior
  *                             pivot, with the step-wise Cholesky after a time-out, a chunked pass that is put back — is not counted, nor is an
  *                             update that returns an error (ovgpu_msckf_update_async alone counts when it enqueues)
+ *   "mode_a_wide"             (default 0) a level; the read-back returns it (values above 1 are taken as 1).  Independent of "gram_wide".
+ *                             1: ovgpu_msckf_compress on a float64 context (options.gram_fp32 = 0) whose compress_route is not OVGPU_COMPRESS_TSQR
+ *                             takes the pivoted Gram route at 384 .. 511 Jacobian columns as well (the rule at ovgpu_msckf_compress):
+ *                             ovgpu_last_update_route reports OVGPU_COMPRESS_PCHOLQR and rows = the numerical rank.  0: such compressions return
+ *                             the Householder triangle, as without the switch.  Whatever the level: ovgpu_slam_compress, compress_route =
+ *                             OVGPU_COMPRESS_TSQR, a gram_fp32 context and an un-whitened stack keep the Householder triangle, every update entry
+ *                             keeps its route, and more than 511 columns are refused.  A prior block that does not factor (or a follower's
+ *                             time-out) repeats the call through the Householder route.  Takes effect where "gram_wide" does: with the next
+ *                             ovgpu_set_state / ovgpu_set_features, and at no other call
+ *   "mode_a_wide_compressions" (read only) number of compressions that took the pivoted route beyond 383 columns and stand: an attempt the
+ *                             library repeats through the Householder route is not counted
  *   "tsqr_leaves" / "tsqr_rows_per_node" / "tsqr_last_leaf_kernel" / "tsqr_last_tree" / "tsqr_last_qh"  (read only) what the last Householder
  *                             compression launched, stand-alone (ovgpu_measurement_compress, ovgpu_ekf_update) or on the update route: the number
  *                             of leaves W; the rows per leaf; the leaf kernel (0 the panel-wave kernel of k_tsqr_pw.h, 1 k_qr_node of k_tsqr.h,
@@ -1245,8 +1262,9 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             per Jacobian record (48; 72 once an anchored representation is in force); the launch's dynamic LDS size in bytes
  *   "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel"  (read only) what the last batch pipeline launched: the Gram kernel (0 none,
  *                             1 the one-pass kernel, 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32); mode A's pivoted factor (0 none: the
- *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB the rank-one k_gram_pchol<NB>);
- *                             mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>): the rule at ovgpu_msckf_compress
+ *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 3 k_pchol_panel + k_pchol_schur, 32 + NB the rank-one
+ *                             k_gram_pchol<NB>); mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>, 4 k_unwhiten_blk<32> on
+ *                             the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles'): the rule at ovgpu_msckf_compress
  *   "slam_fused"              (default 0) a level; the read-back returns it (values above 3 are taken as 3).
  *                             1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
  *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every

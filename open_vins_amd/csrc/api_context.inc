@@ -403,6 +403,11 @@ struct ovgpu_ctx {
   int gram_wide_on = 0;           // ... the level in force: taken over by ovgpu_set_state and by a batch handed over (end_feature_batch: ovgpu_set_features, ovgpu_tracks_to_features), nowhere else
   int64_t gram_wide_updates = 0;  // ovgpu_debug_option "gram_wide_updates": updates that took the Gram route at 25 .. 32 tile columns AND stand: counted where the Gram kernel is enqueued, taken off again for an attempt that is repeated or that ends in an error (update_with_fallbacks, ovgpu_slam_update_chunked)
   int gram_wide_attempt = 0;      // ... of them, the ones of the update attempt that is running (update_with_fallbacks)
+  int mode_a_wide = 0;            // ovgpu_debug_option "mode_a_wide": 1 = mode A's pivoted Gram route (ovgpu_msckf_compress) holds 32 tile columns of [H | r] (D <= 511) instead of 24 (mode_a_tile_cap, api_pipeline.inc); default 0; independent of "gram_wide"
+  int mode_a_wide_on = 0;         // ... the level in force: taken over exactly where gram_wide_on is
+  int64_t mode_a_wide_compressions = 0; // ovgpu_debug_option "mode_a_wide_compressions": compressions that took the pivoted route at 25 .. 32 tile columns AND stand (compress_impl takes an attempt it repeats through the Householder route off again)
+  DevBuf<double> pchol_dots;      // [512 + 8] k_pchol_wide.h: the running diagonal and the first pivot between the panels' launches
+  DevBuf<double> uinv_tiles;      // [32][256] k_uinv_tiles: U_JJ^-1 of a prior block that was factored step-wise, for k_unwhiten_blk<32>
   PinBuf<double> h_tri;        // mode A: the compressed system on its way to the caller ([D x LD] + one word of flags per double behind it)
   int chol_slot = 0;
   bool no_chol_pipe = false;   // options.no_single_launch_cholesky
@@ -432,8 +437,8 @@ struct ovgpu_ctx {
   bool last_factor_from_gram = false;
   // read-only ovgpu_debug_option "last_gram_kernel" / "last_factor_kernel" / "last_unwhiten_kernel": what the last batch pipeline launched
   //   gram:     0 none, 1 k_gram_il / k_gram<NT> (launch_gram), 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32
-  //   factor:   0 none (the Householder triangle), 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 32 + NB k_gram_pchol<NB>
-  //   unwhiten: 0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>
+  //   factor:   0 none (the Householder triangle), 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 3 k_pchol_panel + k_pchol_schur (k_pchol_wide.h), 32 + NB k_gram_pchol<NB>
+  //   unwhiten: 0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>, 4 k_unwhiten_blk<32> on the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles'
   int last_gram_kernel = 0, last_factor_kernel = 0, last_unwhiten_kernel = 0;
   bool chol_timed_out = false;    // finish_update: a follower of the single-launch Cholesky gave up waiting; nothing was modified
   bool prior_pending = false; // the sharded update's local stage has started the prior block's factorisation on stream2

@@ -121,6 +121,11 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (value >= 0) c->gram_wide = (int)std::min<int64_t>(value, 1);
   } else if (n == "gram_wide_updates") { // read-only: the count of updates that took the Gram route beyond 383 columns, once per update (a repeated attempt — Householder route, step-wise Cholesky — is not counted)
     if (old_value) *old_value = c->gram_wide_updates;
+  } else if (n == "mode_a_wide") { // a level.  1: ovgpu_msckf_compress on a float64 context with the whitened stack takes the pivoted Gram route at 384 .. 511 Jacobian columns as well (k_gram_blk over four column windows, k_pchol_wide.h, k_unwhiten_blk<32>); default 0: such compressions take the Householder route; independent of "gram_wide"; reads back the level; takes effect with the next ovgpu_set_state / ovgpu_set_features
+    if (old_value) *old_value = c->mode_a_wide;
+    if (value >= 0) c->mode_a_wide = (int)std::min<int64_t>(value, 1);
+  } else if (n == "mode_a_wide_compressions") { // read-only: the count of compressions that took the pivoted route beyond 383 columns and stand (an attempt repeated through the Householder route is not counted)
+    if (old_value) *old_value = c->mode_a_wide_compressions;
   } else if (n == "tsqr_leaves") { // read-only, this and the four below: what the last Householder compression launched (enqueue_compress / enqueue_merge_tree)
     if (old_value) *old_value = c->tsqr_last_W;
   } else if (n == "tsqr_rows_per_node") {

@@ -332,9 +332,12 @@ static size_t gram_part_doubles(const ovgpu_ctx *c, int NT, int64_t nchunks) {
   return need;
 }
 // The Gram route's capacity in tile columns of [H | r] for the updates of this context: 32 under ovgpu_debug_option "gram_wide" on a float64 context
-// with the whitened stack (DESIGN.md §7), 24 otherwise.  Mode A (factor_gram), the speculative prior, the local-Gram, sharded and multi entries keep
-// gram::GR_NT_BLK whatever the switch says.
+// with the whitened stack (DESIGN.md §7), 24 otherwise.  The speculative prior, the local-Gram, sharded and multi entries keep gram::GR_NT_BLK
+// whatever the switch says; mode A (factor_gram) has a switch of its own (mode_a_tile_cap).
 static int gram_route_tile_cap(const ovgpu_ctx *c) { return c->gram_wide_on >= 1 && c->whiten && !c->gram_fp32 ? gram::GR_NT_WIDE : gram::GR_NT_BLK; }
+// ... and for mode A's pivoted factor (factor_gram, enqueue_pipeline_body): 32 under ovgpu_debug_option "mode_a_wide" on a float64 context with the
+// whitened stack (k_pchol_wide.h, k_unwhiten_blk<32>), 24 otherwise.  The two switches are independent of each other.
+static int mode_a_tile_cap(const ovgpu_ctx *c) { return c->mode_a_wide_on >= 1 && c->whiten && !c->gram_fp32 ? gram::GR_NT_WIDE : gram::GR_NT_BLK; }
 static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   const int D = c->D, LD = c->LD, NT = (LD + 15) / 16, NP = NT * (NT + 1) / 2, LG = 16 * NT;
   const int64_t rows_total = batch_of(c).rows_total;
@@ -385,7 +388,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     hipLaunchKernelGGL(gram::k_gram_reduce, dim3(NP), dim3(1024), 0, c->stream, NT, Gw, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
     c->last_gram_kernel = 3;
-    return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: up to 383 columns, k_gram_pchol<9 .. 12>)
+    return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: k_gram_pchol<9 .. 12> up to 383 columns, k_pchol_wide.h beyond)
   }
   if (NT > gram::GR_NT || c->gram_fp32) { // more than 255 columns (configs[4]), or its fp32 variant: 8 x 8-tile blocks of the grid, one block pair per blockIdx.y
     const int NB = (NT + gram::GB_T - 1) / gram::GB_T, pairs = NB * (NB + 1) / 2;
@@ -397,7 +400,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     hipLaunchKernelGGL(gram::k_gram_blk_reduce, dim3(gram::GB_T * gram::GB_T, pairs), dim3(256), 0, c->stream, NB, NT, Gb, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
     c->last_gram_kernel = 2;
-    return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: up to 383 columns, k_gram_pchol<9 .. 12>)
+    return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: k_gram_pchol<9 .. 12> up to 383 columns, k_pchol_wide.h beyond)
   }
   switch ((NT + 1) / 2) {
   case 1: launch_gram<2>(c, G, g, c->stream, c->gram_il); break;
@@ -421,12 +424,28 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
 // diagonally pivoted Cholesky of c->gram_G into c->Rws (k_gram_pchol): the stable factor of a semi-definite matrix (mode A)
 static int enqueue_gram_factor(ovgpu_ctx *c) {
   const int D = c->D, LD = c->LD, LG = 16 * ((LD + 15) / 16);
-  HIPCHK(c->gram_dropped.reserve(1));
+  HIPCHK(c->gram_dropped.reserve(2)); // [0] the dropped rows, [1] k_pchol_wide.h's stop word
   const double tol = 1e-15;
   // round 6: blocked — the upper block triangle as 16 x 16 tiles in the registers of 7 wavefronts, one matrix instruction per tile and four
   // pivots, the pivot-by-pivot work in one wavefront (k_pchol.h); up to 14 tile columns (223 Jacobian columns: configs[0..2]).  Beyond — 17 tiles
   // per wavefront in nine wavefronts' 168 registers — the kernel spills, and the rank-one kernel stays.
   const int NTf = (LD + 15) / 16;
+  if (NTf > gram::GR_NT_BLK) { // 25 .. 32 tile columns ("mode_a_wide"): panels of 32 pivots around Schur steps, in place on c->gram_G (k_pchol_wide.h)
+    if (NTf > gram::GR_NT_WIDE) return set_err(OVGPU_ERR_CAPACITY, "the pivoted Gram factor holds at most 511 Jacobian columns");
+    HIPCHK(c->pchol_dots.reserve((size_t)gram::PW_LGMAX + 8));
+    gram::PcholWideParams q;
+    q.D = D, q.LD = LD, q.LG = LG, q.G = c->gram_G.p, q.out = c->Rws.p, q.dots = c->pchol_dots.p, q.ctl = c->gram_dropped.p, q.tol = tol;
+    // every launch of the largest panel count up front: the panel that stops tells the later ones through ctl[PW_DONE]
+    const int panels = gram::pchol_wide_panels(D), tiles = (LG / 16) * (LG / 16);
+    for (int pn = 0; pn < panels; pn++) {
+      q.k0 = pn * gram::PW_NB;
+      hipLaunchKernelGGL(with_max_lds<gram::k_pchol_panel>(c), dim3(1), dim3(gram::PW_LGMAX), gram::pchol_wide_lds_bytes(), c->stream, q);
+      if (pn + 1 < panels) hipLaunchKernelGGL(gram::k_pchol_schur, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, q);
+    }
+    HIPCHK(hipGetLastError());
+    c->last_factor_kernel = 3;
+    return OVGPU_OK;
+  }
   if (c->pchol_blocked && NTf <= 14) {
     if (NTf <= 8) launch_gram_pchol_blk<4, 9, 2>(c->stream, D, LD, LG, c->gram_G.p, c->Rws.p, c->gram_dropped.p, tol);
     else launch_gram_pchol_blk<7, 15, 4>(c->stream, D, LD, LG, c->gram_G.p, c->Rws.p, c->gram_dropped.p, tol);
@@ -605,7 +624,10 @@ static int enqueue_chol_wide(ovgpu_ctx *c, const EkfParams &p, hipStream_t s, do
   const int64_t elems = (int64_t)D2 * LA2 + (Lt ? (int64_t)p.D * p.D : 0);
   hipLaunchKernelGGL(chol::k_chol_place, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, w);
   HIPCHK(hipGetLastError());
-  c->last_uinv = nullptr; // (the inverse tiles are two panels' own: k_unwhiten_blk is a kernel for up to 256 columns)
+  // The inverse tiles are two panels' own: panel 1 left tiles 0 .. 15 in slot 0, panel 2 the tiles of U22 in slot 1, which follows slot 0 in memory —
+  // CW_D1 is exactly sixteen tiles, so c->chol_uinv is uinv[32][256] in tile order, what k_unwhiten_blk<32> reads (mode A beyond 383 columns).  Only
+  // the prior block's factorisation (the one that wants L) says so: the second factorisation of mode B overwrites both slots, and nothing reads its tiles.
+  c->last_uinv = Lt ? c->chol_uinv.p : nullptr;
   c->chol_wide_count++;
   return OVGPU_OK;
 }
@@ -812,9 +834,9 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   //   diagonally pivoted (k_gram_pchol, the DEFAULT and OVGPU_COMPRESS_PCHOLQR): backward stable whatever the rank — a 52-frame loop of
   //     mode A stays at 1e-13 of the oracle-driven one (the UNPIVOTED factor, rounds 3-5's OVGPU_COMPRESS_CHOLQR, drifted 6e-6 and left the tree), snapshots at dx 1e-12 / P 1e-12 (tests/test_closed_loop.py::test_mode_a_closed_loop,
   //     tests/test_gpu_parity.py::test_mode_a_pivoted_factor_shapes).
-  // compress_route = OVGPU_COMPRESS_TSQR keeps the Householder triangle; so do SLAM stacks, more than 383 columns, the fp32 Gram
-  // variant, an un-whitened stack and a prior block whose own factorisation fails (compress_impl repeats the call then).
-  const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && b.F > 0 && (c->LD + 15) / 16 <= gram::GR_NT_BLK &&
+  // compress_route = OVGPU_COMPRESS_TSQR keeps the Householder triangle; so do SLAM stacks, more than 383 columns (511 under "mode_a_wide":
+  // mode_a_tile_cap), the fp32 Gram variant, an un-whitened stack and a prior block whose own factorisation fails (compress_impl repeats the call then).
+  const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && b.F > 0 && (c->LD + 15) / 16 <= mode_a_tile_cap(c) &&
                            (stages & STAGE_EKF) == 0 && (stages & STAGE_LOCAL) != 0 && c->whiten && !c->gram_fp32 && !slam; // (the SLAM stack is short: its mode A stays Householder)
   c->factor_from_gram = false, c->last_factor_from_gram = factor_gram;
   c->last_gram_kernel = c->last_factor_kernel = c->last_unwhiten_kernel = 0;
@@ -862,7 +884,18 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
         if (c->prior_on_side) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
         c->prior_pending = false, c->prior_on_side = false;
         // (nothing happens when the prior block's factorisation failed: flags[0]; the call is repeated through the Householder route then)
-        if ((c->D + 15) / 16 <= 16 && c->unwhiten_blocked && c->prior_uinv)
+        const int NTd = (c->D + 15) / 16;
+        if (NTd > gram::GR_NT_BLK || (c->LD + 15) / 16 > gram::GR_NT_BLK) { // "mode_a_wide": 384 .. 511 columns, eight accumulator slots per wavefront
+          const double *tiles = c->unwhiten_blocked ? c->prior_uinv : nullptr;
+          if (!tiles) { // the prior was factored step-wise: the diagonal tiles' inverses out of U1 itself
+            HIPCHK(c->uinv_tiles.reserve((size_t)gram::GR_NT_WIDE * 256));
+            hipLaunchKernelGGL(gram::k_uinv_tiles, dim3(NTd), dim3(64), 0, c->stream, c->D, (const double *)c->Yaug.p, c->D + c->N + 1, c->uinv_tiles.p, (const int32_t *)c->flags.p);
+            tiles = c->uinv_tiles.p;
+          }
+          hipLaunchKernelGGL(k_unwhiten_blk<32>, dim3(NTd), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1, tiles,
+                             (const int32_t *)nullptr, (const int32_t *)c->flags.p);
+          c->mode_a_wide_compressions++;
+        } else if ((c->D + 15) / 16 <= 16 && c->unwhiten_blocked && c->prior_uinv)
           hipLaunchKernelGGL(k_unwhiten_blk<16>, dim3((c->D + 15) / 16), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
                              c->prior_uinv, (const int32_t *)nullptr, (const int32_t *)c->flags.p);
         else if ((c->D + 15) / 16 <= 16)
@@ -872,7 +905,8 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
           hipLaunchKernelGGL(k_unwhiten<24>, dim3((c->D + 15) / 16), dim3(64), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
                              (const int32_t *)nullptr, (const int32_t *)c->flags.p);
         HIPCHK(hipGetLastError());
-        c->last_unwhiten_kernel = (c->D + 15) / 16 > 16 ? 3 : (c->unwhiten_blocked && c->prior_uinv ? 1 : 2);
+        if ((c->LD + 15) / 16 > gram::GR_NT_BLK) c->last_unwhiten_kernel = c->unwhiten_blocked && c->prior_uinv ? 4 : 5;
+        else c->last_unwhiten_kernel = (c->D + 15) / 16 > 16 ? 3 : (c->unwhiten_blocked && c->prior_uinv ? 1 : 2);
       }
     } else {
       rc = enqueue_compress(c);
@@ -1220,6 +1254,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
   int rc;
   const double *tri = nullptr;
   int32_t dropped = 0;
+  const int64_t wide0 = c->mode_a_wide_compressions;
   for (int attempt = 0;; attempt++) {
     c->factor_from_gram = attempt == 0; // the whitened Gram matrix's factor (pivoted by default) where it applies; Householder TSQR otherwise
     if ((rc = enqueue_pipeline(c, STAGE_LOCAL, slam)) != OVGPU_OK) return rc;
@@ -1242,6 +1277,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
     // the prior block is not (numerically) positive definite, or its single-launch factorisation was not co-scheduled: the whitened
     // route has nothing to offer; repeat through the Householder TSQR on the raw rows (which needs no factor of the prior)
     c->force_tsqr = true;
+    c->mode_a_wide_compressions = wide0; // (the attempt does not stand)
     if (attempt > 0) return set_err(OVGPU_ERR_NOT_SPD, "prior block of the involved variables not positive definite");
   }
   const int D = c->D, LD = c->LD;

@@ -30,6 +30,7 @@
 #include "k_slam_y.h"
 #include "k_gram.h"
 #include "k_pchol.h"
+#include "k_pchol_wide.h"
 #include "k_unwhiten.h"
 #include "k_gram32.h"
 #include <unordered_map>
