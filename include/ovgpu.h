@@ -92,6 +92,9 @@ extern "C" {
 /*      Likewise the debug option "slam_fused" (ovgpu_slam_update's per-feature  */
 /*      stage as one fused kernel on the matrix cores; off by default: every     */
 /*      entry enqueues what it enqueued and returns its bits).  No new symbol.   */
+/*      Likewise the debug option "slam_mode_a" (ovgpu_slam_compress on the      */
+/*      pivoted Gram route; off by default: every entry enqueues what it         */
+/*      enqueued and returns its bits).  No new symbol.                          */
 /* ------------------------------------------------------------------------- */
 #define OVGPU_ABI_VERSION 10
 int ovgpu_abi_version(void);
@@ -479,7 +482,12 @@ int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, do
  *                 ("last_factor_kernel" 3); un-whitening k_unwhiten_blk<32> on the inverse diagonal tiles of the prior block's two-panel
  *                 factorisation ("last_unwhiten_kernel" 4), or on k_uinv_tiles' when that factorisation ran step-wise
  *                 (options.no_single_launch_cholesky, "chol_wide" = 0) or "unwhiten_blocked" is 0 (5); rows = the numerical rank,
- *                 OVGPU_COMPRESS_PCHOLQR.  ovgpu_slam_compress keeps the Householder triangle at every width.
+ *                 OVGPU_COMPRESS_PCHOLQR.  ovgpu_slam_compress keeps the Householder triangle at every width, unless ovgpu_debug_option
+ *                 "slam_mode_a" is in force: then the table above is its own (D counts the active landmarks' columns), with one difference:
+ *   un-whitening  (ovgpu_slam_compress under "slam_mode_a") D = 257 .. 383: k_unwhiten_blk<24>, the blocked form with six accumulator tiles per
+ *                 wavefront, on the inverse diagonal tiles of the prior block's two-panel factorisation ("last_unwhiten_kernel" 6), or on
+ *                 k_uinv_tiles' when that factorisation ran step-wise (options.no_single_launch_cholesky, "chol_wide" = 0) or
+ *                 "unwhiten_blocked" is 0 (7).  ovgpu_msckf_compress keeps k_unwhiten<24> (3) there.
  * A batch whose every feature is rejected returns rows = 0 and OVGPU_OK. */
 int ovgpu_msckf_compress(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2,
                          double *chi2_thresh, double *p_FinG, int32_t *D_out,
@@ -638,7 +646,18 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *ctx, int32_t n_chunks, const int32_t *c
 /* Mode A of the SLAM update (strict drop-in): everything of ovgpu_slam_update up to the
  * compressed stack, returned for the stock StateHelper::EKFUpdate exactly as
  * ovgpu_msckf_compress does.  The landmark columns appear in col_cov_id with the landmarks'
- * covariance ids.  H, r, col_cov_id must hold 6*C + 14*K + 3*L columns / rows.                */
+ * covariance ids.  H, r, col_cov_id must hold 6*C + 14*K + 3*L columns / rows.
+ * By default the Householder triangle at every width: rows = D (0 when nothing was used),
+ * OVGPU_COMPRESS_TSQR.  With ovgpu_debug_option "slam_mode_a" = 1, set after ovgpu_create, the
+ * entry takes the pivoted Gram route on the terms ovgpu_msckf_compress does (the rule there): a
+ * float64 context on OVGPU_COMPRESS_GRAM with the whitened stack, D <= 383 (D <= 511 when
+ * "mode_a_wide" = 1 is in force as well) and a prior block that factors.  rows = the numerical
+ * rank, at most the rows of the stack plus noise rows; ovgpu_last_update_route reports
+ * OVGPU_COMPRESS_PCHOLQR.  The per-feature stage is then the one ovgpu_slam_update runs:
+ * k_slam_y for a batch laid out under "slam_fused" ("last_feature_kernel" 4 / 5 / 6 / 7), the
+ * general kernel writing whitened rows otherwise.  Rows are scaled to the context's sigma_pix
+ * whatever ovgpu_set_feature_options gave (R = sigma_pix^2 I holds on both routes).  The resident
+ * state is untouched.  A batch whose every feature is rejected returns rows = 0 and OVGPU_OK.     */
 int ovgpu_slam_compress(ovgpu_ctx *ctx, const int32_t *lm_index, int32_t *feat_status,
                         double *chi2, double *chi2_thresh, int32_t *D_out, int32_t *rows_out,
                         int32_t *col_cov_id, double *H, double *r, ovgpu_update_stats *stats);
@@ -1208,13 +1227,28 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             1: ovgpu_msckf_compress on a float64 context (options.gram_fp32 = 0) whose compress_route is not OVGPU_COMPRESS_TSQR
  *                             takes the pivoted Gram route at 384 .. 511 Jacobian columns as well (the rule at ovgpu_msckf_compress):
  *                             ovgpu_last_update_route reports OVGPU_COMPRESS_PCHOLQR and rows = the numerical rank.  0: such compressions return
- *                             the Householder triangle, as without the switch.  Whatever the level: ovgpu_slam_compress, compress_route =
+ *                             the Householder triangle, as without the switch.  Whatever the level: ovgpu_slam_compress (it has a switch of
+ *                             its own, "slam_mode_a"; with both in force it takes the route at 384 .. 511 columns too), compress_route =
  *                             OVGPU_COMPRESS_TSQR, a gram_fp32 context and an un-whitened stack keep the Householder triangle, every update entry
  *                             keeps its route, and more than 511 columns are refused.  A prior block that does not factor (or a follower's
  *                             time-out) repeats the call through the Householder route.  Takes effect where "gram_wide" does: with the next
  *                             ovgpu_set_state / ovgpu_set_features, and at no other call
  *   "mode_a_wide_compressions" (read only) number of compressions that took the pivoted route beyond 383 columns and stand: an attempt the
  *                             library repeats through the Householder route is not counted
+ *   "slam_mode_a"             (default 0) a level; the read-back returns it (values above 1 are taken as 1).
+ *                             1: ovgpu_slam_compress on a float64 context (options.gram_fp32 = 0) whose compress_route is not OVGPU_COMPRESS_TSQR
+ *                             takes the pivoted Gram route up to 383 Jacobian columns (511 when "mode_a_wide" = 1 is in force as well), by the
+ *                             rule at ovgpu_msckf_compress: ovgpu_last_update_route reports OVGPU_COMPRESS_PCHOLQR and rows = the numerical rank.
+ *                             Its per-feature stage is ovgpu_slam_update's ("slam_fused", "last_feature_kernel"), its un-whitening at D = 257 ..
+ *                             383 k_unwhiten_blk<24> ("last_unwhiten_kernel" 6 / 7).  0: the Householder triangle, as without the switch.
+ *                             Whatever the level: compress_route = OVGPU_COMPRESS_TSQR, a gram_fp32 context and an un-whitened stack keep the
+ *                             Householder triangle, so do more than 383 columns without "mode_a_wide"; every other entry keeps its route and its
+ *                             bits; more than 511 columns are refused.  A prior block that does not factor (or a follower's time-out) repeats
+ *                             the call through the Householder route with the bits of a context that never named the switch.  Takes effect
+ *                             where "mode_a_wide" does: with the next ovgpu_set_state / ovgpu_set_features, and at no other call: a batch that
+ *                             is resident keeps the level it was handed over under
+ *   "slam_mode_a_compressions" (read only) number of SLAM compressions that took the pivoted route and stand: an attempt the library repeats
+ *                             through the Householder route is not counted
  *   "tsqr_leaves" / "tsqr_rows_per_node" / "tsqr_last_leaf_kernel" / "tsqr_last_tree" / "tsqr_last_qh"  (read only) what the last Householder
  *                             compression launched, stand-alone (ovgpu_measurement_compress, ovgpu_ekf_update) or on the update route: the number
  *                             of leaves W; the rows per leaf; the leaf kernel (0 the panel-wave kernel of k_tsqr_pw.h, 1 k_qr_node of k_tsqr.h,
@@ -1264,7 +1298,9 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             1 the one-pass kernel, 2 k_gram_blk, 3 k_gram_wide, 4 k_gram_regions, 5 k_gram_f32); mode A's pivoted factor (0 none: the
  *                             Householder triangle, 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 3 k_pchol_panel + k_pchol_schur, 32 + NB the rank-one
  *                             k_gram_pchol<NB>); mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>, 4 k_unwhiten_blk<32> on
- *                             the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles'): the rule at ovgpu_msckf_compress
+ *                             the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles', 6 k_unwhiten_blk<24> on the
+ *                             two-panel factorisation's inverse tiles, 7 k_unwhiten_blk<24> on k_uinv_tiles' — ovgpu_slam_compress under
+ *                             "slam_mode_a"): the rule at ovgpu_msckf_compress
  *   "slam_fused"              (default 0) a level; the read-back returns it (values above 3 are taken as 3).
  *                             1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
  *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every
@@ -1272,7 +1308,8 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             options.no_fast_feature_kernel is 0 and the update takes the whitened (Gram) route; per-feature sigma_pix /
  *                             chi2_multipler do not disqualify.  Everything else keeps the general kernel: a batch with a single-depth landmark,
  *                             the Householder route (compress_route = OVGPU_COMPRESS_TSQR, more than 383 columns — 511 under "gram_wide" —, the repeat after a failed prior
- *                             pivot), ovgpu_slam_compress, the delayed initialisation.
+ *                             pivot), ovgpu_slam_compress (unless "slam_mode_a" puts it on the whitened route: then the terms above hold for it
+ *                             as well, at every level), the delayed initialisation.
  *                             2: level 1, and a batch that observes a single-depth landmark (OVGPU_REP_ANCHORED_INVERSE_DEPTH_SINGLE) takes
  *                             k_slam_y<true> when the remaining terms hold (longest track <= 62, 16 <= D, K C <= 8192, no_fast_feature_kernel 0, the
  *                             whitened route): per feature of such a landmark the two reflectors of its bearing columns are applied to the rows

@@ -406,6 +406,9 @@ struct ovgpu_ctx {
   int mode_a_wide = 0;            // ovgpu_debug_option "mode_a_wide": 1 = mode A's pivoted Gram route (ovgpu_msckf_compress) holds 32 tile columns of [H | r] (D <= 511) instead of 24 (mode_a_tile_cap, api_pipeline.inc); default 0; independent of "gram_wide"
   int mode_a_wide_on = 0;         // ... the level in force: taken over exactly where gram_wide_on is
   int64_t mode_a_wide_compressions = 0; // ovgpu_debug_option "mode_a_wide_compressions": compressions that took the pivoted route at 25 .. 32 tile columns AND stand (compress_impl takes an attempt it repeats through the Householder route off again)
+  int slam_mode_a = 0;            // ovgpu_debug_option "slam_mode_a", a level: 0 off; 1 (and above) ovgpu_slam_compress takes mode A's pivoted Gram route on the terms ovgpu_msckf_compress does (factor_gram, enqueue_pipeline_body), the per-feature stage the kernel "slam_fused" lays the batch out for, and at 17 .. 24 tile columns of D the blocked un-whitening k_unwhiten_blk<24>
+  int slam_mode_a_on = 0;         // ... the level in force: taken over exactly where mode_a_wide_on is
+  int64_t slam_mode_a_compressions = 0; // ovgpu_debug_option "slam_mode_a_compressions": SLAM compressions that took the pivoted route AND stand (compress_impl takes an attempt it repeats through the Householder route off again)
   DevBuf<double> pchol_dots;      // [512 + 8] k_pchol_wide.h: the running diagonal and the first pivot between the panels' launches
   DevBuf<double> uinv_tiles;      // [32][256] k_uinv_tiles: U_JJ^-1 of a prior block that was factored step-wise, for k_unwhiten_blk<32>
   PinBuf<double> h_tri;        // mode A: the compressed system on its way to the caller ([D x LD] + one word of flags per double behind it)

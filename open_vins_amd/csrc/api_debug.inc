@@ -126,6 +126,11 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (value >= 0) c->mode_a_wide = (int)std::min<int64_t>(value, 1);
   } else if (n == "mode_a_wide_compressions") { // read-only: the count of compressions that took the pivoted route beyond 383 columns and stand (an attempt repeated through the Householder route is not counted)
     if (old_value) *old_value = c->mode_a_wide_compressions;
+  } else if (n == "slam_mode_a") { // a level.  1 (and above): ovgpu_slam_compress takes the pivoted Gram route on the terms ovgpu_msckf_compress does (a float64 context on OVGPU_COMPRESS_GRAM, the whitened stack, D <= 383, or 511 with "mode_a_wide" = 1 as well), its per-feature stage the kernel "slam_fused" lays the batch out for, its un-whitening at D = 257 .. 383 k_unwhiten_blk<24>; default 0: the Householder triangle; reads back the level; takes effect with the next ovgpu_set_state / ovgpu_set_features
+    if (old_value) *old_value = c->slam_mode_a;
+    if (value >= 0) c->slam_mode_a = (int)std::min<int64_t>(value, 1);
+  } else if (n == "slam_mode_a_compressions") { // read-only: the count of SLAM compressions that took the pivoted route and stand (an attempt repeated through the Householder route is not counted)
+    if (old_value) *old_value = c->slam_mode_a_compressions;
   } else if (n == "tsqr_leaves") { // read-only, this and the four below: what the last Householder compression launched (enqueue_compress / enqueue_merge_tree)
     if (old_value) *old_value = c->tsqr_last_W;
   } else if (n == "tsqr_rows_per_node") {

@@ -834,10 +834,11 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   //   diagonally pivoted (k_gram_pchol, the DEFAULT and OVGPU_COMPRESS_PCHOLQR): backward stable whatever the rank — a 52-frame loop of
   //     mode A stays at 1e-13 of the oracle-driven one (the UNPIVOTED factor, rounds 3-5's OVGPU_COMPRESS_CHOLQR, drifted 6e-6 and left the tree), snapshots at dx 1e-12 / P 1e-12 (tests/test_closed_loop.py::test_mode_a_closed_loop,
   //     tests/test_gpu_parity.py::test_mode_a_pivoted_factor_shapes).
-  // compress_route = OVGPU_COMPRESS_TSQR keeps the Householder triangle; so do SLAM stacks, more than 383 columns (511 under "mode_a_wide":
-  // mode_a_tile_cap), the fp32 Gram variant, an un-whitened stack and a prior block whose own factorisation fails (compress_impl repeats the call then).
+  // compress_route = OVGPU_COMPRESS_TSQR keeps the Householder triangle; so do SLAM stacks (unless ovgpu_debug_option "slam_mode_a" is in force: then
+  // ovgpu_slam_compress comes here on the MSCKF entry's terms), more than 383 columns (511 under "mode_a_wide": mode_a_tile_cap), the fp32 Gram
+  // variant, an un-whitened stack and a prior block whose own factorisation fails (compress_impl repeats the call then).
   const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && b.F > 0 && (c->LD + 15) / 16 <= mode_a_tile_cap(c) &&
-                           (stages & STAGE_EKF) == 0 && (stages & STAGE_LOCAL) != 0 && c->whiten && !c->gram_fp32 && !slam; // (the SLAM stack is short: its mode A stays Householder)
+                           (stages & STAGE_EKF) == 0 && (stages & STAGE_LOCAL) != 0 && c->whiten && !c->gram_fp32 && (!slam || c->slam_mode_a_on >= 1); // (SLAM stacks: Householder by default, "slam_mode_a")
   c->factor_from_gram = false, c->last_factor_from_gram = factor_gram;
   c->last_gram_kernel = c->last_factor_kernel = c->last_unwhiten_kernel = 0;
   c->force_tsqr = false;
@@ -885,28 +886,39 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
         c->prior_pending = false, c->prior_on_side = false;
         // (nothing happens when the prior block's factorisation failed: flags[0]; the call is repeated through the Householder route then)
         const int NTd = (c->D + 15) / 16;
-        if (NTd > gram::GR_NT_BLK || (c->LD + 15) / 16 > gram::GR_NT_BLK) { // "mode_a_wide": 384 .. 511 columns, eight accumulator slots per wavefront
+        const bool wide = NTd > gram::GR_NT_BLK || (c->LD + 15) / 16 > gram::GR_NT_BLK; // "mode_a_wide": 384 .. 511 columns, eight accumulator slots per wavefront
+        // "slam_mode_a": the SLAM entry at 17 .. 24 tile columns of D (257 .. 383 columns, where a state with landmarks sits) takes the blocked form
+        // as well, six accumulator slots per wavefront; ovgpu_msckf_compress keeps k_unwhiten<24> there
+        const bool mid = !wide && NTd > 16 && slam && c->slam_mode_a_on >= 1;
+        bool own_tiles = false;
+        if (wide || mid) {
           const double *tiles = c->unwhiten_blocked ? c->prior_uinv : nullptr;
           if (!tiles) { // the prior was factored step-wise: the diagonal tiles' inverses out of U1 itself
             HIPCHK(c->uinv_tiles.reserve((size_t)gram::GR_NT_WIDE * 256));
             hipLaunchKernelGGL(gram::k_uinv_tiles, dim3(NTd), dim3(64), 0, c->stream, c->D, (const double *)c->Yaug.p, c->D + c->N + 1, c->uinv_tiles.p, (const int32_t *)c->flags.p);
-            tiles = c->uinv_tiles.p;
+            tiles = c->uinv_tiles.p, own_tiles = true;
           }
-          hipLaunchKernelGGL(k_unwhiten_blk<32>, dim3(NTd), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1, tiles,
-                             (const int32_t *)nullptr, (const int32_t *)c->flags.p);
-          c->mode_a_wide_compressions++;
-        } else if ((c->D + 15) / 16 <= 16 && c->unwhiten_blocked && c->prior_uinv)
-          hipLaunchKernelGGL(k_unwhiten_blk<16>, dim3((c->D + 15) / 16), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
+          if (wide)
+            hipLaunchKernelGGL(k_unwhiten_blk<32>, dim3(NTd), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1, tiles,
+                               (const int32_t *)nullptr, (const int32_t *)c->flags.p);
+          else
+            hipLaunchKernelGGL(k_unwhiten_blk<24>, dim3(NTd), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1, tiles,
+                               (const int32_t *)nullptr, (const int32_t *)c->flags.p);
+          if (wide) c->mode_a_wide_compressions++;
+        } else if (NTd <= 16 && c->unwhiten_blocked && c->prior_uinv)
+          hipLaunchKernelGGL(k_unwhiten_blk<16>, dim3(NTd), dim3(256), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
                              c->prior_uinv, (const int32_t *)nullptr, (const int32_t *)c->flags.p);
-        else if ((c->D + 15) / 16 <= 16)
-          hipLaunchKernelGGL(k_unwhiten<16>, dim3((c->D + 15) / 16), dim3(64), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
+        else if (NTd <= 16)
+          hipLaunchKernelGGL(k_unwhiten<16>, dim3(NTd), dim3(64), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
                              (const int32_t *)nullptr, (const int32_t *)c->flags.p);
         else
-          hipLaunchKernelGGL(k_unwhiten<24>, dim3((c->D + 15) / 16), dim3(64), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
+          hipLaunchKernelGGL(k_unwhiten<24>, dim3(NTd), dim3(64), 0, c->stream, c->D, c->LD, c->Rws.p, (const double *)c->Yaug.p, c->D + c->N + 1,
                              (const int32_t *)nullptr, (const int32_t *)c->flags.p);
         HIPCHK(hipGetLastError());
-        if ((c->LD + 15) / 16 > gram::GR_NT_BLK) c->last_unwhiten_kernel = c->unwhiten_blocked && c->prior_uinv ? 4 : 5;
-        else c->last_unwhiten_kernel = (c->D + 15) / 16 > 16 ? 3 : (c->unwhiten_blocked && c->prior_uinv ? 1 : 2);
+        if (wide) c->last_unwhiten_kernel = own_tiles ? 5 : 4;
+        else if (mid) c->last_unwhiten_kernel = own_tiles ? 7 : 6;
+        else c->last_unwhiten_kernel = NTd > 16 ? 3 : (c->unwhiten_blocked && c->prior_uinv ? 1 : 2);
+        if (slam) c->slam_mode_a_compressions++;
       }
     } else {
       rc = enqueue_compress(c);
@@ -1254,7 +1266,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
   int rc;
   const double *tri = nullptr;
   int32_t dropped = 0;
-  const int64_t wide0 = c->mode_a_wide_compressions;
+  const int64_t wide0 = c->mode_a_wide_compressions, slam0 = c->slam_mode_a_compressions, fused0 = c->slam_fused_batches;
   for (int attempt = 0;; attempt++) {
     c->factor_from_gram = attempt == 0; // the whitened Gram matrix's factor (pivoted by default) where it applies; Householder TSQR otherwise
     if ((rc = enqueue_pipeline(c, STAGE_LOCAL, slam)) != OVGPU_OK) return rc;
@@ -1277,7 +1289,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
     // the prior block is not (numerically) positive definite, or its single-launch factorisation was not co-scheduled: the whitened
     // route has nothing to offer; repeat through the Householder TSQR on the raw rows (which needs no factor of the prior)
     c->force_tsqr = true;
-    c->mode_a_wide_compressions = wide0; // (the attempt does not stand)
+    c->mode_a_wide_compressions = wide0, c->slam_mode_a_compressions = slam0, c->slam_fused_batches = fused0; // (the attempt does not stand)
     if (attempt > 0) return set_err(OVGPU_ERR_NOT_SPD, "prior block of the involved variables not positive definite");
   }
   const int D = c->D, LD = c->LD;

@@ -18,7 +18,7 @@
 
 namespace ovg {
 
-template <int NTM> // tile columns at most (D <= 16 NTM): 16, or 32 — eight accumulator slots per wavefront, one wavefront per SIMD — for mode A beyond 383 columns
+template <int NTM> // tile columns at most (D <= 16 NTM): 16; 32 — eight accumulator slots per wavefront, one wavefront per SIMD — for mode A beyond 383 columns; 24 — six slots — for ovgpu_slam_compress at 257 .. 383 columns ("slam_mode_a")
 __global__ void __launch_bounds__(256) k_unwhiten_blk(int D, int LD, double *__restrict__ R, const double *__restrict__ Y1, int LA, const double *__restrict__ uinv,
                                                        const int32_t *pred, const int32_t *pred_not) {
   typedef double d4 __attribute__((ext_vector_type(4)));
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(256) k_unwhiten_blk(int D, int LD, double *__r
       step((JJ), (NTM - 1 - (JJ)) & 1, std::integral_constant<int, ((JJ) >> 2)>{});            \
     }                                                                                          \
   }
-  // (tile columns 16 .. 31: discarded statements of the <16> instantiation, whose code they do not change)
+  // (tile columns 16 .. 31: discarded statements of the <16> instantiation, whose code they do not change; 24 .. 31 likewise of <24>)
   OVG_UW_STEP(31) OVG_UW_STEP(30) OVG_UW_STEP(29) OVG_UW_STEP(28) OVG_UW_STEP(27) OVG_UW_STEP(26) OVG_UW_STEP(25) OVG_UW_STEP(24)
   OVG_UW_STEP(23) OVG_UW_STEP(22) OVG_UW_STEP(21) OVG_UW_STEP(20) OVG_UW_STEP(19) OVG_UW_STEP(18) OVG_UW_STEP(17) OVG_UW_STEP(16)
   OVG_UW_STEP(15) OVG_UW_STEP(14) OVG_UW_STEP(13) OVG_UW_STEP(12) OVG_UW_STEP(11) OVG_UW_STEP(10) OVG_UW_STEP(9) OVG_UW_STEP(8)
