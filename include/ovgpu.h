@@ -921,7 +921,10 @@ int ovgpu_state_augment_clone(ovgpu_ctx *ctx, int32_t src_cov_id, const double *
  * Phi P(old, old) Phi^T + Q for the contiguous block [new_cov_id, new_cov_id + n_new).
  *   old_cov_ids [n_old]  covariance index of every COLUMN of Phi (the flattened order_OLD)
  *   Phi [n_new * n_old] row-major, Q [n_new * n_new] (its upper triangle is used, :87)
- * OVGPU_ERR_NEGATIVE_DIAGONAL mirrors the reference's exit on a negative diagonal (:101-113). */
+ * OVGPU_ERR_NEGATIVE_DIAGONAL mirrors the reference's exit on a negative diagonal (:101-113): the
+ * WHOLE diagonal of the covariance is scanned, not only the propagated block's — a negative
+ * entry that ovgpu_set_state accepted outside the block is reported here.  The covariance has
+ * been written by then, as in the reference.                                                  */
 int ovgpu_state_propagate(ovgpu_ctx *ctx, int32_t new_cov_id, int32_t n_new, int32_t n_old,
                           const int32_t *old_cov_ids, const double *Phi, const double *Q);
 

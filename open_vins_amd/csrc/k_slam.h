@@ -290,7 +290,7 @@ __global__ void k_cov_dt(int N, int nid, int dt, const double *__restrict__ dnc,
 // StateHelper::EKFPropagation (StateHelper.cpp:36-114)
 //   pass 0: W[i][a]   = sum_k P[i][old_k] Phi[a][k]                        (Cov_PhiT, :77-82)
 //   pass 1: PCP[a][b] = Qsym[a][b] + sum_k Phi[a][k] W[old_k][b]           (:85-90)
-//   pass 2: P(new, :) = W^T, P(:, new) = W, P(new, new) = PCP, negative diagonal -> flags[1]   (:93-113)
+//   pass 2: P(new, :) = W^T, P(:, new) = W, P(new, new) = PCP, a negative entry anywhere on the diagonal -> flags[1]   (:93-113)
 __global__ void k_cov_propagate(int N, int nid, int n_new, int n_old, const int32_t *__restrict__ old_ids, const double *__restrict__ Phi,
                                 const double *__restrict__ Q, double *P, double *W, double *PCP, int32_t *flags, int pass) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -317,6 +317,8 @@ __global__ void k_cov_propagate(int N, int nid, int n_new, int n_old, const int3
       const double v = W[t];
       P[(size_t)i * N + nid + a] = v;
       P[(size_t)(nid + a) * N + i] = v;
+      // the reference scans the WHOLE diagonal (:101-113): a row outside the block keeps its diagonal entry (no thread of this pass writes it)
+      if (a == 0 && P[(size_t)i * N + i] < 0.0) flags[1] = 1;
     }
   }
 }
