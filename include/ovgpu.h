@@ -1100,7 +1100,11 @@ int ovgpu_msckf_merge_update(ovgpu_ctx *ctx, const void *tris_dev, int G,
 /* The same exchange in Gram form (k_gram.h): every GPU accumulates G_g = [H_g | r_g]^T [H_g | r_g] of its
  * shard, the shards' sum is ONE all-reduce of ovgpu_gram_len() doubles (a 16 ceil((D+1)/16) square, row
  * major, + 1 trailing double = the accepted-row count), and every rank factors the sum and applies
- * the identical update.  Needs D <= 255.  The caller falls back to the triangle exchange above when
+ * the identical update.  Needs D <= 383 (OVGPU_ERR_CAPACITY beyond, from all three calls, the state untouched); a rank
+ * whose shard is empty hands out zeros and takes the summed matrix as the other ranks' whitened one.  A follower time-out of the
+ * single-launch Cholesky (ovgpu_msckf_update_sharded below) makes ovgpu_msckf_gram_update and ovgpu_msckf_merge_update return OVGPU_ERR_HIP:
+ * no update was applied.  ovgpu_msckf_gram_update leaves the state untouched and may be called again with the same buffer; after
+ * ovgpu_msckf_merge_update's, upload the state again (ovgpu_set_state / ovgpu_reset_state) before the call is repeated.  The caller falls back to the triangle exchange above when
  * the summed row count is below 4 (D + 1) (short stacks: see DESIGN.md section 4).  Replaces the
  * same stretch of UpdaterMSCKF::update as ovgpu_msckf_local / ovgpu_msckf_merge_update.            */
 int ovgpu_gram_len(ovgpu_ctx *ctx, int64_t *n_doubles);
@@ -1152,8 +1156,9 @@ uint64_t ovgpu_stream(ovgpu_ctx *ctx);
 /* Gram matrices of the (identically whitened) shards add, so the exchange is */
 /* ONE all-reduce of (16 ceil((D+1)/16))^2 doubles over RCCL / xGMI on the    */
 /* context's stream; every GPU then applies the identical update.  With the   */
-/* Householder route (or more than 255 columns) the D x (D+1) triangles are   */
-/* all-gathered and merged instead.  RCCL is loaded at run time.              */
+/* Householder route (or more than 383 columns: 24 tile columns of [H | r],  */
+/* whatever "gram_wide" says) the D x (D+1) triangles are all-gathered and    */
+/* merged instead.  RCCL is loaded at run time.                               */
 /* ------------------------------------------------------------------------- */
 typedef struct { char internal[128]; } ovgpu_comm_id; /* = ncclUniqueId */
 
@@ -1174,14 +1179,22 @@ int ovgpu_comm_info(ovgpu_ctx *ctx, int32_t *rank_told, int32_t *world_told, int
  * blocks of the factor workgroup's own launch, placed behind it, so it takes a wedged device or the test knob to see one) is NOT
  * repeated in a world of more than one rank -- a local repeat would issue a collective the peers never match: OVGPU_ERR_HIP is
  * returned, this rank's state is untouched while the peers have applied the update, and the caller uploads the state again on every
- * rank (ovgpu_multi_msckf_update: the same, detected for the whole set).  options.no_single_launch_cholesky = 1 rules it out. */
+ * rank (ovgpu_multi_msckf_update: the same, detected for the whole set).  options.no_single_launch_cholesky = 1 rules it out.
+ * ovgpu_last_update_route reports the exchange the call took: OVGPU_COMPRESS_GRAM, or OVGPU_COMPRESS_TSQR for the triangles. */
 int ovgpu_msckf_update_sharded(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, double *chi2_thresh, double *p_FinG, double *dx, double *P_out,
                                ovgpu_update_stats *stats);
 int ovgpu_msckf_update_sharded_async(ovgpu_ctx *ctx);
 
 /* One host process driving several GPUs (the reference's host is ONE C++ process: VioManager.cpp:155-156, :518-526).
- * devices == NULL: 0 .. n-1.  set_features deals the tracks round-robin by length; the update returns every output in the
- * caller's feature order. */
+ * devices == NULL: 0 .. n-1.  set_features deals the tracks round-robin by length (stable sort by descending length, rank g holds
+ * every n-th from the g-th on, in ascending order of the caller's indices); the update returns every output in the caller's feature
+ * order.  A device may be named more than once, up to 8 times (OVGPU_ERR_CAPACITY beyond, nothing is left allocated): those ranks
+ * share the device and exchange through the library's loop-back collective, and are driven through ovgpu_multi_msckf_update alone
+ * (ovgpu_msckf_update_sharded[_async] on one of them returns OVGPU_ERR_INVALID).
+ * ovgpu_multi_msckf_update does NOT repeat an update: a prior block that does not factor on the Gram exchange returns
+ * OVGPU_ERR_NOT_SPD for the set, and every rank's state is left as it was uploaded, bit for bit (the prior is replicated: every rank
+ * skipped the same kernels).  Such a filter selects compress_route = OVGPU_COMPRESS_TSQR, whose exchange needs no factor of the prior.
+ * ovgpu_last_update_route of a rank (ovgpu_multi_ctx) reports the exchange the set took. */
 typedef struct ovgpu_multi ovgpu_multi;
 int ovgpu_multi_create(const ovgpu_options *opts, int n, const int *devices, ovgpu_multi **out);
 void ovgpu_multi_destroy(ovgpu_multi *m);

@@ -154,6 +154,7 @@ static int sharded_exchange(ovgpu_ctx *c, bool gram) {
   return OVGPU_OK;
 }
 static int sharded_update(ovgpu_ctx *c, bool gram) {
+  c->last_route = gram ? OVGPU_COMPRESS_GRAM : OVGPU_COMPRESS_TSQR; // ovgpu_last_update_route: the exchange this rank took (the pipeline sets it for STAGE_EKF only)
   if (gram) return enqueue_ekf_gram(c, c->prior_pending ? 2 : 3);
   const int G = c->comm_world;
   if (G > 1) {

@@ -111,8 +111,9 @@ int ovgpu_msckf_local_gram(ovgpu_ctx *c, int32_t *feat_status, double *chi2, dou
     HIPCHK(hipMemcpyAsync(dst, c->gram_G.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(k_gram_count, dim3(1), dim3(1), 0, c->stream, dst + n, c->rows_used.p);
     HIPCHK(hipGetLastError());
-  } else {
+  } else { // an empty shard: nothing was whitened here, but the sum ovgpu_msckf_gram_update receives is the other ranks' whitened Gram matrix
     HIPCHK(hipMemsetAsync(dst, 0, sizeof(double) * (n + 1), c->stream));
+    c->gram_is_whitened = c->whiten;
   }
   if (feat_status || chi2 || chi2_thresh || p_FinG || stats) {
     rc = read_feature_outputs(c, feat_status, chi2, chi2_thresh, p_FinG, stats);
@@ -149,6 +150,11 @@ int ovgpu_msckf_gram_update(ovgpu_ctx *c, const void *gram_dev, double *dx, doub
   if (dx) HIPCHK(hipMemcpyAsync(dx, c->dx.p, sizeof(double) * c->N, hipMemcpyDeviceToHost, s));
   if (P_out) HIPCHK(hipMemcpyAsync(P_out, c->P.p, sizeof(double) * c->N * c->N, hipMemcpyDeviceToHost, s));
   HIPCHK(upload_sync(c, s));
+  // a follower's time-out switched the kernels behind the factorisation off: nothing was modified, and dx / P_out are not an update's
+  if (flags[2]) {
+    c->chol_timeouts++;
+    return set_err(OVGPU_ERR_HIP, CHOL_TIMED_OUT "; the state was not modified: call again with the same buffer" CHOL_STEPWISE_HINT);
+  }
   const int status = flags[0] ? OVGPU_ERR_NOT_SPD : (flags[1] ? OVGPU_ERR_NEGATIVE_DIAGONAL : OVGPU_OK);
   if (stats) stats->status = status;
   if (status != OVGPU_OK) return set_err(status, "EKF update failed");
@@ -179,6 +185,10 @@ int ovgpu_msckf_merge_update(ovgpu_ctx *c, const void *tris_dev, int G, double *
   if (dx) HIPCHK(hipMemcpyAsync(dx, c->dx.p, sizeof(double) * c->N, hipMemcpyDeviceToHost, s));
   if (P_out) HIPCHK(hipMemcpyAsync(P_out, c->P.p, sizeof(double) * c->N * c->N, hipMemcpyDeviceToHost, s));
   HIPCHK(upload_sync(c, s));
+  if (flags[2]) { // (as ovgpu_msckf_gram_update)
+    c->chol_timeouts++;
+    return set_err(OVGPU_ERR_HIP, CHOL_TIMED_OUT "; no update was applied: upload the state again, then repeat the call" CHOL_STEPWISE_HINT);
+  }
   int status = flags[0] ? OVGPU_ERR_NOT_SPD : (flags[1] ? OVGPU_ERR_NEGATIVE_DIAGONAL : OVGPU_OK);
   if (stats) stats->status = status;
   if (status != OVGPU_OK) return set_err(status, "EKF update failed");
