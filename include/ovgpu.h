@@ -1368,6 +1368,9 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *   "gram_interleaved"        0: k_gram instead of k_gram_il (staging not interleaved with the matrix instructions)
  *   "gram_read_ahead"         (default 1) k_gram_regions reads the operands of a 4-row step during the products of the step before; 0: every step
  *                             opens with its own reads (as k_gram_il).  The same products in the same order: the same Gram matrix bit for bit
+ *   "gram_waves"              (default 8) wavefronts per workgroup of k_gram_regions: 8 puts two on every SIMD, so that one's products fill the matrix
+ *                             pipe while the other issues its staging; 4: one per SIMD.  Anything else is refused.  Every tile is summed by one
+ *                             wavefront over the same rows in the same order: the same Gram matrix bit for bit.  With "gram_read_ahead" = 0 always 4
  *   "featy_chains"            (default 1) k_feat_y takes the run list of the unprojected stack from k_batch_layout's table and requests the next
  *                             slot's record and status a feature ahead; 0: the kernel without either (the run list derived per feature). The same
  *                             loads, products and stores: the results are equal bit for bit.

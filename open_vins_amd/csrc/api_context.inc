@@ -361,6 +361,7 @@ struct ovgpu_ctx {
   // the unprojected stack of the Gram route (ovgpu_types.h: RawStack; k_gram.h: k_gram_regions)
   bool raw_enable = true;          // ovgpu_debug_option "raw_stack"
   bool gram_read_ahead = true;     // k_gram_regions<PF>: operand reads a k-step ahead (ovgpu_debug_option "gram_read_ahead")
+  int gram_waves = 8;              // k_gram_regions<PF, NW>: wavefronts per workgroup, 8 (two per SIMD) or 4 (ovgpu_debug_option "gram_waves"); without the reads ahead always 4
   bool featy_chains = true;        // k_feat_y<.., CH>: the run table, the next slot requested a feature ahead (ovgpu_debug_option "featy_chains"; k_featy.h)
   int raw_work_const = 12;         // per-row cost of a region beside its tiles, in tiles (ovgpu_debug_option "raw_work_const"; see raw_stack_layout)
   bool raw_veto = false;           // this pipeline's stack feeds mode A's factorisation: projected rows (api_pipeline.inc)

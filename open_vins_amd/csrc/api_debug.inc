@@ -87,6 +87,12 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "gram_read_ahead") { // 0: k_gram_regions opens every k-step with its own operand reads (k_gram.h: gram_il_loop without PF) — same products in the same order, the same bits
     if (old_value) *old_value = c->gram_read_ahead ? 1 : 0;
     if (value >= 0) c->gram_read_ahead = value != 0;
+  } else if (n == "gram_waves") { // 8 | 4: k_gram_regions with two wavefronts per SIMD or one (k_gram.h: gram_w8 | gram_il_loop) — every tile summed by one wavefront in the same order, the same bits
+    if (old_value) *old_value = c->gram_waves;
+    if (value >= 0) {
+      if (value != 4 && value != 8) return set_err(OVGPU_ERR_INVALID, "gram_waves: 4 or 8");
+      c->gram_waves = (int)value;
+    }
   } else if (n == "featy_chains") { // 0: k_feat_y as it was before the run table and the requests ahead (k_featy.h: CH = false) — same products in the same order, the same bits
     if (old_value) *old_value = c->featy_chains ? 1 : 0;
     if (value >= 0) c->featy_chains = value != 0;
@@ -180,14 +186,14 @@ int ovgpu_debug_cycles(ovgpu_ctx *c, int enable, long long *out512) {
 }
 
 #ifdef OVG_GRAM_PROF
-// developer build (-DOVG_GRAM_PROF): the phase counters of the last k_gram_regions launch, eight values per wavefront, four wavefronts per workgroup (k_gram.h);
+// developer build (-DOVG_GRAM_PROF): the phase counters of the last k_gram_regions launch, eight values per wavefront, room for eight wavefronts per workgroup (k_gram.h; the four-wavefront form leaves the last four as they were);
 // *launched = the workgroups of that launch (entries past it are an earlier launch's)
 extern "C" int ovgpu_debug_gram_phases(ovgpu_ctx *c, long long *out, int workgroups, int *launched) {
   if (!c || !out || !launched || workgroups < 0 || workgroups > 1024) return set_err(OVGPU_ERR_INVALID, "bad argument");
   *launched = c->gram_wg_n;
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(upload_sync(c, c->stream));
-  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(gram::gram_prof_buf), sizeof(long long) * 32 * workgroups));
+  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(gram::gram_prof_buf), sizeof(long long) * 64 * workgroups));
   return OVGPU_OK;
 }
 #endif

@@ -371,8 +371,12 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   }
   if (c->last_stack_raw) { // the unprojected stack, region by region (k_gram.h: k_gram_regions), the dropped rows' region subtracted in the reduction
     HIPCHK(c->gram_part.reserve((size_t)std::max(c->gram_wg_tiles, 1) * 256));
-    hipLaunchKernelGGL(c->gram_read_ahead ? with_max_lds<gram::k_gram_regions<true>>(c) : with_max_lds<gram::k_gram_regions<false>>(c), dim3(c->gram_wg_n), dim3(256), gram::gram_lds_bytes(), c->stream,
-                       (const double *)c->Hraw.p, (const gram::GramRegionWG *)c->gram_wg.p, c->gram_part.p);
+    const int waves = c->gram_read_ahead ? c->gram_waves : 4; // (two wavefronts per SIMD exist with the reads ahead only)
+    const auto kern = !c->gram_read_ahead ? with_max_lds<gram::k_gram_regions<false>>(c)
+                      : waves == 8        ? with_max_lds<gram::k_gram_regions<true, 8>>(c)
+                                          : with_max_lds<gram::k_gram_regions<true>>(c);
+    hipLaunchKernelGGL(kern, dim3(c->gram_wg_n), dim3(64 * waves), gram::gram_lds_bytes(), c->stream, (const double *)c->Hraw.p, (const gram::GramRegionWG *)c->gram_wg.p,
+                       c->gram_part.p);
     hipLaunchKernelGGL(gram::k_gram_regions_reduce, dim3(NP, 256 / gram::RR_E), dim3(gram::RR_E * gram::RR_G), 0, c->stream, NT, D, c->raw_rs,
                        (const gram::GramRegionWG *)c->gram_wg.p, c->gram_wg_n, (const double *)c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());

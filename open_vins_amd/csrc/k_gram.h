@@ -19,6 +19,7 @@
 //     matrix cores.  This kernel's 27-34 tiles per wavefront need 172 + 256 registers: one wavefront per SIMD, by design.
 //   * 8 wavefronts, two per SIMD, 13-17 tiles each, ONE code path (slot -> tile by run-time offsets, no spills): 0.27 ms — one LDS
 //     operand read per matrix instruction instead of one per two; the second wavefront per SIMD does not make up for it.
+//     (k_gram_regions' eight-wavefront form below is the other shape: a compile-time deal per tile-column count, one instantiation per wavefront.)
 //   * rows r and r + 4 interleaved in LDS so that one ds_read_b128 feeds two 4-row steps (half the LDS instructions): 0.226 vs 0.225 ms
 //     at 14 tile columns — the LDS instruction rate is not the limit.  At the ~1.96 GHz the chip sustains under this load the kernel's
 //     62-64 % of the nominal FP64 matrix peak is ~78 % of what the clock allows.
@@ -34,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include <utility>
 
 namespace ovg {
 namespace gram {
@@ -79,7 +81,7 @@ constexpr int GR_ACC = 34; // tiles per wavefront: 64 - (R0 + R1 + R2 + R3)
 // first barrier, [4] the stage loop, [5] of it the waits for the first operand read of a k-step, [6] of it the stage barriers, [7] the tile stores.
 // The stamps fence the schedule (every use drains the LDS counter): read the SHARES, never this build's run time.
 #ifdef OVG_GRAM_PROF
-__device__ long long gram_prof_buf[1024 * 4 * 8];
+__device__ long long gram_prof_buf[1024 * 8 * 8]; // [workgroup & 1023][wavefront 0 .. 7][value]: the four-wavefront form fills the first four
 #define GRAM_T(x)                          \
   __builtin_amdgcn_sched_barrier(0);       \
   const long long x = clock64();           \
@@ -349,7 +351,7 @@ template <int W, int NTC, bool BAL = false, bool PF = false> __device__ __forcei
 #ifdef OVG_GRAM_PROF
   GRAM_T(prof_t2)
   if (BAL && lane == 0) {
-    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 4 + W) * 8;
+    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 8 + W) * 8;
     o[3] = prof_t1 - prof_t0, o[4] = prof_t2 - prof_t1, o[5] = prof_wait, o[6] = prof_bar;
   }
 #endif
@@ -392,20 +394,213 @@ struct GramRegionWG {
   int64_t h_off, rows;          // first element and rows of the region
   int32_t chunk_begin, chunk_end, part_tile, region; // this workgroup's stages of GR_ROWS rows; its first partial tile; its region's place in GramRegionSum, + 16: subtracted
 };
-template <int NTC, bool PF> __device__ __forceinline__ void gram_region_body(const GramParams &p, double *gram_lds, int tid, int lane, int wave, int cb, int ce) {
-  d4 acc[GR_ACC];
+// ---------------------------------------------------------------------------------------------------
+// The eight-wavefront form of k_gram_regions (NW = 8): 512 threads, TWO wavefronts on every SIMD, the same stage buffer.
+//
+// One wavefront per SIMD issues its own staging between its products — per 32-row stage 2 ntc global loads, the walk of wr / wc with a select and an LDS
+// write per element, and the operand reads — and while it does, nobody else feeds that SIMD's matrix pipe (profiles/r16_gram_phases.txt: the stage loop
+// without its waits is 217 - 243 kcycles of which the pipe is busy 165).  The staging slots are fenced runs of non-matrix instructions, so a partner's
+// products can enter the pipe during them.  Here a stage's elements go to 512 threads (ntc slots per thread), and the tiles of the triangle go to eight
+// wavefronts by a compile-time deal per NTC: the T = NTC (NTC + 1) / 2 tiles in row-major order (= pair_index) cut into eight runs of floor / ceil (T / 8)
+// tiles, so a tile row may be split between two wavefronts by column range; wavefronts w and w + 4 share a SIMD, and the longer runs come first, so the
+// SIMDs are level to one tile (14: 27 / 26 / 26 / 26 as before; 12: 20 / 20 / 19 / 19; 4: 3 / 3 / 2 / 2 against 4 / 3 / 2 / 1).  A wavefront reads
+// only the operand columns its tiles use.  Every tile is still accumulated by ONE wavefront, rows ascending, four to a product, from zero: the partial
+// tiles are bit for bit the four-wavefront kernel's (tests/test_gpu_gram_waves.py).
+// ---------------------------------------------------------------------------------------------------
+template <int NTC> struct Deal8 {
+  static constexpr int T = NTC * (NTC + 1) / 2;
+  static constexpr int begin(int w) { return w * (T / 8) + (w < T % 8 ? w : T % 8); } // first tile of wavefront w (8: one past the last)
+  static constexpr int count(int w) { return begin(w + 1) - begin(w); }
+  static constexpr int row_of(int t) {
+    int i = 0;
+    while (t >= NTC - i) t -= NTC - i, i++;
+    return i;
+  }
+  static constexpr int col_of(int t) {
+    int i = 0;
+    while (t >= NTC - i) t -= NTC - i, i++;
+    return i + t;
+  }
+  static constexpr unsigned cols(int w) { // the operand columns of wavefront w: rows and columns of its tiles
+    unsigned m = 0;
+    for (int t = begin(w); t < begin(w + 1); t++) m |= (1u << row_of(t)) | (1u << col_of(t));
+    return m;
+  }
+  static constexpr int ncols(int w) {
+    int n = 0;
+    for (int j = 0; j < NTC; j++) n += (cols(w) >> j) & 1;
+    return n;
+  }
+  static constexpr int nth_col(int w, int n) { // ascending
+    for (int j = 0; j < NTC; j++)
+      if ((cols(w) >> j) & 1) {
+        if (n == 0) return j;
+        n--;
+      }
+    return 0;
+  }
+  static constexpr int max_count() {
+    int m = 0;
+    for (int w = 0; w < 8; w++) m = count(w) > m ? count(w) : m;
+    return m;
+  }
+};
+template <int... S, class F> __device__ __forceinline__ void static_for(std::integer_sequence<int, S...>, F &&f) { (f(std::integral_constant<int, S>{}), ...); }
+
+// One wavefront's whole pass (W = 0 .. 7): gram_il_loop's schedule with PF — puts of stage s + 1 in k-steps 0-3, fetches of stage s + 2 in k-steps 4-7, the
+// operand reads a k-step ahead — over this wavefront's run of tiles.  Position s of a k-step is [product of tile s] [read of the s-th operand column for the
+// next k-step] [staging slot s]; a wavefront with more operand columns or slots than tiles (4 tile columns: 1 - 2 tiles) issues the rest behind its last product.
+template <int W, int NTC> __device__ __forceinline__ void gram_w8(const GramParams &p, double *gram_lds, int tid, int lane, int chunk_begin, int chunk_end) {
+  using D = Deal8<NTC>;
+  static_assert(D::begin(0) == 0 && D::begin(8) == D::T && D::count(7) >= 1, "every tile dealt once, no wavefront without one");
+  static_assert(D::max_count() <= (D::T + 7) / 8 + 1, "the busiest wavefront within a tile of the mean");
+  constexpr int T0 = D::begin(W), N = D::count(W), NU = D::ncols(W);
+  constexpr int NQ = NTC;             // >= ceil(GR_ROWS * LD / 512): element e = tid + 512 q of a stage
+  constexpr int SL = (NQ + 3) / 4;    // staging slots per k-step
+  constexpr int NS = N > NU ? (N > SL ? N : SL) : (NU > SL ? NU : SL);
+  constexpr int SCRATCH = GR_LS - 1;
+  const int LD = p.LD;
+  const int g = lane >> 4, cl = lane & 15;
+  d4 acc[N];
 #pragma unroll
-  for (int i = 0; i < GR_ACC; i++) acc[i] = d4{0, 0, 0, 0};
-  switch (wave) {
-  case 0: gram_il_loop<0, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<0, true>(p.part, NTC, lane, acc); break;
-  case 1: gram_il_loop<1, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<1, true>(p.part, NTC, lane, acc); break;
-  case 2: gram_il_loop<2, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<2, true>(p.part, NTC, lane, acc); break;
-  default: gram_il_loop<3, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<3, true>(p.part, NTC, lane, acc); break;
+  for (int i = 0; i < N; i++) acc[i] = d4{0, 0, 0, 0};
+  double v[NQ];
+  const double *src_f = p.H;
+  int left_f = 1, left_v = 1;
+  const int row0 = tid / LD, col0 = tid - row0 * LD, step_r = 512 / LD, step_c = 512 - step_r * LD;
+  int wr = row0, wc = col0;
+  auto put = [&](double *buf, int q) {
+    buf[wr < GR_ROWS ? wr * GR_LS + wc : SCRATCH] = (tid + 512 * q) < left_v ? v[q] : 0.0;
+    wr += step_r, wc += step_c;
+    if (wc >= LD) wc -= LD, wr++;
+  };
+  auto aim = [&](int chunk) {
+    const int c = chunk < chunk_end ? chunk : chunk_end - 1;
+    const int64_t first = (int64_t)c * GR_ROWS;
+    const int64_t left64 = (p.rows_total - first) * LD;
+    left_f = (int)(left64 < (int64_t)GR_ROWS * LD ? left64 : (int64_t)GR_ROWS * LD);
+    src_f = p.H + first * LD;
+  };
+  auto fetch1 = [&](int q) {
+    const int e = tid + 512 * q;
+    v[q] = src_f[e < left_f ? e : left_f - 1];
+  };
+#ifdef OVG_GRAM_PROF
+  long long prof_wait = 0, prof_bar = 0;
+  GRAM_T(prof_t0)
+#endif
+  if (chunk_begin < chunk_end) {
+    aim(chunk_begin);
+#pragma unroll
+    for (int q = 0; q < NQ; q++) fetch1(q);
+    left_v = left_f;
+#pragma unroll
+    for (int q = 0; q < NQ; q++) put(gram_lds, q);
+    aim(chunk_begin + 1);
+#pragma unroll
+    for (int q = 0; q < NQ; q++) fetch1(q);
+    left_v = left_f;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#ifdef OVG_GRAM_PROF
+  GRAM_T(prof_t1)
+#endif
+  double bb[2][GR_NT];
+  for (int chunk = chunk_begin; chunk < chunk_end; chunk++) {
+    const double *cur = gram_lds + (size_t)((chunk - chunk_begin) & 1) * GR_ROWS * GR_LS;
+    double *nxt = gram_lds + (size_t)((chunk - chunk_begin + 1) & 1) * GR_ROWS * GR_LS;
+    wr = row0, wc = col0;
+    static_for(std::make_integer_sequence<int, 8>{}, [&](auto kc) { // (compile-time k-step: every register index below is a constant)
+      constexpr int ks = decltype(kc)::value;
+      if constexpr (ks == 4) aim(chunk + 2);
+      const double *rowp = cur + (4 * ks + g) * GR_LS + cl;
+      if constexpr (ks == 0) { // the rows of a stage are complete only behind its barrier
+        static_for(std::make_integer_sequence<int, NU>{}, [&](auto n) {
+          constexpr int j = D::nth_col(W, decltype(n)::value);
+          bb[0][j] = rowp[16 * j];
+        });
+        __builtin_amdgcn_sched_barrier(0);
+#ifdef OVG_GRAM_PROF
+        GRAM_T(w0)
+        __builtin_amdgcn_s_waitcnt(0xC07F | ((NU - 1) << 8)); // until the first of the reads is back
+        GRAM_T(w1)
+        prof_wait += w1 - w0;
+#endif
+      }
+      static_for(std::make_integer_sequence<int, NS>{}, [&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        constexpr bool ahead = ks < 7 && s < NU, slot = s < SL && (ks & 3) * SL + s < NQ;
+        if constexpr (s < N) {
+          constexpr int ti = D::row_of(T0 + s), tj = D::col_of(T0 + s);
+          GRAM_MFMA(bb[ks & 1][ti], bb[ks & 1][tj], acc[s]);
+        }
+        if constexpr (ahead || slot) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (ahead) {
+          constexpr int j = D::nth_col(W, s);
+          bb[(ks + 1) & 1][j] = rowp[4 * GR_LS + 16 * j];
+        }
+        if constexpr (slot) {
+          constexpr int q = (ks & 3) * SL + s;
+          if constexpr (ks < 4) put(nxt, q);
+          else fetch1(q);
+        }
+        if constexpr (ahead || slot) __builtin_amdgcn_sched_barrier(0);
+      });
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    left_v = left_f;
+#ifdef OVG_GRAM_PROF
+    GRAM_T(b0)
+#endif
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#ifdef OVG_GRAM_PROF
+    GRAM_T(b1)
+    prof_bar += b1 - b0;
+#endif
+  }
+#ifdef OVG_GRAM_PROF
+  GRAM_T(prof_t2)
+  if (lane == 0) {
+    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 8 + W) * 8;
+    o[3] = prof_t1 - prof_t0, o[4] = prof_t2 - prof_t1, o[5] = prof_wait, o[6] = prof_bar;
+  }
+#endif
+  // partial tiles -> memory, gram_put's slot order
+#pragma unroll
+  for (int s = 0; s < N; s++) {
+    double2 *o = reinterpret_cast<double2 *>(p.part + (size_t)(T0 + s) * 256) + lane; // (T0 + s = pair_index(NTC, row, column))
+    o[0] = double2{acc[s][0], acc[s][1]}, o[64] = double2{acc[s][2], acc[s][3]};
+  }
+}
+
+template <int NTC, bool PF, int NW> __device__ __forceinline__ void gram_region_body(const GramParams &p, double *gram_lds, int tid, int lane, int wave, int cb, int ce) {
+  if constexpr (NW == 8) {
+    switch (wave) { // every wavefront runs its own instantiation: tiles, operand columns and accumulator indices are compile-time
+    case 0: gram_w8<0, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    case 1: gram_w8<1, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    case 2: gram_w8<2, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    case 3: gram_w8<3, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    case 4: gram_w8<4, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    case 5: gram_w8<5, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    case 6: gram_w8<6, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    default: gram_w8<7, NTC>(p, gram_lds, tid, lane, cb, ce); break;
+    }
+  } else {
+    d4 acc[GR_ACC];
+#pragma unroll
+    for (int i = 0; i < GR_ACC; i++) acc[i] = d4{0, 0, 0, 0};
+    switch (wave) {
+    case 0: gram_il_loop<0, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<0, true>(p.part, NTC, lane, acc); break;
+    case 1: gram_il_loop<1, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<1, true>(p.part, NTC, lane, acc); break;
+    case 2: gram_il_loop<2, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<2, true>(p.part, NTC, lane, acc); break;
+    default: gram_il_loop<3, NTC, true, PF>(p, gram_lds, tid, lane, cb, ce, acc), gram_put<3, true>(p.part, NTC, lane, acc); break;
+    }
   }
 }
 // PF = false keeps the k-step of k_gram_il (every k-step opens with its own operand reads): ovgpu_debug_option "gram_read_ahead" = 0, the other side of the
-// bit comparison in tests/test_gpu_gram_regions_shapes.py
-template <bool PF> __global__ void __launch_bounds__(256) k_gram_regions(const double *H, const GramRegionWG *tab, double *part) {
+// bit comparison in tests/test_gpu_gram_regions_shapes.py.  NW = 4 | 8 wavefronts (ovgpu_debug_option "gram_waves"); eight exist with the reads ahead only.
+template <bool PF, int NW = 4> __global__ void __launch_bounds__(64 * NW) k_gram_regions(const double *H, const GramRegionWG *tab, double *part) {
+  static_assert(NW == 4 || (NW == 8 && PF), "the eight-wavefront form reads ahead");
   extern __shared__ double gram_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const GramRegionWG r = tab[blockIdx.x];
@@ -416,7 +611,7 @@ template <bool PF> __global__ void __launch_bounds__(256) k_gram_regions(const d
   // the staging writes every element of the ld columns of a stage's rows, rows past the region's end as zeros, and the k-steps read 16 ntc columns:
   // only the columns between the two, of both buffers, are read and never written — they are all there is to zero (a few stores per thread; the
   // whole 139 KB took 4460 cycles = 2 us of every workgroup, profiles/r16_gram_phases.txt)
-  for (int i = tid, w = 16 * r.ntc - r.ld; i < 2 * GR_ROWS * w; i += 256) gram_lds[(i / w) * GR_LS + r.ld + i % w] = 0.0;
+  for (int i = tid, w = 16 * r.ntc - r.ld; i < 2 * GR_ROWS * w; i += 64 * NW) gram_lds[(i / w) * GR_LS + r.ld + i % w] = 0.0;
   __syncthreads();
 #ifdef OVG_GRAM_PROF
   GRAM_T(prof_c1)
@@ -424,19 +619,19 @@ template <bool PF> __global__ void __launch_bounds__(256) k_gram_regions(const d
   GramParams p;
   p.LD = r.ld, p.NT = r.ntc, p.rows_total = r.rows, p.H = H + r.h_off, p.part = part + (size_t)r.part_tile * 256;
   switch (r.ntc) {
-  case 4: gram_region_body<4, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 6: gram_region_body<6, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 8: gram_region_body<8, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 10: gram_region_body<10, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 12: gram_region_body<12, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  case 14: gram_region_body<14, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
-  default: gram_region_body<15, PF>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 4: gram_region_body<4, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 6: gram_region_body<6, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 8: gram_region_body<8, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 10: gram_region_body<10, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 12: gram_region_body<12, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  case 14: gram_region_body<14, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
+  default: gram_region_body<15, PF, NW>(p, gram_lds, tid, lane, wave, r.chunk_begin, r.chunk_end); break;
   }
 #ifdef OVG_GRAM_PROF
   __builtin_amdgcn_s_waitcnt(0x0070); // the tile stores are out
   GRAM_T(prof_c2)
   if (lane == 0) {
-    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 4 + wave) * 8;
+    long long *o = gram_prof_buf + ((size_t)(blockIdx.x & 1023) * 8 + wave) * 8;
     o[0] = prof_w0, o[1] = wall_clock64(), o[2] = prof_c1 - prof_c0, o[7] = (prof_c2 - prof_c1) - o[3] - o[4];
   }
 #endif
