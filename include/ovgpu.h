@@ -205,10 +205,33 @@ typedef struct {
                              /* 17 (tuning / tests; a shape the batch does not   */
                              /* fit falls back to the automatic choice)          */
   int32_t gram_fp32;         /* 1: the Gram matrix of the (prior-whitened)    */
-                             /* stack is accumulated in fp32 on                */
-                             /* v_mfma_f32_16x16x4_f32 — BASELINE configs[4]'s */
-                             /* "fp32 compressed-QR"; dx 1e-4 / P 1e-3 of the  */
-                             /* f64 result (tests/test_gpu_fullsize.py)        */
+                             /* stack is formed in fp32 — BASELINE configs[4]'s */
+                             /* "fp32 compressed-QR"; up to 383 columns, on the */
+                             /* update, local-Gram and sharded entries.  Two    */
+                             /* device paths.  (a) The fused per-feature        */
+                             /* kernels (the MSCKF fast path: one noise level,  */
+                             /* no resident landmark off the fast path,         */
+                             /* "featy_big" != 2) store the stack as FLOATS and */
+                             /* gram32::k_gram_f32 forms G on                   */
+                             /* v_mfma_f32_32x32x2_f32 ("stack_is_f32" 1,       */
+                             /* "last_gram_kernel" 5).  (b) Where the stack     */
+                             /* stays float64 on such a context — the general   */
+                             /* per-feature kernel: no_fast_feature_kernel,     */
+                             /* tracks beyond the fused kernels, per-feature    */
+                             /* noise, resident landmarks off the fast path; or */
+                             /* "featy_big" = 2, which has no float twin —      */
+                             /* gram::k_gram_blk<true> rounds it to float stage */
+                             /* by stage and forms G on v_mfma_f32_16x16x4_f32  */
+                             /* ("last_gram_kernel" 2).  Either way a product   */
+                             /* is summed in fp32 over one stage of 32 rows at  */
+                             /* most and the stages in float64, so with         */
+                             /* u = 2^-24 and n_i the 2-norm of column i of the */
+                             /* stack  |G_ij - (A^T A)_ij| <= 40 u n_i n_j      */
+                             /* (35 u and 34 u by the arithmetic; measured 0.4  */
+                             /* to 9 u: tests/test_gpu_fp32_gram.py, DESIGN.md  */
+                             /* section 7); the update stays within dx 1e-4 /   */
+                             /* P 1e-3 of the f64 result                        */
+                             /* (tests/test_gpu_fullsize.py)                    */
 } ovgpu_options;
 
 /* Measurement compression (UpdaterHelper.cpp:456-487) of ovgpu_msckf_update / ovgpu_slam_update (mode B) and  */
@@ -1317,6 +1340,10 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles', 6 k_unwhiten_blk<24> on the
  *                             two-panel factorisation's inverse tiles, 7 k_unwhiten_blk<24> on k_uinv_tiles' — ovgpu_slam_compress under
  *                             "slam_mode_a"): the rule at ovgpu_msckf_compress
+ *   "last_gram_workgroups"    (read only) the row shares of that Gram kernel where it is one of the two that options.gram_fp32 reaches: gridDim.x of the
+ *                             last pipeline's k_gram_f32 launch (workgroups per part of the macro-tile triangle: max(1, ceil(rows / 1536),
+ *                             min(ceil(2 CUs / parts), ceil(rows / 128)))) or k_gram_blk launch (min(CUs, ceil(rows / 32)); a tenth of the CUs at
+ *                             25 .. 32 tile columns); 0 for every other Gram kernel, for a pipeline without one and before the first
  *   "slam_fused"              (default 0) a level; the read-back returns it (values above 3 are taken as 3).
  *                             1: ovgpu_slam_update / ovgpu_slam_update_chunked run the per-feature stage of a batch as the fused kernel
  *                             k_slam_y — one sweep Y = H L on the matrix cores feeds the stack and the gate's S0 = Y Y^T + sigma_f^2 I — when every

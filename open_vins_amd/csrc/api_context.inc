@@ -444,6 +444,7 @@ struct ovgpu_ctx {
   //   factor:   0 none (the Householder triangle), 1 k_gram_pchol_blk<4, 9, 2>, 2 k_gram_pchol_blk<7, 15, 4>, 3 k_pchol_panel + k_pchol_schur (k_pchol_wide.h), 32 + NB k_gram_pchol<NB>
   //   unwhiten: 0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>, 4 k_unwhiten_blk<32> on the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles'
   int last_gram_kernel = 0, last_factor_kernel = 0, last_unwhiten_kernel = 0;
+  int last_gram_workgroups = 0;   // read-only "last_gram_workgroups": gridDim.x of the last pipeline's k_gram_f32 (Gw) or k_gram_blk (Gb) launch, 0 for every other Gram kernel
   bool chol_timed_out = false;    // finish_update: a follower of the single-launch Cholesky gave up waiting; nothing was modified
   bool prior_pending = false; // the sharded update's local stage has started the prior block's factorisation on stream2
   bool prior_overlap = true; // options.no_prior_overlap == 0: the prior block is factored on the second stream

@@ -112,6 +112,8 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->last_feat_kernel;
   } else if (n == "last_gram_kernel") { // read-only, this and the two below: what the last batch pipeline launched (api_context.inc lists the codes)
     if (old_value) *old_value = c->last_gram_kernel;
+  } else if (n == "last_gram_workgroups") { // read-only: gridDim.x of the last pipeline's k_gram_f32 or k_gram_blk launch (the row shares), 0 otherwise
+    if (old_value) *old_value = c->last_gram_workgroups;
   } else if (n == "last_factor_kernel") {
     if (old_value) *old_value = c->last_factor_kernel;
   } else if (n == "last_unwhiten_kernel") {

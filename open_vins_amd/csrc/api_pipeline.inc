@@ -366,7 +366,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     hipLaunchKernelGGL(gram32::k_gram_f32_reduce, dim3(slots, 4), dim3(256), 0, c->stream, (const int32_t *)c->gram32_tiles.p, Gw,
                        (const float *)c->gram32_part.p, c->gram_G.p, LG);
     HIPCHK(hipGetLastError());
-    c->last_gram_kernel = 5;
+    c->last_gram_kernel = 5, c->last_gram_workgroups = Gw;
     return factor ? set_err(OVGPU_ERR_CAPACITY, "the fp32 Gram variant feeds the on-device update only") : OVGPU_OK;
   }
   if (c->last_stack_raw) { // the unprojected stack, region by region (k_gram.h: k_gram_regions), the dropped rows' region subtracted in the reduction
@@ -403,7 +403,7 @@ static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
     else hipLaunchKernelGGL(with_max_lds<gram::k_gram_blk<true>>(c), dim3(Gb, pairs), dim3(256), gram::gram_blk_lds_bytes() / 2, c->stream, g, NB);
     hipLaunchKernelGGL(gram::k_gram_blk_reduce, dim3(gram::GB_T * gram::GB_T, pairs), dim3(256), 0, c->stream, NB, NT, Gb, c->gram_part.p, c->gram_G.p);
     HIPCHK(hipGetLastError());
-    c->last_gram_kernel = 2;
+    c->last_gram_kernel = 2, c->last_gram_workgroups = Gb;
     return factor ? enqueue_gram_factor(c) : OVGPU_OK; // (the pivoted factor: k_gram_pchol<9 .. 12> up to 383 columns, k_pchol_wide.h beyond)
   }
   switch ((NT + 1) / 2) {
@@ -844,7 +844,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
   const bool factor_gram = c->factor_from_gram && !gram_only && c->mode_a_factor != 0 && !c->force_tsqr && b.F > 0 && (c->LD + 15) / 16 <= mode_a_tile_cap(c) &&
                            (stages & STAGE_EKF) == 0 && (stages & STAGE_LOCAL) != 0 && c->whiten && !c->gram_fp32 && (!slam || c->slam_mode_a_on >= 1); // (SLAM stacks: Householder by default, "slam_mode_a")
   c->factor_from_gram = false, c->last_factor_from_gram = factor_gram;
-  c->last_gram_kernel = c->last_factor_kernel = c->last_unwhiten_kernel = 0;
+  c->last_gram_kernel = c->last_factor_kernel = c->last_unwhiten_kernel = 0, c->last_gram_workgroups = 0;
   c->force_tsqr = false;
   // The prior block's factorisation needs nothing from the measurements: it runs on the second stream next to the
   // triangulation.  With the whitened stack (default) the per-feature kernel reads its factor L, so it joins before that kernel;
