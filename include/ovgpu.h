@@ -1326,7 +1326,8 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             4 the fused kernel of the SLAM update (k_slam_y.h, under "slam_fused")
  *                             (k_slam_y<false>: no single-depth landmark observed), 5 k_slam_y<true>, the same kernel with the projection of
  *                             single-depth landmarks ("slam_fused" = 2), 6 / 7 the long shapes of k_slam_y<false> / k_slam_y<true>: a batch whose
- *                             longest track holds 63 to 126 measurements ("slam_fused" = 3)
+ *                             longest track holds 63 to 126 measurements ("slam_fused" = 3), 8 / 9 the block-row shapes k_slam_y_big<false> /
+ *                             k_slam_y_big<true>: 127 to 232 measurements ("slam_fused_big" = 1 under "slam_fused" = 3)
  *   "sys_lds_limit" / "sys_m_lds_max" / "sys_rows_global" / "sys_row_stride" / "sys_lds_bytes"  (read only) the general per-feature kernel's
  *                             LDS carve for the batch in force, as sized with the last ovgpu_set_features (or the entry point that laid the batch out):
  *                             the byte limit of a workgroup's LDS; the largest track length whose gate matrix is LDS-resident (longer tracks of
@@ -1366,6 +1367,18 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             shapes of level 2 with their bits (4 / 5); 127 measurements and beyond, and every fall-back of levels 1 and 2, keep
  *                             the general kernel.  Takes effect with the next ovgpu_set_features (a batch over landmarks of both sizes is laid out
  *                             again when a SLAM call names its landmarks: the level in force at that call decides)
+ *   "slam_fused_big"          (default 0) a level; the read-back returns it (1 and every value above is taken as 1).  It acts only when
+ *                             "slam_fused" is at 3.  1: a batch whose longest track holds 127 to 232 measurements (SLY_MMAX_B, csrc/k_slam_y_big.h)
+ *                             takes the block-row shape of the fused kernel, k_slam_y_big — k_slam_y's algebra, the gate matrix factored block
+ *                             row by block row in passes of up to 136 tiles as k_feat_y_big does, the records written by a small kernel in front
+ *                             of it on the same stream — on the long shape's terms: 16 <= D, K C <= 8192, no_fast_feature_kernel 0, the whitened
+ *                             route, its LDS carve within the workgroup's limit.  "last_feature_kernel" 8 without, 9 with a single-depth landmark
+ *                             observed; "slam_fused_batches" counts them.  A batch of at most 126 does what level 3 does, with its bits; 233
+ *                             measurements and beyond, and every fall-back of level 3, keep the general kernel; wherever level 3 hands the batch's
+ *                             fused kernel to another entry (ovgpu_slam_update_chunked, ovgpu_slam_compress under "slam_mode_a", the 384 .. 511
+ *                             column routes under "gram_wide" / "mode_a_wide") the block-row shape goes the same way.  A short track of such a
+ *                             batch goes through the block-row kernel's single pass: the same update to rounding, not the short shapes' bits.
+ *                             Takes effect with the next ovgpu_set_features, as "slam_fused" does
  *   "slam_fused_batches"      counter: batch pipelines that took k_slam_y (either instantiation), once per update — the pipelines of an attempt the library repeats (through the
  *                             Householder route after a failed prior pivot, with the step-wise Cholesky after a time-out) are not counted; a value >= 0 sets it
  *   "anchored_fast"           (default 1) batches of an anchored feat_rep_msckf take the fused per-feature kernels: 48-double records with

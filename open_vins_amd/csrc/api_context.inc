@@ -123,6 +123,8 @@ enum FeatKernel : int {
   FK_SLAMY_PROJ = 5,      // k_slam_y<true>: with the projection of single-depth landmarks
   FK_SLAMY_LONG = 6,      // the long shapes of the two: 63 .. 126 observations ("slam_fused" = 3)
   FK_SLAMY_LONG_PROJ = 7,
+  FK_SLAMY_BIG = 8,       // k_slam_y_big<false> (k_slam_y_big.h): 127 .. 232 observations, block row by block row ("slam_fused_big")
+  FK_SLAMY_BIG_PROJ = 9,  // k_slam_y_big<true>
 };
 
 // What the batch in force and the switches at layout time determine about the per-feature stage: a value, made by plan_feature_stage
@@ -143,6 +145,7 @@ struct FeatPlan {
   // the fused kernel a SLAM batch was laid out for (FK_SLAMY ..), or FK_GENERAL: none — and its LDS bytes
   FeatKernel slam = FK_GENERAL;
   size_t slam_lds = 0;
+  int slam_nt = 0;            // FK_SLAMY_BIG / _PROJ: tile rows of the longest track, the carve's and the scratch's parameter
   const char *error = nullptr; // no kernel holds the batch's longest track (OVGPU_ERR_CAPACITY)
 };
 
@@ -253,6 +256,7 @@ struct ovgpu_ctx {
   bool lm_fast_on = false;        // ovgpu_msckf_update_lm is running: the one entry that takes them with landmarks resident (enqueue_system)
   // the fused per-feature kernel of UpdaterSLAM::update (k_slam_y.h), behind a switch that is off by default
   int slam_fused = 0;             // ovgpu_debug_option "slam_fused", a level: 0 off; 1 SLAM batches whose observed landmarks are all 3-dof are laid out for k_slam_y<false>; 2 also the ones that observe a single-depth landmark, for k_slam_y<true>; 3 also the batches whose longest track holds 63 .. 126 observations, for the long shapes (plan_feature_stage)
+  int slam_fused_big = 0;         // ovgpu_debug_option "slam_fused_big", a level: 0 off; 1 (and above) under "slam_fused" = 3 a batch whose longest track holds 127 .. 232 observations (slamy::SLY_MMAX_B) is laid out for the block-row shapes k_slam_y_big (plan_feature_stage)
   int64_t slam_fused_batches = 0; // ovgpu_debug_option "slam_fused_batches": pipelines that took k_slam_y, counted once per update: the pipelines of an attempt that update_with_fallbacks repeats (Householder route, step-wise Cholesky) are taken off again
   int slam_fused_attempt = 0;     // ... of them, the ones of the update attempt that is running (update_with_fallbacks)
   // device-resident FeatureDatabase (ovgpu_tracks_*)
@@ -354,7 +358,10 @@ struct ovgpu_ctx {
   int featy_skip = 0;              // ovgpu_debug_option "featy_skip": ablation bit mask (timing experiments only)
   DevBuf<double> fs_tq;
   DevBuf<int32_t> fs_inst;
-  DevBuf<double> featyb_ws;        // k_featy_big.h: row panels of the earlier passes, per workgroup
+  DevBuf<double> featyb_ws;        // k_featy_big.h, k_slam_y_big.h: row panels of the earlier passes, per workgroup
+  // k_slam_y_big.h: what its records kernel leaves for it (slamy::SlamYBigStore)
+  DevBuf<double> slyb_rows, slyb_V, slyb_hq;
+  DevBuf<int32_t> slyb_minfo, slyb_inst;
   int featy_big = 0;               // ovgpu_debug_option "featy_big": 1 = the multi-pass kernel also for tracks the one-pass kernels hold,
                                    // 2 = with 5 tiles per wavefront (several passes on short tracks: tests)
   bool no_feat_kernel = false;  // options.no_fast_feature_kernel

@@ -47,6 +47,9 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "slam_fused") { // a level.  1: SLAM batches of 3-dof landmarks take the fused per-feature kernel k_slam_y<false> on the whitened route (k_slam_y.h); 2: batches that observe a single-depth landmark take k_slam_y<true> as well; 3 (and above): batches whose longest track holds 63 .. 126 observations take the long shapes as well; default 0; reads back the level; takes effect with the next ovgpu_set_features
     if (old_value) *old_value = c->slam_fused;
     if (value >= 0) c->slam_fused = (int)std::min<int64_t>(value, 3);
+  } else if (n == "slam_fused_big") { // a level.  1 (and above): under "slam_fused" = 3 a SLAM batch whose longest track holds 127 .. 232 observations takes the block-row shapes k_slam_y_big<false> / <true> (k_slam_y_big.h) on the long shape's terms; default 0; reads back the level; takes effect with the next ovgpu_set_features
+    if (old_value) *old_value = c->slam_fused_big;
+    if (value >= 0) c->slam_fused_big = (int)std::min<int64_t>(value, 1);
   } else if (n == "slam_fused_batches") { // reads the count of batch pipelines that took k_slam_y, once per update (the pipelines of a repeated attempt — Householder route, step-wise Cholesky — are not counted); a value >= 0 sets it
     if (old_value) *old_value = c->slam_fused_batches;
     if (value >= 0) c->slam_fused_batches = value;

@@ -84,7 +84,11 @@ static FeatLaunch select_feat_kernel(const ovgpu_ctx *c, const SysParams &p, int
     // Everything else — the Householder repeat and the other routes without L, the delayed initialisation, a batch it does not hold — keeps k_system_t.
     const bool lng = pl.slam >= FK_SLAMY_LONG, proj = pl.slam == FK_SLAMY_PROJ || pl.slam == FK_SLAMY_LONG_PROJ;
     s.code = s.kernel = pl.slam;
-    need = slamy::slamy_lds_layout(p.m_max, proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total, s.lds = pl.slam_lds;
+    if (pl.slam >= FK_SLAMY_BIG) { // block row by block row (k_slam_y_big.h): the carve of the tile rows the batch was laid out for
+      const int nt = (2 * p.m_max + 15) / 16;
+      need = nt <= pl.slam_nt ? slamy::slamyb_lds_layout(pl.slam_nt, pl.slam == FK_SLAMY_BIG_PROJ).total : limit + 1;
+    } else need = slamy::slamy_lds_layout(p.m_max, proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total;
+    s.lds = pl.slam_lds;
     s.grid = std::max(1, std::min(F, c->num_cu));
     s.err = OVGPU_ERR_INVALID, s.msg = "internal: k_slam_y was selected for a batch it does not hold";
   } else {
@@ -114,6 +118,21 @@ static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams
     case feat_key(FK_SLAMY_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true>>(c)), grid, slam_block, s.lds, c->stream, p); break;
     case feat_key(FK_SLAMY_LONG): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
     case feat_key(FK_SLAMY_LONG_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
+    case feat_key(FK_SLAMY_BIG):
+    case feat_key(FK_SLAMY_BIG_PROJ): { // the records kernel in front on the same stream, a workgroup per feature slot of the launch's range
+      const slamy::SlamYBigStore st{c->slyb_rows.p, c->slyb_minfo.p, c->slyb_V.p, c->slyb_hq.p, c->slyb_inst.p};
+      const dim3 rgrid(std::max(1, p.f_end - p.f_begin));
+      const size_t rlds = slamy::slamyb_rows_lds(p.m_max);
+      const int snt = c->plan.slam_nt;
+      if (s.kernel == FK_SLAMY_BIG) {
+        hipLaunchKernelGGL(slamy::k_slam_rows_big<false>, rgrid, dim3(256), rlds, c->stream, p, st);
+        hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y_big<false>>(c)), grid, slam_block, s.lds, c->stream, p, snt, st, bws);
+      } else {
+        hipLaunchKernelGGL(slamy::k_slam_rows_big<true>, rgrid, dim3(256), rlds, c->stream, p, st);
+        hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y_big<true>>(c)), grid, slam_block, s.lds, c->stream, p, snt, st, bws);
+      }
+      break;
+    }
     default: return set_err(OVGPU_ERR_INVALID, "internal: the per-feature stage has no kernel in the shape selected");
   }
   HIPCHK(hipGetLastError());

@@ -568,7 +568,10 @@ static FeatPlan plan_feature_stage(const ovgpu_ctx *c, const Batch &b) {
   // again once they are (slam_prepare).  Per-feature sigma / multiplier do not disqualify (ArUco corners).
   // Level 3 is level 2 with one addition: a batch whose longest track holds 63 .. 126 observations takes the long shape (16 tile rows, column
   // blocks of 32) on the same terms and its own carve; a batch of at most 62 takes the shapes of level 2.
-  const int slamy_mmax = c->slam_fused >= 3 ? slamy::SLY_MMAX_L : slamy::SLY_MMAX;
+  // "slam_fused_big" (a level of its own, acts at level 3 only): a batch whose longest track holds 127 .. SLY_MMAX_B observations takes the
+  // block-row shape (k_slam_y_big.h) on the long shape's terms and its own carve; SLY_MMAX_B + 1 observations keep the general kernel.
+  const bool big_on = c->slam_fused >= 3 && c->slam_fused_big;
+  const int slamy_mmax = big_on ? slamy::SLY_MMAX_B : (c->slam_fused >= 3 ? slamy::SLY_MMAX_L : slamy::SLY_MMAX);
   if (c->slam_rows && c->slam_fused && !c->no_feat_kernel && c->L > 0 && m_max <= slamy_mmax && c->D >= 16 && c->K * c->C <= 8192) {
     const int udof = lm_uniform_dof(c);
     bool dof3 = udof == 3, named = udof != 0;
@@ -577,9 +580,15 @@ static FeatPlan plan_feature_stage(const ovgpu_ctx *c, const Batch &b) {
       for (int f = 0; f < F; f++) dof3 = dof3 && lm_dof(c->h_lm_rep[b.h_feat_lm[f]]) == 3;
     }
     const bool proj = named && !dof3 && c->slam_fused >= 2;
-    const bool lng = m_max > slamy::SLY_MMAX;
-    const size_t lds = slamy::slamy_lds_layout(m1, proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total;
-    if ((dof3 || proj) && lds <= limit) pl.slam = FeatKernel((lng ? FK_SLAMY_LONG : FK_SLAMY) + (proj ? 1 : 0)), pl.slam_lds = lds;
+    const bool lng = m_max > slamy::SLY_MMAX, big = m_max > slamy::SLY_MMAX_L;
+    if (big) {
+      const int nt = (2 * m_max + 15) / 16;
+      if ((dof3 || proj) && slamy::slamyb_holds(m_max, proj, limit))
+        pl.slam = proj ? FK_SLAMY_BIG_PROJ : FK_SLAMY_BIG, pl.slam_lds = slamy::slamyb_lds_layout(nt, proj).total, pl.slam_nt = nt;
+    } else {
+      const size_t lds = slamy::slamy_lds_layout(m1, proj, lng ? slamy::SLY_CB_L : slamy::SLY_CB).total;
+      if ((dof3 || proj) && lds <= limit) pl.slam = FeatKernel((lng ? FK_SLAMY_LONG : FK_SLAMY) + (proj ? 1 : 0)), pl.slam_lds = lds;
+    }
   }
   return pl;
 }
@@ -595,6 +604,15 @@ static int size_feature_stage(ovgpu_ctx *c) {
   if (pl.rows_global) HIPCHK(c->sys_rows_ws.reserve((size_t)pl.sys_grid * m1 * c->row_stride));
   if (pl.gate_ws_stride) HIPCHK(c->gate_ws.reserve((size_t)pl.gate_ws_stride * pl.sys_grid));
   if (pl.msckf == FK_FEATY_BIG) HIPCHK(c->featyb_ws.reserve((size_t)std::max(1, std::min(F, c->num_cu)) * feat::featyb_ws_doubles(pl.nt)));
+  if (pl.slam >= FK_SLAMY_BIG) { // k_slam_y_big.h: the row panels' scratch and what its records kernel leaves for it
+    const size_t M = std::max(b.M, 1), Fs = std::max(F, 1);
+    HIPCHK(c->featyb_ws.reserve((size_t)std::max(1, std::min(F, c->num_cu)) * feat::featyb_ws_doubles(pl.slam_nt)));
+    HIPCHK(c->slyb_rows.reserve(M * slamy::SLY_RS));
+    HIPCHK(c->slyb_minfo.reserve(M * 8));
+    HIPCHK(c->slyb_V.reserve(M * 6));
+    HIPCHK(c->slyb_hq.reserve(Fs * 64));
+    HIPCHK(c->slyb_inst.reserve(Fs * slamy::SLY_NT_B * slamy::SLY_ISTR));
+  }
   if (pl.msckf != FK_GENERAL) { // row store of the fast path
     const int M = std::max(b.M, 1);
     HIPCHK(c->fs_tq.reserve((size_t)std::max(F, 1) * 8));

@@ -28,6 +28,7 @@
 #include "k_featy.h"
 #include "k_featy_big.h"
 #include "k_slam_y.h"
+#include "k_slam_y_big.h"
 #include "k_gram.h"
 #include "k_pchol.h"
 #include "k_pchol_wide.h"
@@ -62,6 +63,12 @@ extern template __global__ void k_feat_y_big<8, 17, true>(SysParams, int, const 
 extern template __global__ void k_feat_y_big<8, 5, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
     const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
 } // namespace feat
+namespace slamy { // ... and k_slam_y_big.h's, defined in ovgpu_slamy_big_tu.hip
+extern template __global__ void k_slam_rows_big<false>(SysParams, SlamYBigStore);
+extern template __global__ void k_slam_rows_big<true>(SysParams, SlamYBigStore);
+extern template __global__ void k_slam_y_big<false>(SysParams, int, SlamYBigStore, double *);
+extern template __global__ void k_slam_y_big<true>(SysParams, int, SlamYBigStore, double *);
+} // namespace slamy
 } // namespace ovg
 
 #include "api_context.inc"

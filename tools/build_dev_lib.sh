@@ -6,6 +6,7 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-un
 O=../../tools/_prof
 /opt/rocm/bin/hipcc $F -c ovgpu_api.hip -o $O/dev_api.o &
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-sched-strategy=iterative-ilp -c ovgpu_featy_tu.hip -o $O/dev_featy.o &
+/opt/rocm/bin/hipcc $F -c ovgpu_slamy_big_tu.hip -o $O/dev_slamy_big.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared $O/dev_api.o $O/dev_featy.o -o $O/libovgpu_dev.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared $O/dev_api.o $O/dev_featy.o $O/dev_slamy_big.o -o $O/libovgpu_dev.so
 ls -la $O/libovgpu_dev.so

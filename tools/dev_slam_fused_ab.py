@@ -1,7 +1,7 @@
 """What the fused per-feature kernel of the SLAM update (csrc/k_slam_y.h, ovgpu_debug_option "slam_fused") is worth: the tree's library against
 another build of it on one box.
 
-    time [--reps 30] [--rounds 3] [--lib-a PATH] [--tag NAME] [--tag-a NAME] [--cases slam,chunked] [--state 3dof|mixed|long] [--level-a1 0] [--level-b 1] [--out FILE.jsonl]
+    time [--reps 30] [--rounds 3] [--lib-a PATH] [--tag NAME] [--tag-a NAME] [--cases slam,chunked] [--state 3dof|mixed|long|big] [--level-a N] [--level-a1 0] [--level-b 1] [--big-b 0] [--out FILE.jsonl]
                     leg A runs on the library --lib-a names (the parent commit's build; without it: the tree's with the switch untouched), leg A' on
                     the tree's with "slam_fused" = --level-a1 (0), leg B on the tree's with "slam_fused" = --level-b (1): the switch is a level, an
                     integer.  A leg whose count of fused pipelines ("slam_fused_batches") is not what its level and the state say — some at level 1
@@ -16,10 +16,16 @@ another build of it on one box.
                     library, this one at level 1 — k_system_t, as the parent — and this one at level 2, k_slam_y<true>.
                     --state long is the four-camera rig: 30 clones x 4 cameras, the six representations in turn, every track as the rig sees it, up
                     to 120 observations (D = 303 for a batch of 25).  --level-a1 2 --level-b 3 times the parent's library, this one at level 2 —
-                    k_system_t for every batch whose longest track exceeds 62 — and this one at level 3, the long shapes of k_slam_y.)
+                    k_system_t for every batch whose longest track exceeds 62 — and this one at level 3, the long shapes of k_slam_y.
+                    --state big is BASELINE configs[4]'s rig: 50 clones x 4 cameras, the six representations in turn, every track as the rig sees
+                    it, up to 200 observations (D = 423 for a batch of 25: every leg runs with "gram_wide" = 1, the Gram route for 384 .. 511
+                    columns).  --level-a 3 --level-a1 3 --level-b 3 --big-b 1 times the parent's library at level 3 (--level-a sets "slam_fused" on
+                    leg A too, for a parent that knows the name), this one at level 3 with "slam_fused_big" = 0 — k_system_t for every batch whose
+                    longest track exceeds 126, as the parent — and this one with "slam_fused_big" = 1, the block-row shapes k_slam_y_big
+                    (csrc/k_slam_y_big.h).)
                     The legs take turns frame by frame, `rounds` repetitions of `reps` frames; a row per (case, leg) with the median of every
                     round, the median of those and their spread (max - min), and a summary row: A' against A's spread, A - B against the largest spread.
-    trace [--case slam] [--leg B] [--calls 10] [--lib-a PATH] [--state 3dof|mixed|long] [--level-a1 0] [--level-b 1]
+    trace [--case slam] [--leg B] [--calls 10] [--lib-a PATH] [--state 3dof|mixed|long|big] [--level-a N] [--level-a1 0] [--level-b 1] [--big-b 0]
                     the frames of one leg alone, for a rocprofv3 --kernel-trace --stats run of its own"""
 import argparse
 import ctypes as C
@@ -55,8 +61,9 @@ def bind(capi, path):
 class Leg:
     """one context and its frame: prepare() is not timed, frame() is"""
 
-    def __init__(self, capi, synth, lib, case, kind, fused, state="3dof"):
-        """fused: an integer sets "slam_fused" to that level, None leaves the library alone (another build, which may not know the name)"""
+    def __init__(self, capi, synth, lib, case, kind, fused, state="3dof", big=0):
+        """fused: an integer sets "slam_fused" to that level, None leaves the library alone (another build, which may not know the name);
+        big: a level above 0 sets "slam_fused_big" (leg B only: no other build knows the name)"""
         self.lib, self.kind, self.case, self.ctx = lib, kind, case, C.c_void_p()
         opts = capi.default_options(chi2_multipler=1.0)
         assert lib.ovgpu_create(C.byref(opts), 0, C.byref(self.ctx)) == 0
@@ -66,6 +73,10 @@ class Leg:
             self.expect_fused = fused is not None and fused >= 3
         if fused is not None:
             self.ok(lib.ovgpu_debug_option(self.ctx, b"slam_fused", int(fused), None), "ovgpu_debug_option")
+        if big:
+            self.ok(lib.ovgpu_debug_option(self.ctx, b"slam_fused_big", int(big), None), "ovgpu_debug_option")
+        if state == "big":  # D = 423: the Gram route for 384 .. 511 columns, on every leg
+            self.ok(lib.ovgpu_debug_option(self.ctx, b"gram_wide", 1, None), "ovgpu_debug_option")
         self.ip = lambda a: a.ctypes.data_as(capi.c_int32_p)
         self.dp = lambda a: a.ctypes.data_as(capi.c_double_p)
         L, F = (50, 25) if case == "slam" else (100, 100)
@@ -73,14 +84,18 @@ class Leg:
         reps6 = [capi.REP_GLOBAL_3D, capi.REP_ANCHORED_3D, capi.REP_GLOBAL_3D, capi.REP_ANCHORED_MSCKF_INVERSE_DEPTH, capi.REP_GLOBAL_FULL_INVERSE_DEPTH,
                  capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE]  # DESIGN.md section 7's rows (tools/dev_chol_wide_ab.py, tools/dev_slam_chunked_ab.py)
         reps = np.array((reps5 * ((L + 4) // 5))[:L] if state == "3dof" else (reps6 * ((L + 5) // 6))[:L], np.int32)
-        if state == "long":
+        if state in ("long", "big"):
             reps = np.array((reps6 * ((L + 5) // 6))[:L], np.int32)
-        full = synth.make_slam_problem(2, L=L, lm_rep=reps, seed=3, **(dict(C=30, K=4) if state == "long" else {}))
+        full = synth.make_slam_problem(2, L=L, lm_rep=reps, seed=3, **({"long": dict(C=30, K=4), "big": dict(C=50, K=4)}.get(state, {})))
         prob = full.subset(np.arange(F))
         prob.lm_index = np.ascontiguousarray(np.arange(F), dtype=np.int32)
         self.lm = prob.lm_index
         self.m_max = int(np.diff(prob.meas_offsets).max())
         self.first = np.arange(0, F + 1, 25, dtype=np.int32)
+        if state == "big":  # a pipeline is fused when its batch's longest track is within the bound of the shapes the leg's switches allow
+            lens = np.diff(prob.meas_offsets)
+            bound = 0 if fused is None or fused < 3 else (232 if big else 126)
+            self.expect_fused = any(int(lens[a:b].max()) <= bound for a, b in zip(self.first[:-1], self.first[1:]))
         n = len(self.first) - 1
         self.st, self.x2, self.thr, self.lmo = np.zeros(F, np.int32), np.zeros(F), np.zeros(F), np.zeros((L, 3))
         self.dxs = np.zeros((n, prob.N))
@@ -131,7 +146,7 @@ def make_legs(a, case, which=LEGS):
     import torch  # noqa: F401  (capi.load: torch's HIP runtime first)
     from open_vins_amd import capi, synth
     lib, lib_a = capi.load(), bind(capi, a.lib_a)
-    return {k: Leg(capi, synth, lib_a if k == "A" else lib, case, k, fused={"A": None, "A'": a.level_a1, "B": a.level_b}[k], state=a.state) for k in which}
+    return {k: Leg(capi, synth, lib_a if k == "A" else lib, case, k, fused={"A": a.level_a, "A'": a.level_a1, "B": a.level_b}[k], state=a.state, big=(a.big_b if k == "B" else 0)) for k in which}
 
 
 def spread(v):
@@ -160,7 +175,7 @@ def timed(a):
         if any((counts[k] > 0) != leg.expect_fused for k, leg in legs.items()):
             raise RuntimeError(f"case {case}: fused pipelines per leg {counts} — nothing was compared")
         for k, leg in legs.items():
-            row = dict(case=case, state=a.state, m_max=leg.m_max, leg=k, level=({"A": None, "A'": a.level_a1, "B": a.level_b}[k]), D=leg.D, build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k],
+            row = dict(case=case, state=a.state, m_max=leg.m_max, leg=k, level=({"A": a.level_a, "A'": a.level_a1, "B": a.level_b}[k]), big=(a.big_b if k == "B" else 0), D=leg.D, build=(a.tag_a if k == "A" else a.tag), reps=a.reps, ms_round_medians=med[k],
                        ms_median=float(np.median(med[k])), ms_spread=spread(med[k]), fused_pipelines=counts[k])
             if case == "slam":
                 row["ms_total_device"], row["n_used"] = float(leg.stats.ms_total), int(leg.stats.n_used)
@@ -213,7 +228,9 @@ def main():
     r.add_argument("--calls", type=int, default=10)
     r.add_argument("--lib-a", default=None)
     for q in (t, r):
-        q.add_argument("--state", choices=("3dof", "mixed", "long"), default="3dof")
+        q.add_argument("--state", choices=("3dof", "mixed", "long", "big"), default="3dof")
+        q.add_argument("--level-a", type=int, default=None)
+        q.add_argument("--big-b", type=int, default=0)
         q.add_argument("--level-a1", type=int, default=0)
         q.add_argument("--level-b", type=int, default=1)
     a = ap.parse_args()
