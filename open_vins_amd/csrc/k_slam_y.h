@@ -92,6 +92,31 @@ __host__ __device__ inline SlamYLds slamy_lds_layout(int m_max, bool proj = fals
   return L;
 }
 
+// ------------------------------------------------------------------ shared with the block-row shape (k_slam_y_big.h); each leaves its callers' code as it was
+// representation Jacobian by ONE thread, as k_system_t (UpdaterHelper.cpp:32-190): hq[12..20] dpfg_dlambda, [21..38] H_anc, [39..56] H_calib
+// (k_slam_y, k_slam_rows_big)
+__device__ __forceinline__ void slamy_rep_jacobian(const SysParams &p, int f, int rep_f, int anchor_cam, int anchor_clone, const V3 &p_FinG, const V3 &p_FinG_fej,
+                                                   double *hq) {
+  double *dl = hq + 12;
+  if (rep_f == OVGPU_REP_GLOBAL_3D) {
+    dl[0] = 1, dl[1] = 0, dl[2] = 0, dl[3] = 0, dl[4] = 1, dl[5] = 0, dl[6] = 0, dl[7] = 0, dl[8] = 1;
+  } else if (rep_f == OVGPU_REP_GLOBAL_FULL_INVERSE_DEPTH) {
+    inv_depth_jac(p.opt.do_fej ? p_FinG_fej : p_FinG, dl); // UpdaterHelper.cpp:46
+  } else {
+    anchored_rep_jacobian(rep_f, p.opt.do_fej, p.tab_cam + 12 * anchor_cam, p.tab_clone + 24 * anchor_clone, load_v3(p.p_FinA + 3 * f), dl, hq + 21, hq + 39);
+  }
+}
+// the gate's verdict by ONE thread: k_system_t's outputs for the statistic chi2 of a feature of n rows that gives the stack n_out (k_slam_y, k_slam_y_big)
+__device__ __forceinline__ void slamy_verdict(const SysParams &p, int f, double mult_f, bool single, int n, int n_out, double chi2, int *reject_slot) {
+  const double thr = mult_f * p.chi2_table[min(single ? n - 2 : n, p.chi2_table_len - 1)]; // UpdaterSLAM.cpp:392-405: dof = 2m (2m - 2 behind the projection)
+  p.chi2[f] = chi2;
+  p.chi2_thresh[f] = thr;
+  const bool reject = chi2 > thr;
+  *reject_slot = reject ? 1 : 0;
+  if (reject) p.status[f] = OVGPU_FEAT_CHI2_REJECTED;
+  else if (p.rows_used) atomicAdd(p.rows_used, n_out);
+}
+
 #ifndef OVG_TU_FEATY
 // PROJ ("with projection"): a feature whose landmark is ANCHORED_INVERSE_DEPTH_SINGLE has its two bearing columns H_b = H_f[:, 0:2] projected out
 // (UpdaterSLAM.cpp:338-341, :371-379; k_system_t's nproj == 2): the records are those of ANCHORED_MSCKF_INVERSE_DEPTH, the landmark's instance is
@@ -169,16 +194,7 @@ template <bool PROJ, int TPW = SLY_TPW, int CB = SLY_CB, int MMAX = SLY_MMAX> __
       p_FinG = mulT(R_GtoI, mulT(R_ItoC, p_FinA - p_IinC)) + p_IinG; // UpdaterHelper.cpp:274
       p_FinG_fej = p_FinG;                                           // :279-283: the "best" estimate
     }
-    if (tid == 0) {
-      double *dl = hq + 12;
-      if (rep_f == OVGPU_REP_GLOBAL_3D) {
-        dl[0] = 1, dl[1] = 0, dl[2] = 0, dl[3] = 0, dl[4] = 1, dl[5] = 0, dl[6] = 0, dl[7] = 0, dl[8] = 1;
-      } else if (rep_f == OVGPU_REP_GLOBAL_FULL_INVERSE_DEPTH) {
-        inv_depth_jac(p.opt.do_fej ? p_FinG_fej : p_FinG, dl); // UpdaterHelper.cpp:46
-      } else {
-        anchored_rep_jacobian(rep_f, p.opt.do_fej, p.tab_cam + 12 * anchor_cam, p.tab_clone + 24 * anchor_clone, load_v3(p.p_FinA + 3 * f), dl, hq + 21, hq + 39);
-      }
-    }
+    if (tid == 0) slamy_rep_jacobian(p, f, rep_f, anchor_cam, anchor_clone, p_FinG, p_FinG_fej, hq);
     __syncthreads();
     // ------------------------------------------------------------------ (a) the records (UpdaterHelper.cpp:314-421)
     for (int i = tid; i < m; i += NTH) sys_measurement_rows(p, m0 + i, p_FinG, p_FinG_fej, relative, hq, minfo + 8 * i, rows + (size_t)i * RS);
@@ -400,15 +416,7 @@ template <bool PROJ, int TPW = SLY_TPW, int CB = SLY_CB, int MMAX = SLY_MMAX> __
       }
     }
     const double chi2 = feat::gate_ldl_chi2<NW, TPW, PROJ ? 2 : 1>(acc, tij, NT, NTA, n, panel, panelx, st0, stE, stF, chi2_slot, lane, wv, single);
-    if (tid == 0) {
-      const double thr = mult_f * p.chi2_table[min(single ? n - 2 : n, p.chi2_table_len - 1)]; // UpdaterSLAM.cpp:392-405: dof = 2m (2m - 2 behind the projection)
-      p.chi2[f] = chi2;
-      p.chi2_thresh[f] = thr;
-      const bool reject = chi2 > thr;
-      *reject_slot = reject ? 1 : 0;
-      if (reject) p.status[f] = OVGPU_FEAT_CHI2_REJECTED;
-      else if (p.rows_used) atomicAdd(p.rows_used, n_out);
-    }
+    if (tid == 0) slamy_verdict(p, f, mult_f, single, n, n_out, chi2, reject_slot);
     __syncthreads(); // (a full barrier: the other wavefronts' stores to the feature's rows have landed)
     if (*reject_slot)
       for (int64_t e = tid; e < (int64_t)n_out * LD; e += NTH) out[e] = 0.0;

@@ -115,16 +115,7 @@ template <bool PROJ> __global__ void __launch_bounds__(256) k_slam_rows_big(SysP
     p_FinG = mulT(R_GtoI, mulT(R_ItoC, p_FinA - p_IinC)) + p_IinG;
     p_FinG_fej = p_FinG;
   }
-  if (tid == 0) {
-    double *dl = hq + 12;
-    if (rep_f == OVGPU_REP_GLOBAL_3D) {
-      dl[0] = 1, dl[1] = 0, dl[2] = 0, dl[3] = 0, dl[4] = 1, dl[5] = 0, dl[6] = 0, dl[7] = 0, dl[8] = 1;
-    } else if (rep_f == OVGPU_REP_GLOBAL_FULL_INVERSE_DEPTH) {
-      inv_depth_jac(p.opt.do_fej ? p_FinG_fej : p_FinG, dl);
-    } else {
-      anchored_rep_jacobian(rep_f, p.opt.do_fej, p.tab_cam + 12 * anchor_cam, p.tab_clone + 24 * anchor_clone, load_v3(p.p_FinA + 3 * f), dl, hq + 21, hq + 39);
-    }
-  }
+  if (tid == 0) slamy_rep_jacobian(p, f, rep_f, anchor_cam, anchor_clone, p_FinG, p_FinG_fej, hq);
   __syncthreads();
   // ------------------------------------------------------------------ the records (UpdaterHelper.cpp:314-421) -> memory; H_f, r and the block columns -> LDS
   for (int i = tid; i < m; i += NTH) {
@@ -541,15 +532,7 @@ template <bool PROJ> __global__ void __launch_bounds__(64 * SLY_NW, 1) k_slam_y_
         const double l10 = G01 / G00, d1 = G11 - l10 * G01, x1 = g1 - l10 * g0;
         chi2 = sa - (g0 * g0 / G00 + x1 * x1 / d1);
       }
-      if (lane == 0) {
-        const double thr = mult_f * p.chi2_table[min(single ? n - 2 : n, p.chi2_table_len - 1)]; // UpdaterSLAM.cpp:392-405: dof = 2m (2m - 2 behind the projection)
-        p.chi2[f] = chi2;
-        p.chi2_thresh[f] = thr;
-        const bool reject = chi2 > thr;
-        *reject_slot = reject ? 1 : 0;
-        if (reject) p.status[f] = OVGPU_FEAT_CHI2_REJECTED;
-        else if (p.rows_used) atomicAdd(p.rows_used, n_out);
-      }
+      if (lane == 0) slamy_verdict(p, f, mult_f, single, n, n_out, chi2, reject_slot);
     }
     __syncthreads(); // (the pass loop ended with a full barrier: the rows' stores have landed)
     if (*reject_slot)

@@ -5,16 +5,19 @@ in the tree and stores every output; `compare <a.npz> <b.npz>` compares two such
 nothing but instruction ORDER (a scheduler strategy, ovgpu_featy_tu.hip): no tolerance applies, and no oracle time is spent
 (tools/gpu_bitcompare.sh swaps the library files on one box).  `dump` also runs the entries that read the resident feature batch on
 small seeded landmark states (batch_scenarios below): used when a change is meant to touch host code only.  `fused <out.npz> <level>` runs
-SLAM updates with ovgpu_debug_option "slam_fused" at that level (fused_scenarios below): two builds must agree bit for bit at a level both know.
+SLAM updates with ovgpu_debug_option "slam_fused" at that level (fused_scenarios below): two builds must agree bit for bit at a level both know;
+`fused <out.npz> <level> <big>` also sets "slam_fused_big" and adds the batches only the block-row shapes k_slam_y_big hold.
 `init <out.npz> <level>` runs the delayed-initialisation scenarios with "delayed_init_fused" at that level (init_scenarios below), likewise.
 `wide <out.npz> [level]` runs updates of 384 .. 511 Jacobian columns (wide_scenarios below), with "gram_wide" at that level when one is given: without
 one the name is left alone, and a build that knows the switch must agree bit for bit with one that does not.
 `--lib PATH` behind any of the above runs it on that build of the library instead of the tree's."""
+import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
 
 def shapes():
@@ -141,27 +144,50 @@ def batch_scenarios(out):
     print("batch scenarios:", len(out) - n0, "arrays", flush=True)
 
 
-def fused_scenarios(path, level):
+def fused_scenarios(path, level, big=None):
     """ovgpu_slam_update and ovgpu_slam_update_chunked with "slam_fused" = level: fifteen landmarks of the five 3-dof representations (every batch
     takes k_slam_y<false> from level 1 on), and twelve of all six (k_system_t at level 1, k_slam_y<true> at level 2); on the four-camera rig (30 clones,
     tracks of up to 120 observations) ten of the 3-dof representations and twelve of all six: k_system_t up to level 2, the long shapes of k_slam_y
-    (kernels 6 and 7) at level 3."""
+    (kernels 6 and 7) at level 3.  With `big` ("slam_fused_big", set on every context): also the six-landmark batch of tests/slam_big_shapes.py with tracks
+    of 209, 169 and 121 observations — four, three and two passes of the block-row plan — and three short ones, on 3-dof landmarks (kernel 8) and with
+    the longest track on a single-depth landmark (kernel 9)."""
     from open_vins_amd import capi, synth
     from open_vins_amd.updater import UpdaterMSCKF
     opts = capi.default_options(chi2_multipler=1.0)
     out = {}
+
+    def context(o):
+        u = UpdaterMSCKF(o, device=0)
+        u.debug_option("slam_fused", level)
+        if big is not None:
+            u.debug_option("slam_fused_big", big)
+        return u
+
     for tag, reps, rig in (("3dof", (0, 1, 2, 3, 4) * 3, {}), ("six", REPS6 * 2, {}), ("long_3dof", (0, 1, 2, 3, 4) * 2, dict(C=30, K=4)), ("long_six", REPS6 * 2, dict(C=30, K=4))):
         p = synth.make_slam_problem(2, L=len(reps), lm_rep=np.array(reps, np.int32), seed=3, **rig)
         assert not rig or int(np.diff(p.meas_offsets).max()) >= 63, "the long state holds no track of 63 observations"
         for entry in ("update", "chunked"):
-            up = UpdaterMSCKF(opts, device=0)
-            up.debug_option("slam_fused", level)
+            up = context(opts)
             up.set_slam_problem(p)
             res = up.slam_update() if entry == "update" else up.slam_update_chunked(p.lm_index, [0, 5, 5, p.F])
             res.update(up.get_state(P=False))
             res["kernel"], res["fused_batches"] = up.debug_option("last_feature_kernel"), up.debug_option("slam_fused_batches")
             put(out, f"{tag}.{entry}", res)
             print(tag, entry, "level", level, "kernel", res["kernel"], "fused pipelines", res["fused_batches"], flush=True)
+            up.close()
+    if big is not None:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import slam_big_shapes as sb
+        for kind in ("3dof", "single"):
+            p = sb.rig_batch(kind, (209, 169, 121, 12, 9, 3), None)
+            assert [sb.n_passes(int(m)) for m in np.diff(p.meas_offsets)[:3]] == [4, 3, 2]
+            up = context(capi.default_options(chi2_multipler=1.0, **sb.RIG_A_OPTS))
+            up.set_slam_problem(p)
+            res = up.slam_update()
+            res.update(up.get_state(P=False))
+            res["kernel"], res["fused_batches"] = up.debug_option("last_feature_kernel"), up.debug_option("slam_fused_batches")
+            put(out, f"big_{kind}.update", res)
+            print("big", kind, "level", level, "big", big, "kernel", res["kernel"], "fused pipelines", res["fused_batches"], flush=True)
             up.close()
     np.savez(path, **out)
 
@@ -333,7 +359,6 @@ def compare(a, b):
 
 if __name__ == "__main__":
     if "--lib" in sys.argv:  # another build of the library (the parent commit's): every scenario above loads it through capi.load()
-        import os
         from open_vins_amd import capi
         at = sys.argv.index("--lib")
         capi.LIB_PATH = os.path.abspath(sys.argv[at + 1])
@@ -341,7 +366,7 @@ if __name__ == "__main__":
     if sys.argv[1] == "prepare":
         prepare(sys.argv[2])
     elif sys.argv[1] == "fused":
-        fused_scenarios(sys.argv[2], int(sys.argv[3]))
+        fused_scenarios(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]) if len(sys.argv) > 4 else None)
     elif sys.argv[1] == "init":
         init_scenarios(sys.argv[2], int(sys.argv[3]))
     elif sys.argv[1] == "wide":
