@@ -496,7 +496,7 @@ int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, do
  *                 D = 352 .. 367 (NT = 23): k_gram_wide, two passes; D = 256 .. 351 and 368 .. 383: k_gram_blk, 8 x 8-tile blocks
  *   factor        D <= 127 (NT <= 8): k_gram_pchol_blk<4, 9, 2>; D = 128 .. 223 (NT <= 14): k_gram_pchol_blk<7, 15, 4>;
  *                 D = 224 .. 383: the rank-one k_gram_pchol<NB>, NB = ceil(LD / 32) = 8 .. 12 ("pchol_blocked" = 0: for every
- *                 D, NB = 1 .. 12)
+ *                 D, NB = 1 .. 12), unless "mode_a_panel" is in force (below)
  *   un-whitening  D <= 256 and the prior block factored in one launch: k_unwhiten_blk<16>; D <= 256 otherwise
  *                 (options.no_single_launch_cholesky, "unwhiten_blocked" = 0): k_unwhiten<16>; D = 257 .. 383: k_unwhiten<24>
  *   D >= 384      none of them: the Householder triangle, rows = D, OVGPU_COMPRESS_TSQR — unless ovgpu_debug_option "mode_a_wide" = 1
@@ -510,7 +510,12 @@ int ovgpu_msckf_update_lm(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2, do
  *   un-whitening  (ovgpu_slam_compress under "slam_mode_a") D = 257 .. 383: k_unwhiten_blk<24>, the blocked form with six accumulator tiles per
  *                 wavefront, on the inverse diagonal tiles of the prior block's two-panel factorisation ("last_unwhiten_kernel" 6), or on
  *                 k_uinv_tiles' when that factorisation ran step-wise (options.no_single_launch_cholesky, "chol_wide" = 0) or
- *                 "unwhiten_blocked" is 0 (7).  ovgpu_msckf_compress keeps k_unwhiten<24> (3) there.
+ *                 "unwhiten_blocked" is 0 (7).  ovgpu_msckf_compress keeps k_unwhiten<24> (3) there, unless "mode_a_panel" is in force.
+ *   factor        (either entry under ovgpu_debug_option "mode_a_panel" = 1) D = 256 .. 383 (NT = 17 .. 24; the lower edge is one constant
+ *                 of the library, MODE_A_PANEL_MIN_NT = 17 tile columns: at 15 and 16 the rank-one k_gram_pchol<8> measured no slower):
+ *                 k_pchol_panel (32 pivots per launch) around k_pchol_schur ("last_factor_kernel" 3).  Under the switch
+ *                 ovgpu_msckf_compress takes ovgpu_slam_compress's un-whitening at D = 257 .. 383 (6 / 7).  Every other width keeps
+ *                 its kernels.
  * A batch whose every feature is rejected returns rows = 0 and OVGPU_OK. */
 int ovgpu_msckf_compress(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2,
                          double *chi2_thresh, double *p_FinG, int32_t *D_out,
@@ -674,7 +679,8 @@ int ovgpu_slam_update_chunked(ovgpu_ctx *ctx, int32_t n_chunks, const int32_t *c
  * OVGPU_COMPRESS_TSQR.  With ovgpu_debug_option "slam_mode_a" = 1, set after ovgpu_create, the
  * entry takes the pivoted Gram route on the terms ovgpu_msckf_compress does (the rule there): a
  * float64 context on OVGPU_COMPRESS_GRAM with the whitened stack, D <= 383 (D <= 511 when
- * "mode_a_wide" = 1 is in force as well) and a prior block that factors.  rows = the numerical
+ * "mode_a_wide" = 1 is in force as well) and a prior block that factors ("mode_a_panel" picks
+ * the factor kernel at D = 256 .. 383 for this entry as well).  rows = the numerical
  * rank, at most the rows of the stack plus noise rows; ovgpu_last_update_route reports
  * OVGPU_COMPRESS_PCHOLQR.  The per-feature stage is then the one ovgpu_slam_update runs:
  * k_slam_y for a batch laid out under "slam_fused" ("last_feature_kernel" 4 / 5 / 6 / 7), the
@@ -1288,6 +1294,18 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             is resident keeps the level it was handed over under
  *   "slam_mode_a_compressions" (read only) number of SLAM compressions that took the pivoted route and stand: an attempt the library repeats
  *                             through the Householder route is not counted
+ *   "mode_a_panel"            (default 0) a level; the read-back returns it (values above 1 are taken as 1).  Independent of "mode_a_wide" and
+ *                             "slam_mode_a".  Where a compression takes the pivoted Gram route anyway (ovgpu_msckf_compress on a float64 context
+ *                             with the whitened stack whose compress_route is not OVGPU_COMPRESS_TSQR and whose prior block factors;
+ *                             ovgpu_slam_compress on the same terms with "slam_mode_a" in force) and D = 256 .. 383 (17 .. 24 tile columns of
+ *                             [H | r]), 1: the factor is k_pchol_panel / k_pchol_schur instead of the rank-one k_gram_pchol<9 .. 12>, and
+ *                             ovgpu_msckf_compress un-whitens D = 257 .. 383 with k_unwhiten_blk<24>.  0, or
+ *                             never named: every entry enqueues what it did before and returns those bits.  Whatever the level: every other
+ *                             width, route and entry keeps its kernels and its bits.  A prior block that does not factor repeats the call
+ *                             through the Householder route with the bits of a context that never named the switch.  Takes effect where
+ *                             "mode_a_wide" does: with the next ovgpu_set_state / ovgpu_set_features, and at no other call
+ *   "mode_a_panel_compressions" (read only) number of compressions that took the panelled factor at 256 .. 383 columns and stand: an attempt
+ *                             the library repeats through the Householder route is not counted
  *   "tsqr_leaves" / "tsqr_rows_per_node" / "tsqr_last_leaf_kernel" / "tsqr_last_tree" / "tsqr_last_qh"  (read only) what the last Householder
  *                             compression launched, stand-alone (ovgpu_measurement_compress, ovgpu_ekf_update) or on the update route: the number
  *                             of leaves W; the rows per leaf; the leaf kernel (0 the panel-wave kernel of k_tsqr_pw.h, 1 k_qr_node of k_tsqr.h,
@@ -1340,7 +1358,7 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             k_gram_pchol<NB>); mode A's un-whitening (0 none, 1 k_unwhiten_blk<16>, 2 k_unwhiten<16>, 3 k_unwhiten<24>, 4 k_unwhiten_blk<32> on
  *                             the two-panel factorisation's inverse tiles, 5 k_unwhiten_blk<32> on k_uinv_tiles', 6 k_unwhiten_blk<24> on the
  *                             two-panel factorisation's inverse tiles, 7 k_unwhiten_blk<24> on k_uinv_tiles' — ovgpu_slam_compress under
- *                             "slam_mode_a"): the rule at ovgpu_msckf_compress
+ *                             "slam_mode_a", ovgpu_msckf_compress under "mode_a_panel"): the rule at ovgpu_msckf_compress
  *   "last_gram_workgroups"    (read only) the row shares of that Gram kernel where it is one of the two that options.gram_fp32 reaches: gridDim.x of the
  *                             last pipeline's k_gram_f32 launch (workgroups per part of the macro-tile triangle: max(1, ceil(rows / 1536),
  *                             min(ceil(2 CUs / parts), ceil(rows / 128)))) or k_gram_blk launch (min(CUs, ceil(rows / 32)); a tenth of the CUs at

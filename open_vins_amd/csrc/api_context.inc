@@ -417,6 +417,9 @@ struct ovgpu_ctx {
   int slam_mode_a = 0;            // ovgpu_debug_option "slam_mode_a", a level: 0 off; 1 (and above) ovgpu_slam_compress takes mode A's pivoted Gram route on the terms ovgpu_msckf_compress does (factor_gram, enqueue_pipeline_body), the per-feature stage the kernel "slam_fused" lays the batch out for, and at 17 .. 24 tile columns of D the blocked un-whitening k_unwhiten_blk<24>
   int slam_mode_a_on = 0;         // ... the level in force: taken over exactly where mode_a_wide_on is
   int64_t slam_mode_a_compressions = 0; // ovgpu_debug_option "slam_mode_a_compressions": SLAM compressions that took the pivoted route AND stand (compress_impl takes an attempt it repeats through the Householder route off again)
+  int mode_a_panel = 0;           // ovgpu_debug_option "mode_a_panel", a level: 0 off; 1 (and above) mode A's pivoted Gram route factors 17 .. 24 tile columns of [H | r] (D = 256 .. 383) with k_pchol_panel / k_pchol_schur instead of the rank-one k_gram_pchol<NB> (mode_a_panel_factor, api_pipeline.inc), and ovgpu_msckf_compress un-whitens 17 .. 24 tile columns of D with k_unwhiten_blk<24>
+  int mode_a_panel_on = 0;        // ... the level in force: taken over exactly where mode_a_wide_on is
+  int64_t mode_a_panel_compressions = 0; // ovgpu_debug_option "mode_a_panel_compressions": compressions that took the panelled factor at 17 .. 24 tile columns AND stand (compress_impl takes an attempt it repeats through the Householder route off again)
   DevBuf<double> pchol_dots;      // [512 + 8] k_pchol_wide.h: the running diagonal and the first pivot between the panels' launches
   DevBuf<double> uinv_tiles;      // [32][256] k_uinv_tiles: U_JJ^-1 of a prior block that was factored step-wise, for k_unwhiten_blk<32>
   PinBuf<double> h_tri;        // mode A: the compressed system on its way to the caller ([D x LD] + one word of flags per double behind it)

@@ -137,6 +137,11 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (value >= 0) c->mode_a_wide = (int)std::min<int64_t>(value, 1);
   } else if (n == "mode_a_wide_compressions") { // read-only: the count of compressions that took the pivoted route beyond 383 columns and stand (an attempt repeated through the Householder route is not counted)
     if (old_value) *old_value = c->mode_a_wide_compressions;
+  } else if (n == "mode_a_panel") { // a level.  1 (and above): on mode A's pivoted Gram route (ovgpu_msckf_compress; ovgpu_slam_compress under "slam_mode_a") 17 .. 24 tile columns of [H | r] (256 .. 383 Jacobian columns) are factored by k_pchol_panel / k_pchol_schur (k_pchol_wide.h, 32 pivots per launch) instead of the rank-one k_gram_pchol<9 .. 12>, and ovgpu_msckf_compress un-whitens 257 .. 383 columns with k_unwhiten_blk<24>; default 0: the rank-one kernel and k_unwhiten<24>; reads back the level; takes effect with the next ovgpu_set_state / ovgpu_set_features
+    if (old_value) *old_value = c->mode_a_panel;
+    if (value >= 0) c->mode_a_panel = (int)std::min<int64_t>(value, 1);
+  } else if (n == "mode_a_panel_compressions") { // read-only: the count of compressions that took the panelled factor at 256 .. 383 columns and stand (an attempt repeated through the Householder route is not counted)
+    if (old_value) *old_value = c->mode_a_panel_compressions;
   } else if (n == "slam_mode_a") { // a level.  1 (and above): ovgpu_slam_compress takes the pivoted Gram route on the terms ovgpu_msckf_compress does (a float64 context on OVGPU_COMPRESS_GRAM, the whitened stack, D <= 383, or 511 with "mode_a_wide" = 1 as well), its per-feature stage the kernel "slam_fused" lays the batch out for, its un-whitening at D = 257 .. 383 k_unwhiten_blk<24>; default 0: the Householder triangle; reads back the level; takes effect with the next ovgpu_set_state / ovgpu_set_features
     if (old_value) *old_value = c->slam_mode_a;
     if (value >= 0) c->slam_mode_a = (int)std::min<int64_t>(value, 1);

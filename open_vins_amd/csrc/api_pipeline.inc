@@ -357,6 +357,13 @@ static int gram_route_tile_cap(const ovgpu_ctx *c) { return c->gram_wide_on >= 1
 // ... and for mode A's pivoted factor (factor_gram, enqueue_pipeline_body): 32 under ovgpu_debug_option "mode_a_wide" on a float64 context with the
 // whitened stack (k_pchol_wide.h, k_unwhiten_blk<32>), 24 otherwise.  The two switches are independent of each other.
 static int mode_a_tile_cap(const ovgpu_ctx *c) { return c->mode_a_wide_on >= 1 && c->whiten && !c->gram_fp32 ? gram::GR_NT_WIDE : gram::GR_NT_BLK; }
+// ... and the lower edge, in tile columns of [H | r], of the panelled pivoted factor under ovgpu_debug_option "mode_a_panel" (include/ovgpu.h names it at
+// ovgpu_msckf_compress): from here to gram::GR_NT_BLK the switch sends the factor to k_pchol_panel / k_pchol_schur instead of the rank-one k_gram_pchol<NB>.
+// Measured (DESIGN.md section 7): at 15 and 16 tile columns the rank-one k_gram_pchol<8> — no spills at eight blocks — is as fast as seven or eight panels with
+// their launch boundaries, so the edge sits at 17, where the Gram kernel, the prior's factorisation and the un-whitening change as well.
+constexpr int MODE_A_PANEL_MIN_NT = 17; // D = 256
+// Mode A's factor comes here on a float64 context with the whitened stack only (factor_gram, enqueue_pipeline_body), so the level and the width decide.
+static bool mode_a_panel_factor(const ovgpu_ctx *c, int NTf) { return c->mode_a_panel_on >= 1 && NTf >= MODE_A_PANEL_MIN_NT && NTf <= gram::GR_NT_BLK; }
 static int enqueue_compress_gram(ovgpu_ctx *c, bool factor = true) {
   const int D = c->D, LD = c->LD, NT = (LD + 15) / 16, NP = NT * (NT + 1) / 2, LG = 16 * NT;
   const int64_t rows_total = batch_of(c).rows_total;
@@ -453,7 +460,9 @@ static int enqueue_gram_factor(ovgpu_ctx *c) {
   // pivots, the pivot-by-pivot work in one wavefront (k_pchol.h); up to 14 tile columns (223 Jacobian columns: configs[0..2]).  Beyond — 17 tiles
   // per wavefront in nine wavefronts' 168 registers — the kernel spills, and the rank-one kernel stays.
   const int NTf = (LD + 15) / 16;
-  if (NTf > gram::GR_NT_BLK) { // 25 .. 32 tile columns ("mode_a_wide"): panels of 32 pivots around Schur steps, in place on c->gram_G (k_pchol_wide.h)
+  // 25 .. 32 tile columns ("mode_a_wide"): panels of 32 pivots around Schur steps, in place on c->gram_G (k_pchol_wide.h); under "mode_a_panel" 17 .. 24
+  // tile columns as well (both kernels are generic in LG, and every Gram reduction of this route writes the full symmetric square)
+  if (NTf > gram::GR_NT_BLK || mode_a_panel_factor(c, NTf)) {
     if (NTf > gram::GR_NT_WIDE) return set_err(OVGPU_ERR_CAPACITY, "the pivoted Gram factor holds at most 511 Jacobian columns");
     HIPCHK(c->pchol_dots.reserve((size_t)gram::PW_LGMAX + 8));
     gram::PcholWideParams q;
@@ -912,7 +921,8 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
         const bool wide = NTd > gram::GR_NT_BLK || (c->LD + 15) / 16 > gram::GR_NT_BLK; // "mode_a_wide": 384 .. 511 columns, eight accumulator slots per wavefront
         // "slam_mode_a": the SLAM entry at 17 .. 24 tile columns of D (257 .. 383 columns, where a state with landmarks sits) takes the blocked form
         // as well, six accumulator slots per wavefront; ovgpu_msckf_compress keeps k_unwhiten<24> there
-        const bool mid = !wide && NTd > 16 && slam && c->slam_mode_a_on >= 1;
+        // "mode_a_panel": so does ovgpu_msckf_compress
+        const bool mid = !wide && NTd > 16 && ((slam && c->slam_mode_a_on >= 1) || c->mode_a_panel_on >= 1);
         bool own_tiles = false;
         if (wide || mid) {
           const double *tiles = c->unwhiten_blocked ? c->prior_uinv : nullptr;
@@ -942,6 +952,7 @@ static int enqueue_pipeline_body(ovgpu_ctx *c, int stages, bool slam, bool facto
         else if (mid) c->last_unwhiten_kernel = own_tiles ? 7 : 6;
         else c->last_unwhiten_kernel = NTd > 16 ? 3 : (c->unwhiten_blocked && c->prior_uinv ? 1 : 2);
         if (slam) c->slam_mode_a_compressions++;
+        if (mode_a_panel_factor(c, (c->LD + 15) / 16)) c->mode_a_panel_compressions++;
       }
     } else {
       rc = enqueue_compress(c);
@@ -1289,7 +1300,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
   int rc;
   const double *tri = nullptr;
   int32_t dropped = 0;
-  const int64_t wide0 = c->mode_a_wide_compressions, slam0 = c->slam_mode_a_compressions, fused0 = c->slam_fused_batches;
+  const int64_t wide0 = c->mode_a_wide_compressions, slam0 = c->slam_mode_a_compressions, fused0 = c->slam_fused_batches, panel0 = c->mode_a_panel_compressions;
   for (int attempt = 0;; attempt++) {
     c->factor_from_gram = attempt == 0; // the whitened Gram matrix's factor (pivoted by default) where it applies; Householder TSQR otherwise
     if ((rc = enqueue_pipeline(c, STAGE_LOCAL, slam)) != OVGPU_OK) return rc;
@@ -1312,7 +1323,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
     // the prior block is not (numerically) positive definite, or its single-launch factorisation was not co-scheduled: the whitened
     // route has nothing to offer; repeat through the Householder TSQR on the raw rows (which needs no factor of the prior)
     c->force_tsqr = true;
-    c->mode_a_wide_compressions = wide0, c->slam_mode_a_compressions = slam0, c->slam_fused_batches = fused0; // (the attempt does not stand)
+    c->mode_a_wide_compressions = wide0, c->slam_mode_a_compressions = slam0, c->slam_fused_batches = fused0, c->mode_a_panel_compressions = panel0; // (the attempt does not stand)
     if (attempt > 0) return set_err(OVGPU_ERR_NOT_SPD, "prior block of the involved variables not positive definite");
   }
   const int D = c->D, LD = c->LD;

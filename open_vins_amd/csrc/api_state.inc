@@ -341,6 +341,7 @@ int ovgpu_set_state(ovgpu_ctx *c, const ovgpu_state_view *st) {
   c->gram_wide_on = c->gram_wide; // ("gram_wide": with the state and with the batch, end_feature_batch)
   c->mode_a_wide_on = c->mode_a_wide; // ("mode_a_wide": likewise)
   c->slam_mode_a_on = c->slam_mode_a; // ("slam_mode_a": likewise)
+  c->mode_a_panel_on = c->mode_a_panel; // ("mode_a_panel": likewise)
   c->L = 0, c->h_lm_rep.clear(), c->h_lm_cov.clear(), c->h_lm_col.clear(), c->h_lm_anchor.clear();
   c->active_given = false, c->h_lm_active.clear(); // an active landmark set holds until the state or the landmarks are replaced
   c->row_stride = (c->dopt.feat_rep >= OVGPU_REP_ANCHORED_3D) ? 72 : 48;
@@ -797,6 +798,7 @@ static int end_feature_batch(ovgpu_ctx *c) {
   c->gram_wide_on = c->gram_wide; // "gram_wide" takes effect with a batch handed over (here) and with ovgpu_set_state, nowhere else
   c->mode_a_wide_on = c->mode_a_wide; // ... and so does "mode_a_wide"
   c->slam_mode_a_on = c->slam_mode_a; // ... and "slam_mode_a"
+  c->mode_a_panel_on = c->mode_a_panel; // ... and "mode_a_panel"
   c->have_feats = true;
   c->given_tri = false;
   return OVGPU_OK;
