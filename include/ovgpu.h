@@ -751,6 +751,11 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_stat
  * that does not sit on its threshold.  A rejected candidate then costs the step's first four launches (the system's rows, the
  * two products, the factorisation) where level 1 pays the per-feature kernel alone; a candidate whose triangulation failed
  * costs neither.  "delayed_init_rows_steps" counts the candidates that took the step at level 2.
+ * With ovgpu_debug_option "delayed_init_fused_long" = 1 (default 0) the bound of the fused step is m <= 232 measurements, at either
+ * level: up to 129 measurements (2m - 3 <= 256) the step is the same five launches, from 130 on its factorisation is two panels
+ * around a Schur step (eight launches and the clears of the step words; where "chol_wide" is 0 such a candidate takes
+ * ovgpu_slam_delayed_init's step).  Candidates of m <= 64 run what they run without the switch, bit for bit; m >= 233 takes
+ * ovgpu_slam_delayed_init's step in place.  "delayed_init_long_steps" counts the fused candidates of more than 64 measurements.
  * Callers find the entry by symbol (ABI 10).                                                                      */
 int ovgpu_slam_delayed_init_fused(ovgpu_ctx *ctx, int32_t feat_rep, int32_t *feat_status, double *chi2,
                                   double *chi2_thresh, int32_t *lm_cov_id, double *lm_value,
@@ -1324,6 +1329,14 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             counter); "delayed_init_fused_steps" counts the fused steps of either level
  *   "delayed_init_fused_steps" / "delayed_init_chain_steps"  number of candidates of ovgpu_slam_delayed_init_fused that took the fused step /
  *                             the chain's step (a track beyond the fused step's bound, or the switch above; a value >= 0 sets the counter)
+ *   "delayed_init_fused_long" (default 0) 0 / 1; the read-back returns it.  1: under "delayed_init_fused" = 1 or 2 a candidate of
+ *                             ovgpu_slam_delayed_init_fused with 65 .. 232 measurements takes the fused step as well: k_init_rows' LDS carve
+ *                             grows to 152 704 bytes at 232 measurements, and from 130 measurements on (2m - 3 > 256 projected rows) the
+ *                             factorisation runs as two panels around a Schur step (four launches, "chol_wide").  Candidates of 64
+ *                             measurements at most keep their launches and their bits; 233 and more take the chain's step in place, and so
+ *                             does a candidate of 130 .. 232 where "chol_wide" is 0
+ *   "delayed_init_long_steps" number of candidates of ovgpu_slam_delayed_init_fused with more than 64 measurements that took the fused step
+ *                             (a value >= 0 sets the counter); "delayed_init_fused_steps" counts them as well
  *   "slam_chunked_fail_chunk" k >= 0: the next ovgpu_slam_update_chunked treats chunk k's flag word as failed after its pass and takes
  *                             that path (one-shot; tests)
  *   "layout_every_update"     1: the integer tables ovgpu_set_features derives once per batch (anchor measurements, clone-major

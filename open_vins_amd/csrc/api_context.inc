@@ -227,6 +227,8 @@ struct ovgpu_ctx {
                                 // 1: the fused step behind k_system_t's gate; 2: the fused step behind k_init_rows, the gate taken from the step's own factorisation
   int64_t init_fused_steps = 0, init_chain_steps = 0; // "delayed_init_fused_steps" / "delayed_init_chain_steps": candidates of ovgpu_slam_delayed_init_fused by the step they took
   int64_t init_rows_steps = 0;  // "delayed_init_rows_steps": those of the fused steps that ran at level 2
+  int init_fused_long = 0;      // ovgpu_debug_option "delayed_init_fused_long".  1: the fused step holds tracks of up to INITF_M_MAX_LONG = 232 measurements (k_init_fused.h); 0: of up to 64
+  int64_t init_long_steps = 0;  // "delayed_init_long_steps": those of the fused steps whose candidate held more than 64 measurements
   // SLAM landmarks (ovgpu_set_landmarks); L > 0 switches the per-feature kernel to the UpdaterSLAM rules
   int L = 0;
   // the resident landmarks' representations, one each (Landmark::_feat_representation: StateOptions::feat_rep_slam, or feat_rep_aruco for

@@ -20,6 +20,12 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
   } else if (n == "delayed_init_rows_steps") { // ... of those that took it at level 2 (k_init_rows in place of k_system_t)
     if (old_value) *old_value = c->init_rows_steps;
     if (value >= 0) c->init_rows_steps = value;
+  } else if (n == "delayed_init_fused_long") { // 0 / 1.  1: under "delayed_init_fused" = 1 or 2 a candidate of ovgpu_slam_delayed_init_fused with 65 .. 232 measurements takes the fused step as well (k_init_rows' carve through with_max_lds; r = 2m - 3 > 256, m >= 130, factored by the two panels of k_chol_wide.h); default 0: such a candidate takes the chain's step; reads back 0 / 1
+    if (old_value) *old_value = c->init_fused_long;
+    if (value >= 0) c->init_fused_long = value != 0 ? 1 : 0;
+  } else if (n == "delayed_init_long_steps") { // ... of those that took the fused step with more than 64 measurements ("delayed_init_fused_long" = 1)
+    if (old_value) *old_value = c->init_long_steps;
+    if (value >= 0) c->init_long_steps = value;
   } else if (n == "delayed_init_chain_steps") { // ... and of those ovgpu_slam_delayed_init_fused ran as the chain runs them
     if (old_value) *old_value = c->init_chain_steps;
     if (value >= 0) c->init_chain_steps = value;

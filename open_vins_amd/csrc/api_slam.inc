@@ -533,6 +533,12 @@ static int enqueue_init_feature(ovgpu_ctx *c, int f, int rep, int Nmax, int Lcap
   return OVGPU_OK;
 }
 
+// The fused step's bound on a candidate's measurements, by ovgpu_debug_option "delayed_init_fused_long"
+static int initf_m_bound(const ovgpu_ctx *c) { return c->init_fused_long ? INITF_M_MAX_LONG : INITF_M_MAX; }
+// k_init_rows' carve for the batch in force: its longest track, at most the bound in force (a batch of tracks of 64 measurements at most keeps the
+// carve it had before the long bound)
+static int init_rows_m_max(const ovgpu_ctx *c) { return std::min(std::max(c->m_max, 1), initf_m_bound(c)); }
+
 // The system of candidate f without its gate (k_init_rows, k_init_fused.h): enqueue_system's parameters for f_one = f, one workgroup whose carve
 // holds the fused step's longest track at most
 static int enqueue_init_rows(ovgpu_ctx *c, int f, int rep) {
@@ -542,17 +548,30 @@ static int enqueue_init_rows(ovgpu_ctx *c, int f, int rep) {
   sys_params_init_mode(c, p, f, rep);
   c->stack_is_f32 = false, c->last_stack_raw = false; // (as enqueue_system leaves them: the candidate's rows are float64 and projected)
   p.P = nullptr, p.ws = nullptr, p.init_keep = 0;      // nothing of the gate is read
-  p.m_max = std::min(p.m_max, INITF_M_MAX);
-  const size_t lds = init_rows_lds_layout(p.m_max, p.row_stride).total; // (42496 bytes at the bound and 72-double records: under the 64 KB every kernel may ask for)
-  if (p.row_stride > 72) return set_err(OVGPU_ERR_INVALID, "internal: k_init_rows' carve is sized for records of 72 doubles at most");
-  hipLaunchKernelGGL(k_init_rows, dim3(1), dim3(SYS_NT), lds, c->stream, p);
+  p.m_max = std::min(p.m_max, initf_m_bound(c));
+  // 42496 bytes at 64 measurements and 72-double records, 152704 at 232: beyond the 64 KB a kernel may ask for by default, hence with_max_lds
+  const size_t lds = init_rows_lds_layout(p.m_max, p.row_stride).total;
+  if (p.row_stride > 72 || lds > (size_t)c->lds_limit) return set_err(OVGPU_ERR_INVALID, "internal: k_init_rows' carve is sized for records of 72 doubles at most, within the device's LDS");
+  // a long track's phase (d) — 3m steps over LDS per column — is dealt to a workgroup per 64 columns (each repeats the phases before it: measured at
+  // 232 measurements, one workgroup spent 285 us, 40 % of the step); up to 64 measurements the one workgroup the launch always had
+  const int m = b.h_offsets[f + 1] - b.h_offsets[f];
+  const int wgs = m > INITF_M_MAX ? (p.LD + INIT_ROWS_CPW - 1) / INIT_ROWS_CPW : 1;
+  hipLaunchKernelGGL(with_max_lds<k_init_rows>(c), dim3(wgs), dim3(SYS_NT), lds, c->stream, p);
   HIPCHK(hipGetLastError());
   return OVGPU_OK;
 }
 
-// One candidate as the fused step (k_init_fused.h): five launches, no memset.  The caller has checked initf_holds(c, m).
+// One candidate as the fused step (k_init_fused.h): five launches, no memset (eight and the host's clears of the step words where r > 256).  The
+// caller has checked initf_holds(c, m, level), the one place that knows the step's bounds: on the track (64 measurements; 232 under
+// "delayed_init_fused_long"), on the factorisation (one panel of k_chol_fused up to r = 2m - 3 = 256, the two panels of k_chol_wide.h up to 461,
+// each where the context's options leave it usable) and, at level 2, on k_init_rows' carve.
 // level 1: k_system_t decides the gate ahead of the step; 2: k_init_rows, and the tail decides it from the factorisation's carried residual.
-static bool initf_holds(const ovgpu_ctx *c, int m) { return m >= 2 && m <= INITF_M_MAX && chol_pipe_usable(c, 2 * m - 3); }
+static bool initf_holds(const ovgpu_ctx *c, int m, int level) {
+  if (m < 2 || m > initf_m_bound(c)) return false;
+  const int r = 2 * m - 3;
+  if (!chol_pipe_usable(c, r) && !chol_wide_usable(c, r)) return false;
+  return level < 2 || (c->row_stride <= 72 && init_rows_lds_layout(init_rows_m_max(c), c->row_stride).total <= (size_t)c->lds_limit);
+}
 static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, double *dx, int level) {
   hipStream_t s = c->stream;
   const Batch b = batch_of(c);
@@ -569,16 +588,28 @@ static int enqueue_init_feature_fused(ovgpu_ctx *c, int f, int rep, int Nmax, do
   p.clone_qp = c->clone_qp.p, p.calib_qp = c->calib_qp.p, p.intr = c->intr.p, p.clone_fej = c->clone_fej.p;
   p.tab_clone = c->tab_clone.p, p.tab_cam = c->tab_cam.p, p.tab_cc = c->tab_cc.p;
   p.p_FinG = b.pG, p.p_FinA = b.pA, p.meas_cc = b.meas_cc, p.anchor_meas = c->anchor.p, p.lm = landmark_store(c), p.feat_slot = c->feat_slot.p;
-  const int slot = chol_next_slot(c);
-  p.prog = c->chol_prog.p + CHOL_PROG_STRIDE * slot;
-  c->ctrl_clean &= ~(slot ? CTRL_PROG1 : CTRL_PROG0), c->ctrl_pre &= ~(slot ? CTRL_PROG1 : CTRL_PROG0); // (the step words are k_initf_s's to clear, and dirty afterwards)
+  // r <= 256: one panel, whose step words k_initf_s' last workgroup clears.  Beyond ("delayed_init_fused_long"): the two panels of k_chol_wide.h
+  // use both sets of step words and the GO word, and enqueue_chol_wide clears the sets through ctrl_zero — k_initf_s is told to leave them alone.
+  const bool wide = !chol_pipe_usable(c, r);
+  const int slot = wide ? 0 : chol_next_slot(c);
+  p.prog = wide ? nullptr : c->chol_prog.p + CHOL_PROG_STRIDE * slot;
+  if (!wide) c->ctrl_clean &= ~(slot ? CTRL_PROG1 : CTRL_PROG0), c->ctrl_pre &= ~(slot ? CTRL_PROG1 : CTRL_PROG0); // (the step words are k_initf_s's to clear, and dirty afterwards)
   const int tn = (Nmax + 15) / 16, tw = (r + 3 + 15) / 16, tm = (r + 15) / 16;
   hipLaunchKernelGGL(k_initf_w, dim3((tw * tn + 3) / 4), dim3(256), 0, s, p);
   hipLaunchKernelGGL(k_initf_s, dim3((tm * tw + 3) / 4 + 1), dim3(256), 0, s, p);
-  chol::CholParams q;
-  q.D = r, q.LA = p.LA, q.A = p.A, q.Y = c->Yaug.p, q.Lt = nullptr, q.flags = c->flags.p, q.diag0 = nullptr, q.pivot_tol = 1e-13, q.pred = c->init_ctr.p + 2;
-  q.src = chol::CH_SRC_MATRIX, q.N = Nmax, q.pred_not = nullptr;
-  if ((rc = launch_chol_fused(c, q, slot, s)) != OVGPU_OK) return rc;
+  if (wide) {
+    // panel, Schur step, panel, place on [S | W2 | new columns | res2] (CH_SRC_MATRIX), predicated on ctr[2], the step's pivot tolerance; the
+    // second panel's rows of Y, the carried residual Y[k LA + r + N] among them, are where the tails read them once k_chol_place has run
+    EkfParams e;
+    e.N = Nmax, e.D = r, e.DC = c->D, e.LD = c->LD, e.LA = p.LA, e.tri = 0, e.pred = c->init_ctr.p + 2, e.R = nullptr, e.col_cov = p.col_cov, e.P = p.P, e.Mt = nullptr;
+    e.A = p.A, e.Y = c->Yaug.p, e.dx = dx, e.flags = c->flags.p, e.sigma2 = p.sigma2, e.diag0 = nullptr, e.pivot_tol = 1e-13, e.pred_not = nullptr;
+    if ((rc = enqueue_chol_wide(c, e, s, nullptr)) != OVGPU_OK) return rc;
+  } else {
+    chol::CholParams q;
+    q.D = r, q.LA = p.LA, q.A = p.A, q.Y = c->Yaug.p, q.Lt = nullptr, q.flags = c->flags.p, q.diag0 = nullptr, q.pivot_tol = 1e-13, q.pred = c->init_ctr.p + 2;
+    q.src = chol::CH_SRC_MATRIX, q.N = Nmax, q.pred_not = nullptr;
+    if ((rc = launch_chol_fused(c, q, slot, s)) != OVGPU_OK) return rc;
+  }
   if (level >= 2) hipLaunchKernelGGL(k_initf_tail_gate, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p, InitGateParams{b.chi2_thr, b.chi2, b.status});
   else hipLaunchKernelGGL(k_initf_tail, dim3((tn * tn + 3) / 4 + 1), dim3(256), 0, s, p);
   HIPCHK(hipGetLastError());
@@ -632,6 +663,12 @@ static int begin_init_chain(ovgpu_ctx *c, int32_t feat_rep, int first, bool fuse
   HIPCHK(c->feat_slot.reserve(std::max(F, 1)));
   HIPCHK(c->dx_seq.reserve((size_t)std::max(F, 1) * Nmax));
   if (fused) HIPCHK(c->chol_uinv.reserve((size_t)2 * 16 * 256));
+  const int r_wide = std::min(ch.r_max, 2 * chol::CW_D1);
+  if (fused && c->init_fused_long && chol_wide_usable(c, r_wide)) { // the second panel's compact matrices for the batch's longest track: nothing is allocated inside the chain
+    const size_t D2 = (size_t)r_wide - chol::CW_D1;
+    HIPCHK(c->chol_wide_A.reserve(D2 * (D2 + Nmax + 1)));
+    HIPCHK(c->chol_wide_Y.reserve(D2 * (D2 + Nmax + 1)));
+  }
   HIPCHK(c->Mt.reserve(rD * Nmax));
   HIPCHK(c->Aaug.reserve(rD * (rD + Nmax + 1)));
   HIPCHK(c->Yaug.reserve(rD * (rD + Nmax + 1)));
@@ -678,14 +715,15 @@ static int delayed_init_impl(ovgpu_ctx *c, bool fused, int32_t feat_rep, int32_t
   for (int f = 0; f < F && rc == OVGPU_OK; f++) {
     const int m = b.h_offsets[f + 1] - b.h_offsets[f];
     if (m < 2) continue; // :91-93, flagged OVGPU_FEAT_TOO_FEW_MEAS by the triangulation
-    if (fused && c->init_fused > 0 && initf_holds(c, m)) {
+    if (fused && c->init_fused > 0 && initf_holds(c, m, c->init_fused)) {
       rc = enqueue_init_feature_fused(c, f, ch.rep[f], Nmax, c->dx_seq.p + (size_t)f * Nmax, c->init_fused);
       c->init_fused_steps++;
       if (c->init_fused >= 2) c->init_rows_steps++;
+      if (m > INITF_M_MAX) c->init_long_steps++;
       continue;
     }
     rc = enqueue_init_feature(c, f, ch.rep[f], Nmax, L0 + F, ch.init_lds, c->dx_seq.p + (size_t)f * Nmax, nullptr);
-    if (fused) c->init_chain_steps++; // (a track beyond the fused step's bound, or "delayed_init_fused" = 0)
+    if (fused) c->init_chain_steps++; // (a track beyond the fused step's bound, a factorisation the step cannot take, or "delayed_init_fused" = 0)
   }
   // ---- results
   int32_t ctr[4] = {N0, L0, 0, 0};
@@ -761,8 +799,8 @@ int ovgpu_slam_delayed_init(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status
   return delayed_init_impl(c, false, feat_rep, feat_status, chi2, chi2_thresh, lm_cov_id, lm_value, lm_fej, anchor_cam, anchor_clone, dx_seq, N_out, P_out, stats);
 }
 
-// The same call with every candidate the fused step holds (k_init_fused.h: m <= INITF_M_MAX) run as five launches; the others take
-// enqueue_init_feature where they stand in the chain.
+// The same call with every candidate the fused step holds (initf_holds: m <= INITF_M_MAX, or INITF_M_MAX_LONG under "delayed_init_fused_long")
+// run as five launches (eight beyond r = 256); the others take enqueue_init_feature where they stand in the chain.
 int ovgpu_slam_delayed_init_fused(ovgpu_ctx *c, int32_t feat_rep, int32_t *feat_status, double *chi2, double *chi2_thresh, int32_t *lm_cov_id,
                                   double *lm_value, double *lm_fej, int32_t *anchor_cam, int32_t *anchor_clone, double *dx_seq, int32_t *N_out,
                                   double *P_out, ovgpu_update_stats *stats) {

@@ -23,6 +23,12 @@
 //
 // Bound: 2m - 3 + 3 <= 128 rows of W (eight 16-row tiles), m <= INITF_M_MAX = 64; a longer track takes the chain of single launches.
 //
+// ovgpu_debug_option "delayed_init_fused_long" = 1 moves the bound to INITF_M_MAX_LONG = 232, where the other fused per-feature kernels stop.  Nothing
+// in the three kernels of this file is tied to 128 rows (a wavefront per 16 x 16 tile over global memory); what changes is around them: k_init_rows'
+// carve goes beyond the 64 KB default (656 bytes per measurement + 512 at 72-double records, 152 704 bytes at 232: launched through with_max_lds),
+// and r = 2m - 3 > 256 (m >= 130) is factored by the two panels of k_chol_wide.h, whose step words the host clears (p.prog = nullptr: k_initf_s leaves
+// them alone).  k_chol_place puts the second panel's rows, the carried residual among them, where the tails read them.
+//
 // Level 2 of ovgpu_debug_option "delayed_init_fused": the gate is taken from the chain's own factor.  k_chol_fused carries res2 through
 // S = U^T U to y = U^-T res2, and |y|^2 = res2^T (A2_x P_DD A2_x^T + sigma^2 I)^-1 res2 is the statistic StateHelper::initialize gates on
 // (StateHelper.cpp:466; rows scaled by sigma / sigma_f scale S by its square and res2 by itself: the statistic does not see the scale).  So
@@ -40,6 +46,8 @@
 namespace ovg {
 
 constexpr int INITF_M_MAX = 64;
+constexpr int INITF_M_MAX_LONG = 232; // "delayed_init_fused_long": r = 2m - 3 <= 461, two Cholesky panels from m = 130 on
+constexpr int INIT_ROWS_CPW = 64;     // k_init_rows on a track beyond INITF_M_MAX: columns of phase (d) per workgroup (one wavefront's worth)
 
 // k_init_rows' LDS carve in bytes for a launch whose candidate holds at most m_max measurements (host and device agree on this): the Jacobian
 // records at the context's row stride, their bookkeeping, V of the three reflectors, the representation scratch.  64 measurements of 72 doubles:
@@ -47,8 +55,8 @@ constexpr int INITF_M_MAX = 64;
 struct InitRowsLds {
   size_t minfo, rows, V, hq, total;
 };
-__host__ __device__ inline InitRowsLds init_rows_lds_layout(int m_max, int row_stride) {
-  InitRowsLds L;
+__host__ __device__ constexpr InitRowsLds init_rows_lds_layout(int m_max, int row_stride) {
+  InitRowsLds L{};
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
@@ -62,9 +70,13 @@ __host__ __device__ inline InitRowsLds init_rows_lds_layout(int m_max, int row_s
   L.total = o;
   return L;
 }
+static_assert(init_rows_lds_layout(INITF_M_MAX, 72).total == 42496, "the carve of the 64-measurement bound is what it was");
+static_assert(init_rows_lds_layout(INITF_M_MAX_LONG, 72).total == 152704 && init_rows_lds_layout(INITF_M_MAX_LONG, 72).total <= 160 * 1024,
+              "k_init_rows' carve at the long bound and 72-double records has to fit a compute unit's 160 KB of LDS");
 
 // The system of ONE candidate (p.f_begin) of the delayed initialisation without the gate: phases (a0), (a), (b) and the unwhitened (d) of
-// k_system_t for p.init = 1 (an MSCKF-style system: all three columns of H_f are projected), through the same device functions.  One workgroup.
+// k_system_t for p.init = 1 (an MSCKF-style system: all three columns of H_f are projected), through the same device functions.  One workgroup;
+// for a track beyond INITF_M_MAX a workgroup per INIT_ROWS_CPW columns of phase (d), each with the whole carve (see the kernel's head).
 //   init_out[0 .. 3 LD) = oscale Q1^T [H_x | res],  init_out[3 LD .. + 9) = oscale R1,  the candidate's rows of Hbig = oscale Q2^T [H_x | res],
 //   chi2_thresh[f],  init_flag[0] = the candidate arrived OVGPU_FEAT_USED.
 // Neither chi2[f] nor status[f] is written, neither P nor the gate's workspaces are read.  p.m_max sizes the carve (the host passes the fused
@@ -84,7 +96,14 @@ __global__ void __launch_bounds__(SYS_NT) k_init_rows(SysParams p) {
   const int m = p.meas_offsets[f + 1] - m0;
   const int64_t orow0 = p.row_off[f];
   const int n_out = (int)(p.row_off[f + 1] - orow0); // 2m - 3
+  // The columns of phase (d) are dealt to the launch's workgroups in whole blocks of INIT_ROWS_CPW; every workgroup repeats (a0), (a) and (b),
+  // which read nothing of P and write LDS only, and workgroup 0 alone writes what is not a column's.  One workgroup (a track of 64 measurements
+  // at most): all columns, the launch as it was.  A column is one thread's, summed in one order whichever workgroup holds it: the same bits.
+  const bool first_wg = blockIdx.x == 0;
+  const int c_per_wg = ((LD + (int)gridDim.x - 1) / (int)gridDim.x + INIT_ROWS_CPW - 1) / INIT_ROWS_CPW * INIT_ROWS_CPW;
+  const int c_begin = blockIdx.x * c_per_wg, c_end = min(LD, c_begin + c_per_wg);
   if (p.status[f] != OVGPU_FEAT_USED || m < 2 || m > p.m_max) { // failed before the gate (or a track the carve does not hold: the host never sends one)
+    if (!first_wg) return;
     for (int64_t e = tid; e < (int64_t)n_out * LD; e += SYS_NT) p.Hbig[orow0 * LD + e] = 0.0;
     if (tid == 0) p.init_flag[0] = 0;
     return;
@@ -121,8 +140,10 @@ __global__ void __launch_bounds__(SYS_NT) k_init_rows(SysParams p) {
     }
     // StateHelper::initialize gates against the quantile of the res.rows() it was handed: 2m, or 2m - 2 when the bearing was projected out
     // before (StateHelper.cpp:466, UpdaterSLAM.cpp:181-196)
-    p.chi2_thresh[f] = mult_f * p.chi2_table[min(n - p.init_dof_less, p.chi2_table_len - 1)];
-    p.init_flag[0] = 1;
+    if (first_wg) {
+      p.chi2_thresh[f] = mult_f * p.chi2_table[min(n - p.init_dof_less, p.chi2_table_len - 1)];
+      p.init_flag[0] = 1;
+    }
   }
   __syncthreads();
 
@@ -136,7 +157,7 @@ __global__ void __launch_bounds__(SYS_NT) k_init_rows(SysParams p) {
 
   // (d) thread per column: rows 0..2 of Q^T [H_x | res] -> init_out, rows 3..n-1 -> Hbig (k_system_t's unwhitened stack, p.init)
   const double T00 = hq[3], T01 = hq[4], T02 = hq[5], T11 = hq[6], T12 = hq[7], T22 = hq[8];
-  for (int c = tid; c < LD; c += SYS_NT) {
+  for (int c = c_begin + tid; c < c_end; c += SYS_NT) {
     int kind = COL_RESIDUAL, var = 0, sub = 0;
     if (c < D) kind = p.col_kind[c], var = p.col_var[c], sub = p.col_sub[c];
     const bool anc_hit_c = (kind == COL_CLONE && var == anchor_clone && relative);
@@ -176,7 +197,7 @@ __global__ void __launch_bounds__(SYS_NT) k_init_rows(SysParams p) {
       else out[(size_t)(r - nproj) * LD] = q;
     }
   }
-  if (tid < 9) { // H_finit = R1 (3 x 3 upper triangular): Q^T H_f, diagonal = beta
+  if (first_wg && tid < 9) { // H_finit = R1 (3 x 3 upper triangular): Q^T H_f, diagonal = beta
     const int i = tid / 3, j = tid % 3;
     p.init_out[(size_t)3 * LD + tid] = oscale * (j < i ? 0.0 : (j == i ? hq[58 + i] : rows[(size_t)(i >> 1) * RS + RO_HF + 3 * (i & 1) + j]));
   }
@@ -204,7 +225,7 @@ struct InitFusedParams {
   double *PLL;              // [9] G P_DD G^T + sigma^2 R1^-1 R1^-T
   double sigma2;
   int32_t *ctr;             // [0] covariance dimension, [1] landmark count, [2] this candidate passed the gate (level 2: was triangulated), [4] arrivals of the tail's workgroups
-  int32_t *prog;            // [16] k_chol_fused's step words (cleared by k_initf_s)
+  int32_t *prog;            // [16] k_chol_fused's step words (cleared by k_initf_s); null: r > 256, both panels' words are cleared by the host
   double *dx;               // [N] row f of dx_seq
   int32_t *flags;           // [1] = 1: a negative diagonal of P after the update
   // the tail
@@ -272,7 +293,7 @@ __global__ void __launch_bounds__(256) k_initf_s(InitFusedParams p) {
   const int id = p.ctr[0], j0 = 3 - p.sz;
   if (blockIdx.x + 1 == gridDim.x) {
     for (int row = threadIdx.x; row < r; row += 256) p.A[(size_t)row * LA + r + N] = p.stack[(size_t)row * LD + D];
-    if (threadIdx.x < 16) p.prog[threadIdx.x] = 0;
+    if (p.prog && threadIdx.x < 16) p.prog[threadIdx.x] = 0; // (null: the two-panel factorisation, whose words the host clears)
     if (threadIdx.x < 64) {
       double s[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
       for (int c = lane; c < D; c += 64) {

@@ -14,9 +14,17 @@ next to the chain of single launches (ovgpu_slam_delayed_init): an A/B of the tw
                     B on the tree's with "delayed_init_fused" = --level-b (the switch is a level: 1 the step behind k_system_t's gate, 2 behind
                     k_init_rows with the gate in the tail).  A row per (F, leg); bits_equal_A: the leg's N, covariance ids, values, dx_seq and P
                     are leg A's bit for bit.  --outlier-frac 1: every candidate a gross outlier (the all-rejected frame).
-    trace [--F 30] [--calls 10] [--entry fused|chain] [--lib-a PATH] [--level N]
+    time --long [--clones 30 50]
+                    the long-track rows of "delayed_init_fused_long" (tracks of 65 .. 232 measurements on the fused step): `clones` x 4 cameras with
+                    online calibration, no resident landmarks, F = 1, 5 and 30 candidates at the window's full length (120 / 200 measurements,
+                    GLOBAL_3D), three legs of the fused entry on the tree's library, interleaved frame by frame on the same inputs: "off-1" the
+                    switch off at level 1 (every candidate on the chain's step), "on-1" the switch on at level 1, "on-2" the switch on at level 2.
+                    A row per (clones, F, leg); the on legs are held to the off leg within the bounds of tests/test_gpu_delayed_init_fused.py's
+                    _check (verdicts identical, values 1e-8 / 1e-10, dx_seq 1e-6, P 1e-7) before their row is written.
+    trace [--F 30] [--calls 10] [--entry fused|chain] [--lib-a PATH] [--level N] [--long CLONES]
                     the frames alone, for a rocprofv3 --kernel-trace --stats run of its own (the kernels per candidate); --lib-a: on that
-                    library; --level: "delayed_init_fused" set to it first"""
+                    library; --level: "delayed_init_fused" set to it first; --long CLONES: the long-track frame of `time --long` at that many
+                    clones with the switch on (--F 1: the per-kernel times of ONE long candidate)"""
 import argparse
 import ctypes as C
 import json
@@ -39,6 +47,14 @@ def problem(synth, F, seed=3, outlier_frac=0.2):
     for k in ("meas_offsets", "uv", "uvn", "clone_idx", "cam_idx", "p_FinG_true"):
         setattr(prob, k, getattr(tracks, k))
     return prob
+
+
+def problem_long(synth, C, F, seed=3):
+    """F candidates at the full length of the C x 4 window (the longest F of 4 F: C * 4 measurements each where the point is seen throughout),
+    online calibration, no resident landmarks, no planted outliers"""
+    prob = synth.make_problem(2, C=C, K=4, F=4 * F, seed=seed)
+    m = np.diff(prob.meas_offsets)
+    return prob.subset(np.sort(np.argsort(-m, kind="stable")[:F]))
 
 
 def forms(up, capi, prob):
@@ -92,15 +108,17 @@ def bind(capi, path):
 class Leg:
     """one context of `lib` and its frame through the fused entry; level: "delayed_init_fused" is set to it, None leaves the library alone"""
 
-    def __init__(self, capi, lib, prob, kind, level):
+    def __init__(self, capi, lib, prob, kind, level, debug=None, reps=None):
         self.capi, self.lib, self.kind, self.level, self.ctx = capi, lib, kind, level, C.c_void_p()
         opts = capi.default_options(chi2_multipler=1.0)
         self.ok(lib.ovgpu_create(C.byref(opts), 0, C.byref(self.ctx)), "ovgpu_create")
         if level is not None:
             self.ok(lib.ovgpu_debug_option(self.ctx, b"delayed_init_fused", int(level), None), "ovgpu_debug_option")
+        for name, value in (debug or {}).items():  # further options of the tree's library
+            self.ok(lib.ovgpu_debug_option(self.ctx, name.encode(), int(value), None), "ovgpu_debug_option")
         self.v = capi.Views(prob)
         F, N = self.v.features.F, prob.N
-        self.reps = np.array((REPS6 * ((F + 5) // 6))[:F], np.int32)
+        self.reps = np.array((REPS6 * ((F + 5) // 6))[:F], np.int32) if reps is None else np.full(F, reps, np.int32)
         Nmax = N + int(np.where(self.reps == capi.REP_ANCHORED_INVERSE_DEPTH_SINGLE, 1, 3).sum())
         self.st, self.cov = np.zeros(F, np.int32), np.zeros(F, np.int32)
         self.val, self.fej, self.dx, self.P = np.zeros((F, 3)), np.zeros((F, 3)), np.zeros((F, Nmax)), np.zeros(Nmax * Nmax)
@@ -115,8 +133,9 @@ class Leg:
         ip = lambda a: a.ctypes.data_as(self.capi.c_int32_p)
         dp = lambda a: a.ctypes.data_as(self.capi.c_double_p)
         self.ok(lib.ovgpu_set_state(ctx, C.byref(v.state)), "ovgpu_set_state")
-        self.ok(lib.ovgpu_set_landmarks(ctx, C.byref(v.landmarks)), "ovgpu_set_landmarks")
-        self.ok(lib.ovgpu_set_active_landmarks(ctx, 0, None), "ovgpu_set_active_landmarks")
+        if v.landmarks is not None:  # (the long-track rows have no resident landmarks)
+            self.ok(lib.ovgpu_set_landmarks(ctx, C.byref(v.landmarks)), "ovgpu_set_landmarks")
+            self.ok(lib.ovgpu_set_active_landmarks(ctx, 0, None), "ovgpu_set_active_landmarks")
         self.ok(lib.ovgpu_set_features(ctx, C.byref(v.features)), "ovgpu_set_features")
         self.ok(lib.ovgpu_set_feature_reps(ctx, ip(self.reps)), "ovgpu_set_feature_reps")
         self.ok(lib.ovgpu_slam_delayed_init_fused(ctx, 0, ip(self.st), None, None, ip(self.cov), dp(self.val), dp(self.fej), None, None, dp(self.dx),
@@ -181,6 +200,62 @@ def timed_legs(a):
                 fh.write(json.dumps(r) + "\n")
 
 
+LONG_LEGS = (("off-1", 1, 0), ("on-1", 1, 1), ("on-2", 2, 1))  # (leg, "delayed_init_fused", "delayed_init_fused_long")
+
+
+def rel(a, b):
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def timed_long(a):
+    import torch  # noqa: F401  (capi.load: torch's HIP runtime first)
+    from open_vins_amd import capi, synth
+    lib = capi.load()
+    rows = []
+    for C_ in a.clones:
+        for F in (1, 5, 30):
+            prob = problem_long(synth, C_, F)
+            m = np.diff(prob.meas_offsets)
+            legs = {k: Leg(capi, lib, prob, k, level, debug={"delayed_init_fused_long": on}, reps=capi.REP_GLOBAL_3D) for k, level, on in LONG_LEGS}
+            med = {k: [] for k in legs}
+            for rnd in range(a.rounds):
+                t = {k: [] for k in legs}
+                for i in range(a.reps + 3):
+                    for k, leg in legs.items():  # interleaved frame by frame
+                        leg.ok(leg.lib.ovgpu_synchronize(leg.ctx), "ovgpu_synchronize")
+                        t0 = time.perf_counter()
+                        leg.frame()
+                        t1 = time.perf_counter()
+                        if i >= 3:
+                            t[k].append((t1 - t0) * 1e3)
+                for k in legs:
+                    med[k].append(float(np.median(t[k])))
+            ref = legs["off-1"].outputs()
+            calls = a.rounds * (a.reps + 3)
+            for k, leg in legs.items():
+                o = leg.outputs()
+                acc = ref[2] >= 0
+                d_val = float(np.abs(o[3][acc] - ref[3][acc]).max(initial=0.0))
+                d_dx, d_P = rel(o[4], ref[4]), rel(o[5], ref[5])
+                # the on legs against the off leg, within the bounds of tests/test_gpu_delayed_init_fused.py::_check
+                assert o[0] == ref[0] and np.array_equal(o[1], ref[1]) and np.array_equal(o[2], ref[2]), f"leg {k}: verdicts differ from the off leg's"
+                assert np.allclose(o[3][acc], ref[3][acc], rtol=1e-8, atol=1e-10) and d_dx < 1e-6 and d_P < 1e-7, f"leg {k}: {d_val} {d_dx} {d_P}"
+                row = dict(case="delayed_init_long", leg=k, level=leg.level, long=int(k != "off-1"), F=F, L=0, clones=int(prob.C), cameras=int(prob.K),
+                           m_min=int(m.min()), m_max=int(m.max()), N=int(prob.N), N_out=int(o[0]), n_accepted=int(acc.sum()),
+                           n_rejected=int((o[1] == capi.FEAT_CHI2_REJECTED).sum()), build=a.tag, reps=a.reps, ms_round_medians=med[k],
+                           ms_median=float(np.median(med[k])), ms_spread=float(np.max(med[k]) - np.min(med[k])),
+                           fused_steps_per_call=leg.counter("delayed_init_fused_steps") / calls, long_steps_per_call=leg.counter("delayed_init_long_steps") / calls,
+                           chain_steps_per_call=leg.counter("delayed_init_chain_steps") / calls, d_values_off=d_val, d_dx_seq_off=d_dx, d_P_off=d_P)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            for leg in legs.values():
+                leg.close()
+    if a.out:
+        with open(a.out, "a") as fh:
+            for r in rows:
+                fh.write(json.dumps(r) + "\n")
+
+
 def same(got):
     (n0, c0, v0), (n1, c1, v1) = got["chain"], got["fused"]
     acc = c0 >= 0
@@ -188,6 +263,8 @@ def same(got):
 
 
 def timed(a):
+    if a.long:
+        return timed_long(a)
     if a.legs:
         return timed_legs(a)
     import torch  # noqa: F401  (capi.load: torch's HIP runtime first)
@@ -231,6 +308,18 @@ def trace(a):
     import torch  # noqa: F401
     from open_vins_amd import capi, synth
     from open_vins_amd.updater import UpdaterMSCKF
+    if a.long is not None:  # the long-track frame with the switch on, at --level (default 1)
+        prob = problem_long(synth, a.long, a.F)
+        level = 1 if a.level is None else a.level
+        leg = Leg(capi, capi.load(), prob, "trace", level, debug={"delayed_init_fused_long": 1}, reps=capi.REP_GLOBAL_3D)
+        for _ in range(a.calls):
+            leg.frame()
+        o = leg.outputs()
+        n_long = leg.counter("delayed_init_long_steps")
+        leg.close()
+        print(f"{a.calls} frames of the fused entry with the long bound at level {level}: {a.long} clones x 4 cameras, {a.F} candidates of "
+              f"{int(np.diff(prob.meas_offsets).min())} .. {int(np.diff(prob.meas_offsets).max())} measurements ({int((o[2] >= 0).sum())} accepted), {n_long} long steps")
+        return
     prob = problem(synth, a.F, outlier_frac=a.outlier_frac)
     if a.lib_a is not None or a.level is not None:  # the fused entry on a library by path and / or at a level
         leg = Leg(capi, bind(capi, a.lib_a), prob, "trace", a.level)
@@ -262,6 +351,8 @@ def main():
     t.add_argument("--level-a", type=int, default=1)
     t.add_argument("--level-b", type=int, default=2)
     t.add_argument("--outlier-frac", type=float, default=0.2)
+    t.add_argument("--long", action="store_true")
+    t.add_argument("--clones", type=int, nargs="+", default=[30, 50])
     r = sub.add_parser("trace")
     r.add_argument("--F", type=int, default=30)
     r.add_argument("--calls", type=int, default=10)
@@ -269,6 +360,7 @@ def main():
     r.add_argument("--lib-a", default=None)
     r.add_argument("--level", type=int, default=None)
     r.add_argument("--outlier-frac", type=float, default=0.2)
+    r.add_argument("--long", type=int, default=None)
     a = ap.parse_args()
     {"time": timed, "trace": trace}[a.cmd](a)
 
