@@ -457,9 +457,11 @@ int ovgpu_msckf_update(ovgpu_ctx *ctx, int32_t *feat_status, double *chi2,
  * definite, step-wise Cholesky after a follower's time-out): an update the device skipped leaves the
  * landmarks untouched, the repeat corrects them once, and on an error return the landmarks are in
  * the state the clones are in.
- * ROUTE: with a global MSCKF representation, no per-feature sigma / multiplier and tracks within
- * the fused kernels' limits the call runs what a landmark-free state of the same N runs — rows laid
- * out once, when the batch is handed over under the empty set; the one-kernel-per-feature path; the
+ * ROUTE: with a global or an anchored MSCKF representation (the anchored ones since
+ * k_feat_rows_anchored, unless "anchored_fast" = 0), no per-feature sigma / multiplier and tracks
+ * within the fused kernels' limits (per length class under "feat_classes" = 1) the call runs
+ * what a landmark-free state of the same N runs — rows laid out once, when the batch is handed
+ * over under the empty set; the one-kernel-per-feature path; the
  * Gram-form update; the prior block's factorisation started by ovgpu_set_features on the second
  * stream — and returns that state's bits.  Otherwise it takes the general per-feature kernel as
  * ovgpu_msckf_update does, and corrects the landmarks all the same.  ovgpu_msckf_update on the
@@ -1077,7 +1079,9 @@ int ovgpu_tracks_group_order(ovgpu_ctx *ctx, int32_t order);
  * flattening: observations whose time is (exactly) one of clone_times [C] (index = clone index
  * of the resident state), camera groups in the order of ovgpu_tracks_group_order (default: the
  * reference's iteration order of Feature::timestamps), time order inside a group.
- * An unknown id gives an empty track.  The state must be resident (C clones).                */
+ * An unknown id gives an empty track.  The state must be resident (C clones).
+ * The track lengths come back to the host before the batch is laid out, so a batch assembled here
+ * follows ovgpu_debug_option "feat_classes" exactly as one handed to ovgpu_set_features does.   */
 int ovgpu_tracks_to_features(ovgpu_ctx *ctx, int32_t F, const int64_t *featid,
                              const double *clone_times);
 
@@ -1359,6 +1363,35 @@ int ovgpu_last_update_route(ovgpu_ctx *ctx);
  *                             single-depth landmarks ("slam_fused" = 2), 6 / 7 the long shapes of k_slam_y<false> / k_slam_y<true>: a batch whose
  *                             longest track holds 63 to 126 measurements ("slam_fused" = 3), 8 / 9 the block-row shapes k_slam_y_big<false> /
  *                             k_slam_y_big<true>: 127 to 232 measurements ("slam_fused_big" = 1 under "slam_fused" = 3)
+ *                             Under "feat_classes" = 1 it keeps its meaning: the kernel of the batch's LONGEST track, the first class launched
+ *   "feat_classes"            a level, default 0.  0: one per-feature kernel per batch, picked from its longest track — up to 62 observations
+ *                             k_feat_y<4, 9, 2>, 63 to 126 k_feat_y<8, 17, 1>, 127 to 232 k_feat_y_big, beyond that the general kernel — so that one
+ *                             long track decides for every other.  1: an MSCKF batch laid out for the fast path is partitioned into up to four
+ *                             LENGTH CLASSES by the same rule applied per track (csrc/feat_classes.h), each a contiguous range of the slots sorted by
+ *                             descending length, and the update launches one kernel per class, longest class first, on the context's stream: each
+ *                             track on the smallest shape that holds it.  Tracks of 0 or 1 observations go with the shortest class present (the
+ *                             kernels skip them by status).  Every other term of the fast path's eligibility is evaluated once per batch as at
+ *                             level 0; the block of the reflector kernel in front is sized by the longest FUSED track, so a track beyond 232
+ *                             observations no longer keeps the others off the fused kernels: it alone takes the general kernel.  The stack: a
+ *                             batch whose classes are all one-pass kernels keeps the unprojected stack on the terms of "raw_stack"; a batch with
+ *                             a block-row or a general class stacks projected rows for all of its classes, as such batches do at level 0.
+ *                             The switch acts only with options.feature_kernel_shape = 0, "featy_big" = 0, no_fast_feature_kernel = 0 and on a
+ *                             batch whose track lengths the host has: one of ovgpu_set_features or of ovgpu_tracks_to_features.  A batch of one
+ *                             class, per-feature sigma / multiplier, the routes without the prior's factor (Householder), options.gram_fp32 next to
+ *                             a general class (the general kernel writes no float stack), SLAM batches and the delayed initialisation keep the
+ *                             single-kernel rule, launch for launch as at level 0.  What follows the switch without code of its own:
+ *                             ovgpu_msckf_update / _async, ovgpu_msckf_update_lm (its eligibility per batch, as before), ovgpu_msckf_compress, the
+ *                             local-Gram, sharded and multi entries (every rank partitions its own share).  Outputs: the reference's update to
+ *                             rounding; a feature's chi2 is the one its kernel gives at level 0 in a batch that kernel takes, bit for bit.
+ *                             Consecutive launches on one stream do not overlap: a class of a few features pays a serial tail (DESIGN.md section 7
+ *                             has the measurements; no class is merged into its neighbour).  Takes effect with the next ovgpu_set_features; a
+ *                             resident batch keeps the level it was laid out under, as with "slam_fused"
+ *   "last_feature_classes"    (read only) bit mask over the FeatKernel codes 0 .. 3 of the kernels the last batch pipeline launched; a single bit
+ *                             (the code "last_feature_kernel" reports) whenever one MSCKF kernel took the whole batch; 0 after a fused SLAM batch
+ *   "last_class_features_0" .. "last_class_features_3"  (read only) features of the last batch pipeline in the class of that code
+ *   "feat_class_batches"      counter: batch pipelines that launched more than one class, once per update that stands — the pipelines of an attempt
+ *                             the library repeats (Householder route, step-wise Cholesky) are not counted, the rule of "slam_fused_batches"; a
+ *                             value >= 0 sets it
  *   "sys_lds_limit" / "sys_m_lds_max" / "sys_rows_global" / "sys_row_stride" / "sys_lds_bytes"  (read only) the general per-feature kernel's
  *                             LDS carve for the batch in force, as sized with the last ovgpu_set_features (or the entry point that laid the batch out):
  *                             the byte limit of a workgroup's LDS; the largest track length whose gate matrix is LDS-resident (longer tracks of

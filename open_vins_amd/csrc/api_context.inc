@@ -146,6 +146,22 @@ struct FeatPlan {
   FeatKernel slam = FK_GENERAL;
   size_t slam_lds = 0;
   int slam_nt = 0;            // FK_SLAMY_BIG / _PROJ: tile rows of the longest track, the carve's and the scratch's parameter
+  // ovgpu_debug_option "feat_classes" = 1: the length classes of an MSCKF batch (feat_classes.h), longest first — a kernel each over its own slot
+  // range.  n_classes >= 2 or none at all: a batch of one class is the single-kernel rule's.  Then `msckf`, `nt` and `nta` above describe the
+  // longest FUSED track (the stride of the instance lists, k_feat_vt's block) and a general class, if there is one, is cls[0].
+  struct Class {
+    FeatKernel kernel = FK_GENERAL;
+    int begin = 0, end = 0;   // slots of b.h_order
+    int m_max = 0;            // the class's longest track, and the carve it sizes:
+    int nt = 0, nta = 0;      // tile rows as above (fused classes)
+    size_t lds = 0;           // dynamic LDS bytes
+    int grid = 1;
+  };
+  int n_classes = 0;
+  Class cls[4];
+  int m_fused = 0;            // the longest track of a fused class
+  bool cls_general() const { return n_classes > 0 && cls[0].kernel == FK_GENERAL; }
+  bool cls_mixed_width() const { return n_classes > 0 && msckf == FK_FEATY_BIG && cls[n_classes - 1].kernel != FK_FEATY_BIG; } // instance lists at both block widths
   const char *error = nullptr; // no kernel holds the batch's longest track (OVGPU_ERR_CAPACITY)
 };
 
@@ -360,7 +376,16 @@ struct ovgpu_ctx {
   int featy_skip = 0;              // ovgpu_debug_option "featy_skip": ablation bit mask (timing experiments only)
   DevBuf<double> fs_tq;
   DevBuf<int32_t> fs_inst;
-  DevBuf<double> featyb_ws;        // k_featy_big.h, k_slam_y_big.h: row panels of the earlier passes, per workgroup
+  // "feat_classes": a batch with a block-row class AND a one-pass class keeps its instance lists once per block width — fs_inst at 32 columns (the
+  // longest fused track's, as ever), fs_inst64 at 64 — built by a second pass of k_batch_layout wherever the first is (enqueue_batch_tables)
+  DevBuf<int32_t> fs_inst64;
+  int inst64_D = 0;                // the column count fs_inst64 was built for; 0 = not built
+  int feat_classes = 0;            // ovgpu_debug_option "feat_classes", a level: 0 one kernel per batch, picked from its longest track; 1 an MSCKF batch laid out for the fast path runs a kernel per length class (plan_feature_stage, feat_classes.h)
+  int64_t feat_class_batches = 0;  // ovgpu_debug_option "feat_class_batches": pipelines that launched more than one class, counted once per update as "slam_fused_batches" is
+  int feat_class_attempt = 0;      // ... of them, the ones of the update attempt that is running (update_with_fallbacks)
+  int last_feat_classes = 0;       // ovgpu_debug_option "last_feature_classes": bit mask over FeatKernel codes 0 .. 3 of the kernels the last batch pipeline launched
+  int last_class_features[4] = {0, 0, 0, 0}; // "last_class_features_0" .. "_3": features in the class of that code
+  DevBuf<double> featyb_ws;       // k_featy_big.h, k_slam_y_big.h: row panels of the earlier passes, per workgroup
   // k_slam_y_big.h: what its records kernel leaves for it (slamy::SlamYBigStore)
   DevBuf<double> slyb_rows, slyb_V, slyb_hq;
   DevBuf<int32_t> slyb_minfo, slyb_inst;

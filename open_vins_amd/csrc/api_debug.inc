@@ -119,6 +119,16 @@ int ovgpu_debug_option(ovgpu_ctx *c, const char *name, int64_t value, int64_t *o
     if (old_value) *old_value = c->stack_is_f32 ? 1 : 0;
   } else if (n == "last_feature_kernel") { // read-only: the per-feature kernel of the last batch pipeline, a FeatKernel (api_context.inc lists the codes)
     if (old_value) *old_value = c->last_feat_kernel;
+  } else if (n == "feat_classes") { // a level.  1 (and above): an MSCKF batch laid out for the fast path runs a per-feature kernel per length class, each track on the smallest shape that holds it (plan_feature_stage, feat_classes.h); default 0: one kernel per batch, picked from its longest track; reads back the level; takes effect with the next ovgpu_set_features
+    if (old_value) *old_value = c->feat_classes;
+    if (value >= 0) c->feat_classes = (int)std::min<int64_t>(value, 1);
+  } else if (n == "feat_class_batches") { // reads the count of batch pipelines that launched more than one length class, once per update (the pipelines of a repeated attempt — Householder route, step-wise Cholesky — are not counted); a value >= 0 sets it
+    if (old_value) *old_value = c->feat_class_batches;
+    if (value >= 0) c->feat_class_batches = value;
+  } else if (n == "last_feature_classes") { // read-only: bit mask over the FeatKernel codes 0 .. 3 of the kernels the last batch pipeline launched; a single bit whenever one kernel took the batch
+    if (old_value) *old_value = c->last_feat_classes;
+  } else if (n.size() == 21 && n.compare(0, 20, "last_class_features_") == 0 && n[20] >= '0' && n[20] <= '3') { // read-only, "last_class_features_0" .. "_3": features of the last batch pipeline in the class of that FeatKernel code
+    if (old_value) *old_value = c->last_class_features[n[20] - '0'];
   } else if (n == "last_gram_kernel") { // read-only, this and the two below: what the last batch pipeline launched (api_context.inc lists the codes)
     if (old_value) *old_value = c->last_gram_kernel;
   } else if (n == "last_gram_workgroups") { // read-only: gridDim.x of the last pipeline's k_gram_f32 or k_gram_blk launch (the row shares), 0 otherwise

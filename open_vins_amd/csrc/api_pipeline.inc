@@ -47,6 +47,10 @@ struct FeatLaunch {
   bool ch = false;  // k_feat_y<.., CH = true>: the run table, the next slot requested a feature ahead ("featy_chains")
   bool alt = false; // the kernel's other shape: k_feat_y_big<8, 5> ("featy_big" = 2), k_system_t<true> (Jacobian records in global memory)
   int cb = 0;       // columns per block of the fused MSCKF kernels' sweep; 0: another kernel
+  int nt = 0, nta = 0; // the fused MSCKF kernels' LDS carve: tile rows of the longest track the launch walks, and of its gate matrix ...
+  int ist = 0;         // ... against the tile rows per feature of the batch's instance lists, which a length class does not shorten
+  const int32_t *inst = nullptr; // the lists at `cb` columns
+  int slot0 = 0;       // the first slot record of the launch (a length class: its range's; the kernels walk p.F records from there)
   size_t lds = 0;   // dynamic LDS bytes, by the kernel header's own layout function
   int grid = 1;
   int err = OVGPU_OK;
@@ -57,25 +61,47 @@ static constexpr int feat_key(FeatKernel k, bool f32 = false, bool ch = false, b
 
 // The kernel of this launch: from the plan of the batch in force (F features), what p asks for — L (the whitened route; never with f_one >= 0),
 // SLAM rows, per-feature sigma / multiplier —, f_one, and the launch-time switches "featy_big", "featy_chains", options.gram_fp32 and lm_fast_on.
-static FeatLaunch select_feat_kernel(const ovgpu_ctx *c, const SysParams &p, int F, int f_one) {
+// k: the launch of ONE length class of the plan ("feat_classes"; enqueue_system has decided that the pipeline runs by classes), m_first the track
+// length at the class's first slot in the batch in force — the class's kernel, carve and grid as planned, held against that track.
+static FeatLaunch select_feat_kernel(const ovgpu_ctx *c, const SysParams &p, int F, int f_one, const FeatPlan::Class *k = nullptr, int m_first = 0) {
   const FeatPlan &pl = c->plan;
   const size_t limit = (size_t)c->lds_limit;
   FeatLaunch s;
   size_t need; // what the batch in force takes of the kernel's LDS, against s.lds: what the batch was laid out for
+  if (k) {
+    s.code = s.kernel = k->kernel, s.lds = k->lds, s.grid = k->grid;
+    s.err = OVGPU_ERR_INVALID, s.msg = "internal: a length class of the per-feature stage does not hold the tracks of its slot range";
+    if (k->kernel == FK_GENERAL) {
+      s.alt = pl.rows_global;
+      need = m_first <= p.m_max ? pl.sys_lds : limit + 1;
+    } else {
+      const int nt = featcls::tile_rows(m_first), nta = featcls::gate_tile_rows(m_first);
+      s.cb = k->kernel == FK_FEATY_BIG ? 32 : feat::FY_CB, s.nt = k->nt, s.nta = k->nta, s.ist = pl.nt, s.slot0 = k->begin;
+      s.inst = s.cb == feat::FY_CB && pl.cls_mixed_width() ? c->fs_inst64.p : c->fs_inst.p;
+      s.f32 = c->want_stack_f32, s.ch = !s.f32 && c->featy_chains && k->kernel != FK_FEATY_BIG;
+      // the carve is the class's, the lists' stride the batch's: a track of the range that needs more tile rows than either would leave its LDS block
+      if (featcls::kernel_of_length(std::max(m_first, 2)) != (int)k->kernel || nt > k->nt || nta > k->nta || k->nt > pl.nt) need = limit + 1;
+      else need = k->kernel == FK_FEATY_BIG ? feat::featyb_lds_layout(nt, 8).total : feat::featy_lds_layout(nt, nta, k->kernel == FK_FEATY_4 ? 4 : 8, s.cb).total;
+    }
+    if (need <= s.lds && s.lds <= limit) s.err = OVGPU_OK, s.msg = nullptr;
+    return s;
+  }
   // the MSCKF fast path: whitened output, one noise level (k_feat.h); a global representation, or an anchored one on its own record kernel
   // (with landmarks resident — the empty active set, set_row_layout — only for ovgpu_msckf_update_lm: every other entry keeps the general kernel)
-  if (p.Lw && pl.msckf != FK_GENERAL && (c->L == 0 || (c->lm_fast_on && pl.lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
+  // (a plan by length classes that holds a general class — enqueue_system runs it as ONE kernel when a launch-time switch rules the classes out —
+  //  is the general kernel's then, as the single-kernel rule has a batch whose longest track no fused kernel holds)
+  if (p.Lw && pl.msckf != FK_GENERAL && !pl.cls_general() && (c->L == 0 || (c->lm_fast_on && pl.lm_fast_ok)) && !p.slam && !p.feat_sigma && !p.feat_chi2mult) {
     s.code = pl.msckf, s.kernel = featy_block_rows(c) ? FK_FEATY_BIG : pl.msckf, s.cb = featy_block_cols(c);
+    s.nt = pl.nt, s.nta = pl.nta, s.ist = pl.nt, s.inst = c->fs_inst.p;
     if (s.kernel == FK_FEATY_BIG) { // block row by block row (k_featy_big.h), one workgroup per CU; <8, 5> has no float32 twin
       s.alt = c->featy_big == 2, s.f32 = c->want_stack_f32 && !s.alt;
       s.lds = feat::featyb_lds_layout(pl.nt, 8).total;
-      s.grid = std::max(1, std::min(F, c->num_cu));
+      s.grid = fused_feat_grid(c, FK_FEATY_BIG, s.lds, F);
       s.err = OVGPU_ERR_CAPACITY, s.msg = "k_feat_y_big: track too long for its LDS block";
     } else { // as many workgroups per CU as its registers (<4, 9, 2>: two; <8, 17, 1>: one) and its LDS block allow, the features dealt round-robin over them
       s.f32 = c->want_stack_f32, s.ch = !s.f32 && c->featy_chains;
       s.lds = feat::featy_lds_layout(pl.nt, pl.nta, pl.nw(), s.cb).total;
-      const int per_cu = std::max(1, std::min(s.kernel == FK_FEATY_4 ? 2 : 1, (int)(limit / s.lds)));
-      s.grid = std::max(1, std::min(F, c->num_cu * per_cu));
+      s.grid = fused_feat_grid(c, s.kernel, s.lds, F);
       s.err = OVGPU_ERR_INVALID, s.msg = "internal: the MSCKF fast path was selected for a batch the fused kernel does not hold";
     }
     need = s.lds;
@@ -101,19 +127,19 @@ static FeatLaunch select_feat_kernel(const ovgpu_ctx *c, const SysParams &p, int
 // The one launch of the per-feature stage: a row per instantiation
 static int launch_feat_kernel(ovgpu_ctx *c, const FeatLaunch &s, const SysParams &p) {
   const dim3 grid(s.grid), slam_block(64 * slamy::SLY_NW);
-  const int nt = c->plan.nt, nta = c->plan.nta;
+  const int nt = s.nt, nta = s.nta, ist = s.ist;
   const double *sr = c->fs_rows.p, *sV = c->fs_V.p, *stq = c->fs_tq.p;
-  const int32_t *sm = c->fs_minfo.p, *sin = c->fs_inst.p, *ssl = c->fs_slots.p, *runs = c->raw_runs.p;
+  const int32_t *sm = c->fs_minfo.p, *sin = s.inst, *ssl = c->fs_slots.p + (size_t)8 * s.slot0, *runs = c->raw_runs.p;
   double *bws = c->featyb_ws.p;
   switch (feat_key(s.kernel, s.f32, s.ch, s.alt)) {
     case feat_key(FK_GENERAL): hipLaunchKernelGGL(with_max_lds<k_system_t<false>>(c), grid, dim3(SYS_NT), s.lds, c->stream, p); break;
     case feat_key(FK_GENERAL, false, false, true): hipLaunchKernelGGL(with_max_lds<k_system_t<true>>(c), grid, dim3(SYS_NT), s.lds, c->stream, p); break;
-#define X(NW, TPW, OCC, F32, CB, CH) case feat_key(NW == 4 ? FK_FEATY_4 : FK_FEATY_8, F32, CH): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y<NW, TPW, OCC, F32, CB, CH>>(c)), grid, dim3(64 * NW), s.lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl, runs); break;
+#define X(NW, TPW, OCC, F32, CB, CH) case feat_key(NW == 4 ? FK_FEATY_4 : FK_FEATY_8, F32, CH): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y<NW, TPW, OCC, F32, CB, CH>>(c)), grid, dim3(64 * NW), s.lds, c->stream, p, nt, nta, sr, sm, sV, stq, sin, ssl, runs, ist); break;
     OVG_FEATY_SHAPES(X)
 #undef X
-    case feat_key(FK_FEATY_BIG): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 17>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws); break;
-    case feat_key(FK_FEATY_BIG, true): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 17, true>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws); break;
-    case feat_key(FK_FEATY_BIG, false, false, true): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 5>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws); break;
+    case feat_key(FK_FEATY_BIG): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 17>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws, ist); break;
+    case feat_key(FK_FEATY_BIG, true): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 17, true>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws, ist); break;
+    case feat_key(FK_FEATY_BIG, false, false, true): hipLaunchKernelGGL((with_max_lds<feat::k_feat_y_big<8, 5>>(c)), grid, dim3(512), s.lds, c->stream, p, nt, sr, sm, sV, stq, sin, ssl, bws, ist); break;
     case feat_key(FK_SLAMY): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<false>>(c)), grid, slam_block, s.lds, c->stream, p); break;
     case feat_key(FK_SLAMY_PROJ): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<true>>(c)), grid, slam_block, s.lds, c->stream, p); break;
     case feat_key(FK_SLAMY_LONG): hipLaunchKernelGGL((with_max_lds<slamy::k_slam_y<false, slamy::SLY_TPW_L, slamy::SLY_CB_L, slamy::SLY_MMAX_L>>(c)), grid, slam_block, s.lds, c->stream, p); break;
@@ -194,7 +220,22 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   if (f_one < 0) c->last_feat_kernel = FK_GENERAL;
   if (f_one < 0) HIPCHK(ctrl_zero(c, CTRL_ROWS, c->rows_used.p, 2 * sizeof(int32_t), c->stream));
   if (f_one >= 0) sys_params_init_mode(c, p, f_one, init_rep);
-  const FeatLaunch s = select_feat_kernel(c, p, b.F, f_one);
+  // ovgpu_debug_option "feat_classes": a batch laid out by length classes runs a kernel per class when this launch is one the fused kernels take at
+  // all (the whitened route, one noise level, no landmark column) and no launch-time switch rules the classes out — "featy_big", or options.gram_fp32
+  // next to a general class, whose kernel writes no float stack.  Otherwise the single-kernel rule holds (select_feat_kernel).  Every class is
+  // selected and held against its carve HERE, in front of the first launch: a refused class refuses the pipeline.
+  const FeatPlan &pl = c->plan;
+  const bool by_class = f_one < 0 && pl.n_classes >= 2 && p.Lw && !c->featy_big && (c->L == 0 || (c->lm_fast_on && pl.lm_fast_ok)) && !p.slam && !p.feat_sigma &&
+                        !p.feat_chi2mult && !(pl.cls_general() && c->want_stack_f32) && (int)b.h_order.size() == b.F;
+  FeatLaunch sc[featcls::FC_MAX];
+  for (int k = 0; by_class && k < pl.n_classes; k++) {
+    const int f0 = pl.cls[k].begin < b.F && pl.cls[k].end <= b.F ? b.h_order[pl.cls[k].begin] : -1;
+    if (f0 < 0) return set_err(OVGPU_ERR_INVALID, "internal: a length class lies outside the batch in force");
+    sc[k] = select_feat_kernel(c, p, b.F, -1, &pl.cls[k], b.h_offsets[f0 + 1] - b.h_offsets[f0]);
+    if (sc[k].err != OVGPU_OK) return set_err(sc[k].err, sc[k].msg);
+  }
+  // (by classes: `s` is the longest FUSED class's launch — what the head below is sized and switched by)
+  const FeatLaunch s = by_class ? sc[pl.cls_general() ? 1 : 0] : select_feat_kernel(c, p, b.F, f_one);
   if (s.err != OVGPU_OK) return set_err(s.err, s.msg);
   if (s.cb) { // the head of the MSCKF fast path
     p.row_stride = 48; // the fused kernels' records (fs_rows holds M * c->row_stride >= 48 M doubles): a 72-double stride — an anchored feat_rep_msckf, anchored
@@ -216,7 +257,8 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
     }
     if (p.opt.feat_rep >= OVGPU_REP_ANCHORED_3D) hipLaunchKernelGGL(feat::k_feat_rows_anchored, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
     else hipLaunchKernelGGL(feat::k_feat_rows_sorted, dim3((b.M + 255) / 256), dim3(256), 0, c->stream, p, st, b.M);
-    if (c->raw_enable && c->raw_tables_ok && !c->raw_veto && s.kernel != FK_FEATY_BIG && !s.f32 && s.cb == feat::FY_CB) {
+    // (by classes: every class a one-pass kernel — the longest fused one is, and there is no general class)
+    if (c->raw_enable && c->raw_tables_ok && !c->raw_veto && s.kernel != FK_FEATY_BIG && !s.f32 && s.cb == feat::FY_CB && !(by_class && pl.cls_general())) {
       p.raw.on = 1, p.raw.ncls = c->raw_ncls, p.raw.H = c->Hraw.p, p.raw.dst = c->raw_dst.p, p.raw.j0 = c->raw_j0;
       for (int k = 0; k <= RAW_NEG; k++) p.raw.base[k] = c->raw_base[k], p.raw.ld[k] = c->raw_ld[k], p.raw.rcol[k] = c->raw_rcol[k];
       c->last_stack_raw = true;
@@ -225,7 +267,13 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
       const int rci = enqueue_instance_lists(c, s.cb);
       if (rci != OVGPU_OK) return rci;
     }
-    hipLaunchKernelGGL(with_max_lds<feat::k_feat_vt>(c), dim3((b.F + 3) / 4), dim3(256), (size_t)4 * (14 * p.m_max + 64) * sizeof(double), c->stream, p, st, c->fs_tq.p);
+    if (by_class && pl.cls_mixed_width() && c->inst64_D != c->D) { // (likewise the one-pass classes' lists next to a block-row class)
+      const int rci = enqueue_instance_lists64(c);
+      if (rci != OVGPU_OK) return rci;
+    }
+    SysParams pv = p; // k_feat_vt's block holds the longest track the fused kernels take: the batch's, or by classes the longest fused class's (a general-class track returns at once)
+    if (by_class) pv.m_max = std::max(pl.m_fused, 1);
+    hipLaunchKernelGGL(with_max_lds<feat::k_feat_vt>(c), dim3((b.F + 3) / 4), dim3(256), (size_t)4 * (14 * pv.m_max + 64) * sizeof(double), c->stream, pv, st, c->fs_tq.p);
   }
   if (p.Lw && c->prior_on_side) { // the general kernel and k_slam_y read L from their first instruction on, the fused MSCKF kernels behind k_feat_vt
     // (L and the carried columns come out of one launch since round 5)
@@ -236,8 +284,26 @@ static int enqueue_system(ovgpu_ctx *c, int f_one = -1, int init_rep = 0, bool w
   if (s.kernel == FK_FEATY_BIG && c->plan.msckf != FK_FEATY_BIG) HIPCHK(c->featyb_ws.reserve((size_t)s.grid * feat::featyb_ws_doubles(c->plan.nt))); // ("featy_big": the batch was not laid out for it)
   if (s.kernel >= FK_SLAMY) c->slam_fused_batches++, c->slam_fused_attempt++;
   if (s.kernel == FK_GENERAL) p.rows_ws = s.alt ? c->sys_rows_ws.p : nullptr;
-  if (f_one < 0) c->last_feat_kernel = s.code;
-  return launch_feat_kernel(c, s, p);
+  if (f_one < 0) {
+    c->last_feat_kernel = by_class ? sc[0].code : s.code; // (by classes: the kernel of the batch's longest track)
+    c->last_feat_classes = 0;
+    for (int k = 0; k < featcls::FC_MAX; k++) c->last_class_features[k] = 0;
+    if (!by_class && s.code <= FK_FEATY_BIG) c->last_feat_classes = 1 << s.code, c->last_class_features[s.code] = b.F;
+  }
+  if (!by_class) return launch_feat_kernel(c, s, p);
+  // a launch per class, longest class first, on this stream: the deal inside a launch is what it was, the slots it walks are the class's
+  c->feat_class_batches++, c->feat_class_attempt++;
+  for (int k = 0; k < pl.n_classes; k++) {
+    SysParams pk = p;
+    pk.f_begin = pl.cls[k].begin, pk.f_end = pl.cls[k].end; // (the general kernel's range over p.order; a fused kernel walks pk.F slot records from the range's first: launch_feat_kernel)
+    if (sc[k].kernel != FK_GENERAL) pk.F = pk.f_end - pk.f_begin;
+    if (sc[k].kernel == FK_GENERAL) // (its own records at its own stride: the head above set the fused kernels' 48)
+      pk.rows_ws = sc[k].alt ? c->sys_rows_ws.p : nullptr, pk.row_stride = c->row_stride, pk.raw.on = 0, pk.Hbig32 = nullptr, pk.LDF = 0;
+    c->last_feat_classes |= 1 << sc[k].code, c->last_class_features[sc[k].code] = pk.f_end - pk.f_begin;
+    const int rc = launch_feat_kernel(c, sc[k], pk);
+    if (rc != OVGPU_OK) return rc;
+  }
+  return OVGPU_OK;
 }
 
 // merges triangles Rws[0..G) pairwise until Rws[0] holds the result
@@ -1227,7 +1293,7 @@ template <class Attempt> static int update_with_fallbacks(ovgpu_ctx *c, ovgpu_up
   int rc;
   for (;;) {
     c->chol_timed_out = false;
-    c->slam_fused_attempt = 0, c->gram_wide_attempt = 0;
+    c->slam_fused_attempt = 0, c->gram_wide_attempt = 0, c->feat_class_attempt = 0;
     rc = attempt();
     if (rc == OVGPU_ERR_NOT_SPD && c->last_update_tform && !c->chol_timed_out && !tried_householder) {
       tried_householder = true, c->force_tsqr = true;
@@ -1238,6 +1304,7 @@ template <class Attempt> static int update_with_fallbacks(ovgpu_ctx *c, ovgpu_up
     }
     c->slam_fused_batches -= c->slam_fused_attempt; // the attempt does not stand: "slam_fused_batches" counts the pipelines of the attempt that is the update
     c->gram_wide_updates -= c->gram_wide_attempt;   // ... and "gram_wide_updates" the update itself
+    c->feat_class_batches -= c->feat_class_attempt; // ... and "feat_class_batches" as "slam_fused_batches"
     if (stats) std::memset(stats, 0, sizeof(*stats));
   }
   if (rc != OVGPU_OK) c->gram_wide_updates -= c->gram_wide_attempt; // an update that ends in an error does not stand either
@@ -1300,7 +1367,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
   int rc;
   const double *tri = nullptr;
   int32_t dropped = 0;
-  const int64_t wide0 = c->mode_a_wide_compressions, slam0 = c->slam_mode_a_compressions, fused0 = c->slam_fused_batches, panel0 = c->mode_a_panel_compressions;
+  const int64_t wide0 = c->mode_a_wide_compressions, slam0 = c->slam_mode_a_compressions, fused0 = c->slam_fused_batches, panel0 = c->mode_a_panel_compressions, classes0 = c->feat_class_batches;
   for (int attempt = 0;; attempt++) {
     c->factor_from_gram = attempt == 0; // the whitened Gram matrix's factor (pivoted by default) where it applies; Householder TSQR otherwise
     if ((rc = enqueue_pipeline(c, STAGE_LOCAL, slam)) != OVGPU_OK) return rc;
@@ -1323,7 +1390,7 @@ static int compress_impl(ovgpu_ctx *c, bool slam, int32_t *feat_status, double *
     // the prior block is not (numerically) positive definite, or its single-launch factorisation was not co-scheduled: the whitened
     // route has nothing to offer; repeat through the Householder TSQR on the raw rows (which needs no factor of the prior)
     c->force_tsqr = true;
-    c->mode_a_wide_compressions = wide0, c->slam_mode_a_compressions = slam0, c->slam_fused_batches = fused0, c->mode_a_panel_compressions = panel0; // (the attempt does not stand)
+    c->mode_a_wide_compressions = wide0, c->slam_mode_a_compressions = slam0, c->slam_fused_batches = fused0, c->mode_a_panel_compressions = panel0, c->feat_class_batches = classes0; // (the attempt does not stand)
     if (attempt > 0) return set_err(OVGPU_ERR_NOT_SPD, "prior block of the involved variables not positive definite");
   }
   const int D = c->D, LD = c->LD;

@@ -469,7 +469,11 @@ static int featy_block_cols(const ovgpu_ctx *c) { return featy_block_rows(c) ? 3
 // Called when the batch is laid out; ovgpu_debug_option "layout_every_update" = 1 calls it at the head of every update as well, so that a
 // timing loop over a resident batch pays what a filter that hands over a new batch per frame pays inside ovgpu_set_features (bench.py's
 // headline since round 6).
-static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
+// second = true: the lists at 64 columns into fs_inst64 — the one-pass classes' of a batch whose longest fused track is the block-row kernel's
+// ("feat_classes").  The pass runs over the whole batch (the lists are indexed by feature, a class is a slot range) and, since the kernel ranks a
+// track's records on its way to the lists, writes measurement -> feature and the record positions again, the same values; the anchors and the
+// unprojected stack's tables are left out
+static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb, bool second = false) {
   const Batch b = batch_of(c);
   const int F = b.F;
   const bool fast = c->plan.msckf != FK_GENERAL && b.M > 0; // (the instance lists go with the fast path's other tables)
@@ -481,22 +485,28 @@ static int enqueue_batch_layout(ovgpu_ctx *c, bool anchors, int cb) {
     while (fpw_want < std::min(c->layout_fpw, (int)feat::BL_FPW) && (F + fpw_want - 1) / fpw_want > 250) fpw_want *= 2;
     const int fpw = fast ? std::max(1, std::min<int>(fpw_want, (int)((48 * 1024) / lds_one))) : 1;
     const size_t lds = fast ? (size_t)fpw * lds_one : 0;
-    const bool raw_tabs = fast && c->raw_tables_ok;
+    const bool raw_tabs = fast && c->raw_tables_ok && !second;
     RawStack rw; // the regions' constants for the run table (raw_stack_layout has run)
     for (int k = 0; k <= RAW_NEG; k++) rw.base[k] = c->raw_base[k], rw.ld[k] = c->raw_ld[k], rw.rcol[k] = c->raw_rcol[k];
     hipLaunchKernelGGL(feat::k_batch_layout, dim3((F + fpw - 1) / fpw), dim3(fast ? feat::BL_NTH * fpw : 64), lds, c->stream, F, m_max, c->D, (const int32_t *)b.meas_offsets, (const uint16_t *)b.meas_cc,
                        (const int32_t *)c->clone_col.p, (const int32_t *)c->calib_col.p, (const int32_t *)c->intr_col.p, anchors ? c->anchor_pre.p : (int32_t *)nullptr,
-                       fast ? c->fs_meas_feat.p : (int32_t *)nullptr, fast ? c->fs_pos.p : (int32_t *)nullptr, fast ? c->fs_inst.p : (int32_t *)nullptr, c->plan.nt, cb, c->C, c->K,
+                       fast ? c->fs_meas_feat.p : (int32_t *)nullptr, fast ? c->fs_pos.p : (int32_t *)nullptr, fast ? (second ? c->fs_inst64.p : c->fs_inst.p) : (int32_t *)nullptr, c->plan.nt, cb, c->C, c->K,
                        (const uint8_t *)c->cls_of_clone.p, (const int32_t *)c->raw_featbase.p, raw_tabs ? c->raw_dst.p : (int32_t *)nullptr,
                        raw_tabs ? c->raw_runs.p : (int32_t *)nullptr, rw);
     HIPCHK(hipGetLastError());
   }
-  c->inst_cb = fast ? cb : 0, c->inst_D = c->D;
+  if (second) c->inst64_D = fast ? c->D : 0;
+  else c->inst_cb = fast ? cb : 0, c->inst_D = c->D;
   return OVGPU_OK;
 }
 // the column-block lists again for another block width (enqueue_system: a switch that changes the sweep's block width was thrown after the layout)
 static int enqueue_instance_lists(ovgpu_ctx *c, int cb) { return enqueue_batch_layout(c, false, cb); }
-static int enqueue_batch_tables(ovgpu_ctx *c, bool anchors) { return enqueue_batch_layout(c, anchors, c->plan.msckf != FK_GENERAL ? featy_block_cols(c) : feat::FY_CB); }
+static int enqueue_instance_lists64(ovgpu_ctx *c) { return enqueue_batch_layout(c, false, feat::FY_CB, true); }
+static int enqueue_batch_tables(ovgpu_ctx *c, bool anchors) {
+  const int rc = enqueue_batch_layout(c, anchors, c->plan.msckf != FK_GENERAL ? featy_block_cols(c) : feat::FY_CB);
+  c->inst64_D = 0;
+  return rc == OVGPU_OK && c->plan.cls_mixed_width() ? enqueue_instance_lists64(c) : rc;
+}
 
 // The rows a feature of m measurements stacks.  MSCKF / delayed init: 2m - 3 after the nullspace projection (UpdaterHelper.cpp:449-450); SLAM
 // update: all 2m (UpdaterSLAM.cpp:381-383) less the `proj` rows a single-depth landmark's bearing takes (UpdaterSLAM.cpp:371-379: 3 - dof).
@@ -519,6 +529,13 @@ static void track_order(const int32_t *offsets, int F, int m_max, int32_t *order
   for (int f = 0; f < F; f++) start[m_max - (offsets[f + 1] - offsets[f]) + 1]++;
   for (int b = 0; b <= m_max; b++) start[b + 1] += start[b];
   for (int f = 0; f < F; f++) order[start[m_max - (offsets[f + 1] - offsets[f])]++] = f;
+}
+
+// Workgroups of a fused MSCKF kernel over `count` features: as many per CU as its registers (<4, 9, 2>: two; <8, 17, 1> and the block-row kernel:
+// one) and its LDS block of `lds` bytes allow, the features dealt round-robin over them (select_feat_kernel and the length classes' plan)
+static int fused_feat_grid(const ovgpu_ctx *c, FeatKernel k, size_t lds, int count) {
+  const int per_cu = k == FK_FEATY_BIG ? 1 : std::max(1, std::min(k == FK_FEATY_4 ? 2 : 1, (int)((size_t)c->lds_limit / std::max<size_t>(lds, 1))));
+  return std::max(1, std::min(count, c->num_cu * per_cu));
 }
 
 // The per-feature stage of batch b under the switches in force, as a value (FeatPlan, api_context.inc).  Pure: no HIP call, no reserve, nothing
@@ -549,8 +566,12 @@ static FeatPlan plan_feature_stage(const ovgpu_ctx *c, const Batch &b) {
   //  general kernel's; ovgpu_debug_option "anchored_fast" = 0 keeps such batches on the general kernel)
   // (resident landmarks under the empty active set have no column: the same batch, the same column map and the same kernels as without them.  The
   //  eligibility is recorded — lm_fast_ok — and only ovgpu_msckf_update_lm switches it on: enqueue_system, api_pipeline.inc)
-  if (!c->slam_rows && !c->no_feat_kernel && (c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D || c->anchored_fast) && (c->L == 0 || c->lm_empty_set) && m_max >= 2 && c->K * c->C <= 8192 && c->D >= 16 &&
-      (size_t)4 * (14 * m1 + 64) * sizeof(double) <= limit) { // (the last: k_feat_vt's block, in front of every one of them)
+  // (m: the longest track the fused kernels are to hold — the batch's; under "feat_classes" the longest of a fused class)
+  auto fast_terms = [&](int m) {
+    return !c->slam_rows && !c->no_feat_kernel && (c->dopt.feat_rep < OVGPU_REP_ANCHORED_3D || c->anchored_fast) && (c->L == 0 || c->lm_empty_set) && m >= 2 && c->K * c->C <= 8192 && c->D >= 16 &&
+           (size_t)4 * (14 * std::max(m, 1) + 64) * sizeof(double) <= limit; // (the last: k_feat_vt's block, in front of every one of them)
+  };
+  if (fast_terms(m_max)) {
     // the gate matrix of the one-pass kernels: 2 m + 4 rows (the right-hand sides [r | H_f] are four augmented rows, k_featy.h), upper triangle
     const int nt = (2 * m_max + 15) / 16, nta = (2 * m_max + 4 + 15) / 16, tiles = nta * (nta + 1) / 2;
     // <4 wavefronts, 9 tiles each>, or <8, 17> (one workgroup per CU: 256 registers per lane) — options.feature_kernel_shape = 2 asks for it where
@@ -559,6 +580,40 @@ static FeatPlan plan_feature_stage(const ovgpu_ctx *c, const Batch &b) {
     const bool holds = k == FK_FEATY_BIG ? nt <= 29 && c->feat_shape == 0 && feat::featyb_lds_layout(nt, 8).total <= limit
                                          : feat::featy_lds_layout(nt, nta, k == FK_FEATY_4 ? 4 : 8, feat::FY_CB).total <= limit;
     if (holds) pl.msckf = k, pl.nt = nt, pl.nta = nta;
+  }
+  // ---- ovgpu_debug_option "feat_classes" = 1: a kernel per length class (feat_classes.h) — the rule above applied per track, every term that
+  // reads no track length evaluated once, k_feat_vt's block sized by the longest FUSED track.  Only with the shape left to the library
+  // (options.feature_kernel_shape = 0, "featy_big" = 0, the fast path not switched off) and the track lengths on the host: a batch of
+  // ovgpu_set_features or ovgpu_tracks_to_features (begin_feature_batch), not a slice of one.  A batch of one class, and a batch one of whose
+  // classes does not fit its LDS carve, keeps the single-kernel rule above.
+  if (c->feat_classes >= 1 && c->feat_shape == 0 && !c->featy_big && !c->view && F > 0 && (int)b.h_order.size() == F && (int)b.h_offsets.size() == F + 1) {
+    const featcls::Partition pt = featcls::partition(b.h_offsets.p, b.h_order.p, F);
+    int first_fused = -1;
+    for (int k = pt.n - 1; k >= 0; k--)
+      if (pt.cls[k].kernel != featcls::FC_GENERAL) first_fused = k;
+    bool ok = pt.n >= 2 && first_fused >= 0 && fast_terms(pt.cls[first_fused].m_max);
+    // (the fast path's tables are built for EVERY track of such a batch, a general class's included: k_batch_layout keeps a track's keys in LDS,
+    //  enqueue_batch_layout gives a workgroup 48 KB at the most — a batch whose longest track needs more keeps the single-kernel rule)
+    ok = ok && feat::batch_layout_lds_ints(feat::batch_layout_m_pad(m1)) * sizeof(int32_t) <= (size_t)48 * 1024;
+    FeatPlan::Class cl[featcls::FC_MAX];
+    for (int k = 0; ok && k < pt.n; k++) {
+      FeatPlan::Class &q = cl[k];
+      q.kernel = (FeatKernel)pt.cls[k].kernel, q.begin = pt.cls[k].begin, q.end = pt.cls[k].end, q.m_max = pt.cls[k].m_max;
+      const int count = q.end - q.begin;
+      if (q.kernel == FK_GENERAL) { // the carve above: it was made for the batch's longest track, which is this class's
+        q.lds = pl.sys_lds, q.grid = std::max(1, std::min(count, c->num_cu * 4));
+        continue;
+      }
+      q.nt = featcls::tile_rows(q.m_max), q.nta = featcls::gate_tile_rows(q.m_max);
+      q.lds = q.kernel == FK_FEATY_BIG ? feat::featyb_lds_layout(q.nt, 8).total : feat::featy_lds_layout(q.nt, q.nta, q.kernel == FK_FEATY_4 ? 4 : 8, feat::FY_CB).total;
+      q.grid = fused_feat_grid(c, q.kernel, q.lds, count);
+      ok = q.lds <= limit;
+    }
+    if (ok) {
+      pl.n_classes = pt.n;
+      for (int k = 0; k < pt.n; k++) pl.cls[k] = cl[k];
+      pl.msckf = cl[first_fused].kernel, pl.nt = cl[first_fused].nt, pl.nta = cl[first_fused].nta, pl.m_fused = cl[first_fused].m_max;
+    }
   }
   pl.lm_fast_ok = c->L > 0 && pl.msckf != FK_GENERAL;
   // ---- SLAM batches: the fused per-feature kernel k_slam_y (k_slam_y.h) behind ovgpu_debug_option "slam_fused", a level.  Eligible at level 1:
@@ -604,7 +659,7 @@ static int size_feature_stage(ovgpu_ctx *c) {
   c->plan = pl;
   if (pl.rows_global) HIPCHK(c->sys_rows_ws.reserve((size_t)pl.sys_grid * m1 * c->row_stride));
   if (pl.gate_ws_stride) HIPCHK(c->gate_ws.reserve((size_t)pl.gate_ws_stride * pl.sys_grid));
-  if (pl.msckf == FK_FEATY_BIG) HIPCHK(c->featyb_ws.reserve((size_t)std::max(1, std::min(F, c->num_cu)) * feat::featyb_ws_doubles(pl.nt)));
+  if (pl.msckf == FK_FEATY_BIG) HIPCHK(c->featyb_ws.reserve((size_t)std::max(1, std::min(F, c->num_cu)) * feat::featyb_ws_doubles(pl.nt))); // (a block-row CLASS: no more workgroups, the same tile rows)
   if (pl.slam >= FK_SLAMY_BIG) { // k_slam_y_big.h: the row panels' scratch and what its records kernel leaves for it
     const size_t M = std::max(b.M, 1), Fs = std::max(F, 1);
     HIPCHK(c->featyb_ws.reserve((size_t)std::max(1, std::min(F, c->num_cu)) * feat::featyb_ws_doubles(pl.slam_nt)));
@@ -618,6 +673,7 @@ static int size_feature_stage(ovgpu_ctx *c) {
     const int M = std::max(b.M, 1);
     HIPCHK(c->fs_tq.reserve((size_t)std::max(F, 1) * 8));
     HIPCHK(c->fs_inst.reserve((size_t)std::max(F, 1) * std::max(pl.nt, 1) * feat::FY_ISTR));
+    if (pl.cls_mixed_width()) HIPCHK(c->fs_inst64.reserve((size_t)std::max(F, 1) * std::max(pl.nt, 1) * feat::FY_ISTR)); // (the same stride: one launch argument for both)
     HIPCHK(c->fs_rows.reserve((size_t)M * c->row_stride));
     HIPCHK(c->fs_minfo.reserve((size_t)M * 8));
     HIPCHK(c->fs_V.reserve((size_t)M * 6));

@@ -173,6 +173,7 @@ __global__ void __launch_bounds__(256) k_feat_vt(SysParams p, FeatStore st, doub
   double *hq = V + (size_t)6 * p.m_max;
   double *res = hq + 64; // [2 m] the residuals
   const int m0 = p.meas_offsets[f], m = p.meas_offsets[f + 1] - m0, n = 2 * m;
+  if (m > p.m_max) return; // (p.m_max sizes the block: the longest track of a fused class — a longer one is the general kernel's, "feat_classes"; nothing was written yet)
   const double *rows = st.rows + (size_t)m0 * RS;
   auto wsync = [] {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -287,7 +288,7 @@ __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_m
     if (threadIdx.x < K) tab_calib[threadIdx.x] = calib_col[threadIdx.x], tab_intr[threadIdx.x] = intr_col[threadIdx.x];
   }
   const int m0 = active ? meas_offsets[f] : 0, m = active ? meas_offsets[f + 1] - m0 : 0;
-  if (pos && tid == 0) grp_nt[grp] = (2 * m + 15) >> 4;
+  if (pos && tid == 0) grp_nt[grp] = min((2 * m + 15) >> 4, nt_max);
   if (anchor_pre && active && wv == (gth >> 6) - 1) { // the group's LAST wavefront: the keys of a track of up to 64 observations are the first one's work
     long long best = -1; // (run length << 32) | (2^31 - 1 - run start): the longest run, the earliest of equals
     int best_end = -1, carry_start = 0;
@@ -321,7 +322,7 @@ __global__ void __launch_bounds__(BL_NTH * BL_FPW) k_batch_layout(int F, int m_m
   int *keys = reinterpret_cast<int *>(smem); // [m], padded with INT_MAX to a multiple of 16
   int *cols3 = keys + m_max;                 // [m][3]
   int *cand = cols3 + 3 * m_max;             // [NT][24] first columns of the candidates, -1 = none
-  const int NT = (2 * m + 15) >> 4;
+  const int NT = min((2 * m + 15) >> 4, nt_max); // (a track longer than the lists' stride holds — the general kernel's, under "feat_classes" — is listed as far as its share goes and never read)
   int *kept = cand + 24 * ((2 * m_max + 15) >> 4); // [NT][24] list codes of the kept candidates, -1 = dropped
   __syncthreads(); // the column tables are in LDS
   for (int i = tid; i < ((m + 15) & ~15); i += BL_NTH) {
@@ -607,7 +608,7 @@ __device__ __forceinline__ double gate_ldl_chi2(d4 (&acc)[TPW], const int (&tij)
 template <int NW, int TPW, int OCC, bool F32OUT = false, int CB = FY_CB, bool CH = false>
 __global__ void __launch_bounds__(64 * NW, OCC)
     k_feat_y(SysParams p, int nt_max, int nta_max, const double *__restrict__ rowsG, const int32_t *__restrict__ minfoG, const double *__restrict__ VG,
-             const double *__restrict__ tqG, const int32_t *__restrict__ instG, const int32_t *__restrict__ slotsG, const int32_t *__restrict__ runsG) {
+             const double *__restrict__ tqG, const int32_t *__restrict__ instG, const int32_t *__restrict__ slotsG, const int32_t *__restrict__ runsG, int ist) {
   static_assert(!(CH && F32OUT), "the chains form is built for the float64 stack");
   // the parts that hold a register through the whole feature (the runs in four registers, the next status, the bound kept for the late verdict): the
   // four-wavefront shape has the room (240 registers, no scratch); the eight-wavefront shape spills already, takes the runs from the table per call and
@@ -676,6 +677,9 @@ __global__ void __launch_bounds__(64 * NW, OCC)
   // dependent scalar loads between two features.
   // CH: the record of the slot the loop takes next, requested a feature ahead, and (CHX) that feature's status behind it (the first ones: here).  A status
   // changes under this kernel's hands only when the feature's OWN workgroup rejects it: the one read a feature early is the one read at its head.
+  // The launch walks the p.F slot records at slotsG: the whole batch, or — a length class of it under ovgpu_debug_option "feat_classes" — the records
+  // from the class's first slot on, p.F the class's count (launch_feat_kernel).  The carve above — nt_max, nta_max — is then the CLASS's, while
+  // `ist`, the tile rows per feature of the instance lists, stays the batch's.
   int nrec[6] = {0, 0, 0, 0, 0, 0}, nstatus = 0;
   if (CH && (int)blockIdx.x < p.F) {
     const int32_t *rec = slotsG + (size_t)8 * blockIdx.x;
@@ -810,7 +814,7 @@ __global__ void __launch_bounds__(64 * NW, OCC)
     // ------------------------------------------------------------------ prologue: T, the bound and the reflectors' DMA (CH: requested above), the tile
     // rows' last columns; the residual column of the stack and the gate's bound were left by k_feat_vt
     if (!CH) head_loads();
-    const int32_t *finst = instG + (size_t)f * nt_max * FY_ISTR; // per tile row: count, last non-zero column, block starts, instances (k_feat_vt)
+    const int32_t *finst = instG + (size_t)f * ist * FY_ISTR; // per tile row: count, last non-zero column, block starts, instances (k_feat_vt)
     if (tid < NT) rowlim[tid] = finst[(size_t)tid * FY_ISTR + 1];
     out.pad(tid, NTH, n_out, LD);
     // (1 - 1e-9): the bound is a float64 sum of ~100 squares and the reference's own chi2 carries ~1e-12 of rounding: a feature
@@ -1071,7 +1075,7 @@ __global__ void __launch_bounds__(64 * NW, OCC)
   X(4, 9, 2, false, 64, true) X(8, 17, 1, false, 64, true)
 #define OVG_FEATY_ARGS                                                                                                                           \
   SysParams, int, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__, const double *__restrict__, \
-      const int32_t *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__
+      const int32_t *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, int
 
 } // namespace feat
 } // namespace ovg

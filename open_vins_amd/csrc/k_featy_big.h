@@ -56,7 +56,7 @@ __host__ __device__ inline size_t featyb_ws_doubles(int nt_max) { return (size_t
 template <int NW, int TPW, bool F32OUT = false>
 __global__ void __launch_bounds__(64 * NW, 1)
     k_feat_y_big(SysParams p, int nt_max, const double *__restrict__ rowsG, const int32_t *__restrict__ minfoG, const double *__restrict__ VG,
-                 const double *__restrict__ tqG, const int32_t *__restrict__ instG, const int32_t *__restrict__ slotsG, double *wsG) {
+                 const double *__restrict__ tqG, const int32_t *__restrict__ instG, const int32_t *__restrict__ slotsG, double *wsG, int ist) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NTH = 64 * NW;
   static_assert(FB_PF * NTH >= 30 * 256, "a fetched row panel must fit the prefetch registers");
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(64 * NW, 1)
   // the scratch is read back by other wavefronts of this workgroup: past the vector cache (it may hold the previous track's panels)
   auto ld_l2 = [](const double *ptr) { return __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 
-  for (int slot = blockIdx.x; slot < p.F; slot += gridDim.x) { // static schedule over the slot records (k_featy.h)
+  for (int slot = blockIdx.x; slot < p.F; slot += gridDim.x) { // static schedule over the launch's p.F slot records (k_featy.h: the batch's, or a length class's; `ist`: the lists' stride, the batch's)
     lds_barrier();
     const int32_t *rec = slotsG + (size_t)8 * slot;
     const int f = __builtin_amdgcn_readfirstlane(rec[0]);
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(64 * NW, 1)
                                          (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(Vl) + 1024 * ch), 16, 0, 0);
       }
     }
-    const int32_t *finst = instG + (size_t)f * nt_max * FY_ISTR;
+    const int32_t *finst = instG + (size_t)f * ist * FY_ISTR;
     if (tid < NT) rowlim[tid] = finst[(size_t)tid * FY_ISTR + 1];
     out.pad(tid, NTH, n_out, LD);
     const double bound = tqG[(size_t)8 * f + 6];

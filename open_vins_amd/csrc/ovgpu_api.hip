@@ -48,6 +48,7 @@
 #include "ovgpu_types.h"
 #include "dev_buf.h"
 #include "host_link.h"
+#include "feat_classes.h"
 
 // The fused per-feature kernels live in the second translation unit (ovgpu_featy_tu.hip: its own scheduler strategy); here they are
 // only declared, so that their launches below bind to those definitions.
@@ -57,11 +58,11 @@ namespace feat {
 OVG_FEATY_SHAPES(X)
 #undef X
 extern template __global__ void k_feat_y_big<8, 17, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
-    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
+    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *, int);
 extern template __global__ void k_feat_y_big<8, 17, true>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
-    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
+    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *, int);
 extern template __global__ void k_feat_y_big<8, 5, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
-    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
+    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *, int);
 } // namespace feat
 namespace slamy { // ... and k_slam_y_big.h's, defined in ovgpu_slamy_big_tu.hip
 extern template __global__ void k_slam_rows_big<false>(SysParams, SlamYBigStore);

@@ -29,10 +29,10 @@ namespace feat {
 OVG_FEATY_SHAPES(X)
 #undef X
 template __global__ void k_feat_y_big<8, 17, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
-    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
+    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *, int);
 template __global__ void k_feat_y_big<8, 17, true>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
-    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
+    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *, int);
 template __global__ void k_feat_y_big<8, 5, false>(SysParams, int, const double *__restrict__, const int32_t *__restrict__, const double *__restrict__,
-    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *);
+    const double *__restrict__, const int32_t *__restrict__, const int32_t *__restrict__, double *, int);
 } // namespace feat
 } // namespace ovg
